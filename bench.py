@@ -10,9 +10,17 @@ One "step" = one mini-batch decoder update (gather latents -> forward, mode 'tra
 -> 3 focal losses + rate terms -> backward -> [RCCL all-reduce of the flat decoder gradient] -> fused Adam),
 NVFPCC.py:149-223 minus its logging syncs, on `--batch` blocks PER GPU (weak scaling: the global
 mini-batch is batch x N).  Inputs (grids, latent table, weights) are resident in HBM before the timed region.
-Rank 0 prints ONE JSON line.  Beside the step number the line carries `epoch`: whole epochs of NVFPCC.py train
+Rank 0 prints ONE JSON line.  With --full, beside the step number the line carries `epoch`: whole epochs of NVFPCC.py train
 (58 mini-batches incl. the short last one + the full-batch latent step + the log line's device sums, eval on
 every 10th) as end-to-end blocks/s -- what a user of the CLI sees.
+
+A plain run does only what the headline needs: set-up, the W warm-up steps, ONE timed region of exactly K steps, the
+outputs (--dump-outputs DIR) and the line.  Everything else the line can carry -- the repeat regions, `roofline` (host-launched
+probe steps and the rocprofv3 child passes), `sustained`, `direct_form`, `epoch`, `sweep` and `cpu_baseline` -- runs with
+--full only (each still has its --no-* switch there):
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_outputs   # + the last timed step's outputs
+    python bench.py --full                                                         # the whole line
 """
 import argparse
 import csv
@@ -60,10 +68,16 @@ def parse_args(argv=None):
     ap.add_argument("--chanstr", default="8,16,8,8")
     ap.add_argument("--q", type=int, default=1)
     ap.add_argument("--mode", choices=["step", "epoch"], default="step",
-                    help="epoch: time whole NVFPCC.py-train epochs only (the default run reports both)")
+                    help="epoch: time whole NVFPCC.py-train epochs only (a --full step run reports both)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: repeat regions, roofline (probe steps, rocprofv3 "
+                         "child passes), sustained, direct_form, epoch, sweep, cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--epochs", type=int, default=10, help="epochs timed for the `epoch` object")
     ap.add_argument("--no-epoch", action="store_true", help="skip the epoch object (profiling runs: step kernels only)")
-    ap.add_argument("--repeats", type=int, default=3, help="timed regions of --steps steps each (value = the first)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each (value = the first); default 3 with --full, else 1")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="do not run the two rocprofv3 --pmc child passes for roofline.traffic")
     ap.add_argument("--prime-rounds", type=int, default=1, help="passes over the captured graphs before the warm-up steps")
@@ -113,6 +127,44 @@ def build_engine(args, device, world):
                       lr=1e-3, wemb=5.0, seed=0)
     nd.attach(eng, world, force=args.force_collective)
     return eng
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20     # --dump-outputs: all files together
+DUMP_MAX_BLOCKS = 128               # ... per-block arrays keep a fixed sample of this many blocks beyond it
+
+
+def step_outputs(eng, a):
+    """What a caller of the timed path holds after its last step: the three heads' probabilities of that step (`a`, the
+    activations the step returned; None in --mode epoch), its loss terms and rate bits, the objective, and the state the
+    step leaves behind -- decoder parameters, their gradient, Adam's moments -- with the latent table."""
+    import numpy as np
+    out = {k: a[k] for k in ("p0", "p1", "p2") if a is not None and a.get(k) is not None}
+    t = eng.last
+    out.update(loss_terms=t["loss_terms"], latent_bits=t["latent_bits"], net_bits=t["net_bits"],
+               loss=np.array([eng.loss_value()], np.float64),
+               params=eng.flat_p, grads=eng.flat_g, adam_m=eng.flat_m, adam_v=eng.flat_v, latents=eng.emb)
+    return out
+
+
+def write_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES, max_blocks=DUMP_MAX_BLOCKS):
+    """DIR/<name>.npy per array, float64 kept, everything else as float32.  An array of more than one dimension is
+    per block (first axis); beyond `max_blocks` blocks it keeps a sample of them drawn from a fixed seed, the same rows in
+    every run of the same shape.  Returns the bytes written."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    conv = {}
+    for name, x in arrays.items():
+        x = np.asarray(x.detach().cpu().numpy() if hasattr(x, "detach") else x)
+        x = x.astype(np.float64 if x.dtype == np.float64 else np.float32)
+        if x.ndim > 1 and x.shape[0] > max_blocks:
+            x = x[np.sort(np.random.default_rng(0).choice(x.shape[0], max_blocks, replace=False))]
+        conv[name] = np.ascontiguousarray(x)
+    total = sum(x.nbytes for x in conv.values())
+    if total > limit:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {limit}-byte limit")
+    for name, x in conv.items():
+        np.save(os.path.join(dirname, name + ".npy"), x)
+    return total
 
 
 class KernelProbe:
@@ -258,7 +310,7 @@ def measure_traffic(args, label):
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = os.path.join(base, counter)
         cmd = [rocprof, "--kernel-trace", "--pmc", counter, "-d", d, "-o", "pmc", "--output-format", "csv", "--",
-               "python3", os.path.abspath(__file__), "--pmc-child", "--pmc-mark", label, "--no-cpu-baseline", "--no-pmc",
+               "python3", os.path.abspath(__file__), "--full", "--pmc-child", "--pmc-mark", label, "--no-cpu-baseline", "--no-pmc",
                "--no-graph", "--no-sweep", "--no-epoch", "--steps", "6", "--warmup", "3", "--repeats", "1", "--batch",
                str(args.batch), "--blocks", str(args.blocks), "--distinct", str(args.distinct), "--ch", str(args.ch),
                "--chanstr", args.chanstr, "--q", str(args.q)]
@@ -303,7 +355,7 @@ def measure_in_step_us(args, labels):
         return {}, {}, "rocprofv3 not found"
     base = tempfile.mkdtemp(prefix="nvf_trace_", dir="/tmp")
     cmd = [rocprof, "--kernel-trace", "-d", base, "-o", "kt", "--output-format", "csv", "--",
-           "python3", os.path.abspath(__file__), "--pmc-child", "--pmc-mark", ",".join(labels), "--no-cpu-baseline",
+           "python3", os.path.abspath(__file__), "--full", "--pmc-child", "--pmc-mark", ",".join(labels), "--no-cpu-baseline",
            "--no-pmc", "--no-sweep", "--no-epoch", "--steps", "48", "--warmup", "4", "--repeats", "1",
            "--batch", str(args.batch), "--blocks", str(args.blocks), "--distinct", str(args.distinct), "--ch", str(args.ch),
            "--chanstr", args.chanstr, "--q", str(args.q)] + (["--no-graph"] if args.no_graph else [])
@@ -363,7 +415,7 @@ def run(args):
     ops.set_naive(args.naive)
     eng = build_engine(args, device, world)
     B = args.batch
-    nreg = max(args.repeats, 1)
+    nreg = max(args.repeats if args.repeats is not None else (3 if args.full else 1), 1)
 
     # epoch order shared by every rank (seeded), global mini-batch = B * world
     rng = np.random.default_rng(1234)
@@ -427,9 +479,8 @@ def run(args):
     def step(i, use_graph=True):
         ids, n_pts = shares(i)
         if graphed is not None and use_graph:
-            graphed(ids, n_pts=n_pts)
-        else:
-            eng.train_step(ids, args.q, n_pts=n_pts)
+            return graphed(ids, n_pts=n_pts)
+        return eng.train_step(ids, args.q, n_pts=n_pts)
 
     def stage_steps(lo, hi):
         """Host half of the schedule of steps [lo, hi) (which blocks, n_pts, noise steps, Adam coefficients as rows in
@@ -444,23 +495,24 @@ def run(args):
     def run_steps(lo, hi, staged=None):
         """Steps [lo, hi): with the graph, ONE host-to-device copy of their schedule ((hi - lo) x (B + 3) words; the copy is
         inside the timed region, the rows were filled before it when `staged` is given), then the unrolled graph replays;
-        without the graph, host-launched steps."""
+        without the graph, host-launched steps.  Returns the activations of the last step (None if there was none)."""
+        a = None
         if graphed is None:
             for i in range(lo, hi):
-                step(i)
-            return
+                a = step(i)
+            return a
         if staged is not None:
             graphed.load_schedule(staged)
-            graphed.replay_all()
-            return
+            return graphed.replay_all()
         i = lo
         W = B * world
         while i < hi:
             e = min(hi, i + graphed.CAP)
             whole = np.asarray(order[i * W:e * W], np.int64).reshape(e - i, W)        # the steps' mini-batches
             graphed.load_schedule((whole[:, rank::world], counts[whole].sum(axis=1).astype(np.float64)))
-            graphed.replay_all()
+            a = graphed.replay_all()
             i = e
+        return a
 
     def barrier():
         torch.cuda.synchronize()
@@ -485,7 +537,7 @@ def run(args):
             staged = stage_steps(nxt, nxt + args.steps)
             barrier()
             t0 = time.perf_counter()
-            run_steps(nxt, nxt + args.steps, staged)
+            last_a = run_steps(nxt, nxt + args.steps, staged)
             t_host = time.perf_counter() - t0
             barrier()
             d = timed_max(time.perf_counter() - t0)
@@ -495,9 +547,11 @@ def run(args):
             region_ms.append(d / args.steps * 1e3)
             if dt is None:
                 dt = d
+                if args.dump_outputs and rank == 0:      # the contract's K steps: the same state with or without --full
+                    write_outputs(args.dump_outputs, step_outputs(eng, last_a))
         # kernels inside a replayed graph cannot be bracketed by events: time the dominant kernels on the same stream
         # in the same process right after the timed region, same shapes and operands, launched from the host
-        if not (args.pmc_child and graphed is not None):        # (a graph-mode child pass has its markers in the graphs)
+        if args.full and not (args.pmc_child and graphed is not None):   # (a graph-mode child pass has its markers in the graphs)
             probe.enabled = not args.pmc_child
             probe.mark = args.pmc_mark or None
             for i in range(nxt, nxt + min(args.steps, 10)):
@@ -513,7 +567,7 @@ def run(args):
     # by HIP events on the compute stream (no host synchronisation inside the region); ms / step of the first and the
     # last tenth show whether the clock holds.
     sustained_obj = None
-    if args.mode == "step" and graphed is not None and args.sustained_s > 0 and region_ms:
+    if args.full and args.mode == "step" and graphed is not None and args.sustained_s > 0 and region_ms:
         per_part = max(int(args.sustained_s / 10 / (region_ms[0] * 1e-3)) // 16 * 16, 16)
         per_part = min(per_part, graphed.CAP // 16 * 16)
         srng = np.random.default_rng(77)
@@ -551,7 +605,7 @@ def run(args):
     # (tests/test_gpu_engine.py::test_direct_forms_follow_the_reference_trajectory_to_rounding); the headline runs the
     # reduced-multiplication (Winograd) forms, whose trajectory parity is statistical
     direct_obj = None
-    if args.mode == "step" and graphed is not None and not args.no_direct:
+    if args.full and args.mode == "step" and graphed is not None and not args.no_direct:
         from nvfpcc_amd import engine as _E
         saved = _E._WINO
         _E._WINO = False
@@ -588,7 +642,7 @@ def run(args):
     # ---- whole epochs of NVFPCC.py train: mini-batches (graph replay; the short last batch replays a graph of its own size), the
     # full-batch latent step on this rank's shard, the device-side sums of the log line, eval on every 10th epoch
     epoch_obj = None
-    if (args.mode == "epoch" or not args.no_graph) and not (args.no_epoch and args.mode == "step"):
+    if args.mode == "epoch" or (args.full and not args.no_graph and not args.no_epoch):
         N = args.blocks
         drv = EpochDriver(eng, B * world, rank, world, use_graph=not args.no_graph)
         lo, hi = nd.shard_range(N, rank, world)
@@ -632,6 +686,8 @@ def run(args):
         if args.mode == "epoch":
             dt = de
             loss = float("nan")
+            if args.dump_outputs and rank == 0:
+                write_outputs(args.dump_outputs, step_outputs(eng, None))
 
     blocks_per_s = (args.steps * B * world / dt) if args.mode == "step" else args.blocks * args.epochs / dt
 
@@ -648,7 +704,7 @@ def run(args):
         "all-reduce captured in the step graph" if (graphed is not None and graphed.collective == "graph")
         else "all-reduce launched from the host")
     extra = {}
-    if not args.no_sweep and args.mode == "step":
+    if args.full and not args.no_sweep and args.mode == "step":
         fwd_macs = FWD_MACS.get(args.chanstr, 0)
         frac = lambda bps, flop_per_block: round(bps / world * flop_per_block / 1e12 / PEAK_FP32_TFLOPS, 4)
 
@@ -821,7 +877,7 @@ def run(args):
             "warmup": args.warmup, "ms_per_step": round(dt / (args.steps if args.mode == "step" else args.epochs) * 1e3, 4),
             "higher_is_better": True,
             "scaling": "weak" if args.mode == "step" else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": workload,
+            "config": {"workload": workload, "full": args.full,
                        "launch": launch_desc, "collective": collective_desc,
                        "primed_steps": primed_steps,      # optimiser steps run before the W warm-up steps (every captured
                        # graph launched once): parameters / Adam moments / noise counters have advanced by that many
@@ -850,7 +906,7 @@ def run(args):
             out["epoch"] = epoch_obj
         if extra:
             out["sweep"] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), file=json_out, flush=True)
     if torch.distributed.is_initialized():

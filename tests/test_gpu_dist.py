@@ -123,7 +123,7 @@ def test_bench_gpus_2_launches_two_ranks_and_reports_the_live_world_size(tmp_pat
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "12", "--warmup", "3",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "12", "--warmup", "3",
                         "--epochs", "1", "--blocks", "61", "--distinct", "61", "--no-pmc", "--no-cpu-baseline",
                         "--sweep-blocks", "300", "--sustained-s", "0.2"],
                        env=env, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=500)
