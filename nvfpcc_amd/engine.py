@@ -26,18 +26,11 @@ from ._lib import lib, check
 from .network import NoiseState
 
 R, S, NONE = ops.ACT_RELU, ops.ACT_SIGMOID, ops.ACT_NONE
-_TAIL = os.environ.get("NVF_TAIL", "1") != "0"   # latent backward as one workgroup of a later launch (0: three launches)
-_STEM = os.environ.get("NVF_STEM", "1") != "0"   # fused stem launches (0: per-layer kernels)
-_G16 = os.environ.get("NVF_G16", "1") != "0"     # matrix-core kernels of the wide decoder (0: the VALU tile kernels)
-_VAR = {k: int(os.environ.get("NVF_VAR_" + k, "0")) for k in ("UP1F", "UP2F", "UP1B", "UP2B", "C1F", "C1B")}   # tile variants
-_CONV2_FWD_VAR = int(os.environ.get("NVF_CONV2_FWD_VAR", "0"))   # tile-shape variants of conv_k4_mfma (tuning)
-_CONV2_BWD_VAR = int(os.environ.get("NVF_CONV2_BWD_VAR", "0"))
-_WINO = os.environ.get("NVF_WINO", "1") != "0"   # conv2's / conv1's backward-data in the Winograd (y, x) form (conv_wino.hip)
-_WINO_FWD = os.environ.get("NVF_WINO_FWD", "1") != "0"   # ... and conv2's forward in TRAINING steps (never in eval)
-_WINO_C1 = os.environ.get("NVF_WINO_C1", "1") != "0"     # conv1's backward-data as well
+# winograd=None: the 4^3 layers of a training step in the Winograd (y, x) form (conv_wino.hip, conv16_wino.hip);
+# NVF_WINO=0 keeps the direct summation order (the strict-trajectory engine)
+_WINO = os.environ.get("NVF_WINO", "1") != "0"
 # (conv1's training FORWARD in that form: measured slower at batch 16 -- 19.1 us two-set / 16.7 us one-set kernel against
 # 12.2 us for the direct kernel, r05 A/B -- 16^3 outputs do not amortise the transforms; used above batch 64 only)
-_CONVT_EDGE = os.environ.get("NVF_CONVT_EDGE", "1") != "0"   # up1 / up2 training forward: kx = 4 taps on rows (co, ey)
 
 
 def _wino_bwd_ppc(g_out):
@@ -52,23 +45,17 @@ def _wino_bwd_ppc(g_out):
     return 18 if g_out.shape[-1] == 32 else 10
 
 
-_WINO16 = os.environ.get("NVF_WINO16", "1") != "0"       # the wide decoder's 4^3 layers in that form (conv16_wino.hip)
-# ... bias sums of the layer below from its backward-data epilogue: measured neutral (the reduction launch 48.9 -> 44.0 us
-# without its 51 MB of re-reads, the two epilogues + 2.7 / + 2.1 us): off by default
-_WINO16_BIAS = os.environ.get("NVF_WINO16_BIAS", "0") != "0"
-_WINO16_WGRAD = tuple(int(v) for v in os.environ.get("NVF_WINO16_WGRAD", "32,16").split(",") if v)   # ... weight gradients (dY extents)
-_GRAPH_LAST = os.environ.get("NVF_GRAPH_LAST_BATCH", "1") != "0"     # the short last mini-batch of an epoch as a graph too
-_UP1B_KSPLIT = os.environ.get("NVF_UP1B_KSPLIT", "1") != "0"   # up1's backward-data: channel groups on different waves
-_HEADS_FWD_IN_LOSS = os.environ.get("NVF_HEADS_FWD_IN_LOSS", "1") != "0"   # heads' forward inside the loss launch
-_HEAD_BIAS_IN_LOSS = os.environ.get("NVF_HEAD_BIAS_IN_LOSS", "1") != "0"   # heads' bias gradients from the loss launch
-_SUMS_IN_TRUNK5 = os.environ.get("NVF_SUMS_IN_TRUNK5", "1") != "0"   # partial bias sums inside the five-gradient launch
-_HEADS_IN_TRUNK5 = os.environ.get("NVF_HEADS_IN_TRUNK5", "1") != "0"   # heads' weight gradients as workgroups of the five-gradient launch
+# One-launch groupings of the step.  Plain constants: tests/test_gpu_engine.py switches the first four off to build the
+# separate-launch reference its bit-equality tests compare against; bench.py reads _HEADS_IN_TRUNK5.
+_HEAD_BIAS_IN_LOSS = True   # heads' bias gradients from the loss launch
+_SUMS_IN_TRUNK5 = True      # partial bias sums inside the five-gradient launch
 # the stem's backward (conv0^T -> IGDN' -> up0^T, up0's gradients) as the first workgroups of the five-gradient launch
 # instead of two launches in front of it (csrc/stem_bwd.h): it needs g1 only and feeds the latent tail only
-_STEM_IN_TRUNK5 = os.environ.get("NVF_STEM_IN_TRUNK5", "1") != "0"
+_STEM_IN_TRUNK5 = True
 # the stem's FORWARD (latent generator + quantiser + up0 / IGDN / conv0) inside the step head's launch: its workgroups
 # derive their weights from the raw parameters, so the two latency-bound launches have nothing to wait for in each other
-_STEM_IN_HEAD = os.environ.get("NVF_STEM_IN_HEAD", "1") != "0"
+_STEM_IN_HEAD = True
+_HEADS_IN_TRUNK5 = True     # heads' weight gradients as workgroups of the five-gradient launch (narrow decoder)
 
 
 def _NAIVE_OFF():
@@ -83,14 +70,6 @@ MFMA_BWD = {"conv1": (2, 64), "conv2": (0, 64)}
 _DESC = np.dtype([("kernel", "<u8"), ("kernel_init", "<u8"), ("b", "<u8"), ("b_init", "<u8"), ("w_fwd", "<u8"),
                   ("w_bwd", "<u8"), ("b_eff", "<u8"), ("dim0", "<i4"), ("dim1", "<i4"), ("k3", "<i4"),
                   ("kind", "<i4"), ("quantised", "<i4"), ("layer_id", "<i4"), ("nbias", "<i4"), ("pad", "<i4")])
-
-
-class _NullCtx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        return False
 
 
 class _Layer:
@@ -145,16 +124,10 @@ class TrainEngine:
         self.last = {}
         # per-step scalars live in device memory while a captured HIP graph replays (see GraphedTrainStep)
         self._step_dev = None     # uint64 noise-step offset
-        # second HIP stream: weight gradients, head backward-data, bias sums and the weight-rate term do not sit on
-        # the backward-data chain, so they overlap with it (at batch 16 one kernel cannot fill 256 CUs by itself)
-        self.side = torch.cuda.Stream(device=self.dev)
-        # Measured at batch 16 once the kernels were fast (round 1): running the side jobs concurrently no longer
-        # shortens the step (0.828 ms either way) -- every kernel fills the chip on its own -- so the default is
-        # one stream; NVF_OVERLAP=1 turns the two-stream schedule back on.
-        self.allow_overlap = os.environ.get("NVF_OVERLAP", "0") == "1"
-        self.fused_stem = ((self.narrow or self.wide) and net.entropy_coder.sigma.shape[1] <= 8 and _STEM)
+        # every launch of a step goes to the current stream: a two-stream schedule stopped paying once the kernels were
+        # fast (round 1, batch 16: 0.828 ms either way -- every kernel fills the chip on its own)
+        self.fused_stem = (self.narrow or self.wide) and net.entropy_coder.sigma.shape[1] <= 8   # stem in fused launches
         self.fused_latent_stem = True      # latent generator + quantiser ride in the stem's forward launch
-        self.overlap = True
         self._g_lat_dev = None    # lambda * w1 / n_pts
         self._wg = None
         self.ctx = ops.StepCtx()  # deferred final passes + queued latent tail of the step in flight (caller-owned)
@@ -168,7 +141,6 @@ class TrainEngine:
         self._graphs_captured = 0  # GraphedTrainStep instances that baked this engine's buffers into a graph
         self.tail_done = False    # the last backward pass applied the optimiser itself (fused tail)
         self._stem_gdn_in_finals = False
-        self._stem_pre = None     # (idx pointer, mode, tensors) of a stem forward the step head's launch already ran
         self._tail_ranges = {}    # gradient index ranges no fused launch covers, per set of covered intervals
         self.collective_mode = None   # "graph" / "host": where GraphedTrainStep puts the all-reduce (dist.attach)
         # the three classifier heads go through the one-launch kernels (instantiated for the two decoders of BASELINE.json);
@@ -225,7 +197,7 @@ class TrainEngine:
                 # matrix-core form of the padding-0 transposed convolutions: forward, and backward-data (a
                 # stride-2 gather convolution with cin output channels)
                 L.wp_t = torch.empty(int(lib().nvf_pack_convT_mfma_floats(L.cin)), device=self.dev)
-                if self.winograd and _CONVT_EDGE:
+                if self.winograd:
                     # the forward of TRAINING steps with the kx = 4 taps on rows (co, ey): 65 instead of 75 A fragments per
                     # channel group, another summation order for the even x outputs (pack kind 12, kernel variant 15);
                     # evaluation / encode / decode keep wp_t
@@ -240,11 +212,10 @@ class TrainEngine:
                     # flattened 18-cell rows (conv2; faster than the VALU kernel only while the batch is small)
                     L.bwd_pair, L.bwd_max_batch = MFMA_BWD[name]
                     L.wp_b = torch.empty(int(lib().nvf_pack_mfma_k4_floats(L.cout, L.bwd_pair)), device=self.dev)
-                if self.winograd and (name == "conv2" or (name == "conv1" and _WINO_C1)):
+                if self.winograd and name in ("conv2", "conv1"):
                     # backward-data in the reduced-multiplication form (Winograd over (y, x), z pairs on the matrix
-                    # cores: 52 us against 85 for the direct form at batch 16)
+                    # cores: 52 us against 85 for the direct form at batch 16) ...
                     L.wp_w = torch.empty(int(lib().nvf_pack_wino_k4_floats()), device=self.dev)
-                if self.winograd and _WINO_FWD and name in ("conv2", "conv1"):
                     # ... and the forward of TRAINING steps (mode 'train': NVFPCC.py:160, 234); the eval / encode / decode
                     # forward keeps the direct fixed-order kernel (bit-exact batch invariance, the occupancy contract).
                     # conv1 only above batch 64 (the full-batch latent step: 207 us against 375 for the direct kernel at
@@ -252,10 +223,10 @@ class TrainEngine:
                     L.wp_wf = torch.empty(int(lib().nvf_pack_wino_k4_floats()), device=self.dev)
             # wide decoder (16 / 32 channels): the output channels are the MFMA rows (conv16_mfma.hip) -- conv1 / conv2
             # forward and backward-data, and the backward-data of up2 / up1 (stride-2 gather with cin output channels)
-            if _G16 and self.wide and L.k == 4 and L.cin == 16 and L.cout == 16 and L.pad == 0 and name in ("conv1", "conv2"):
+            if self.wide and L.k == 4 and L.cin == 16 and L.cout == 16 and L.pad == 0 and name in ("conv1", "conv2"):
                 L.wp_gf = torch.empty(int(lib().nvf_pack_g16_mfma_floats(16, 16, 4)), device=self.dev)
                 L.wp_gb = torch.empty(int(lib().nvf_pack_g16_mfma_floats(16, 16, 4)), device=self.dev)
-                if self.winograd and _WINO16:
+                if self.winograd:
                     # the Winograd (y, x) form with the 16 output channels as MFMA rows (conv16_wino.hip), training steps
                     # only: conv2 backward-data 257 -> 140 us, forward 170 -> 95, conv1 backward-data 59 -> 33 at batch 16.
                     # conv1's FORWARD stays direct (27 -> 25 us would cost the engine == operator-path agreement its 2e-5:
@@ -263,14 +234,14 @@ class TrainEngine:
                     L.wp_w = torch.empty(int(lib().nvf_pack_wino16_k4_floats()), device=self.dev)
                     if name == "conv2":
                         L.wp_wf = torch.empty(int(lib().nvf_pack_wino16_k4_floats()), device=self.dev)
-            if _G16 and self.wide and L.k == 5 and L.cout == 16 and L.cin in (16, 32) and L.pad == 0 and name in ("up1", "up2"):
+            if self.wide and L.k == 5 and L.cout == 16 and L.cin in (16, 32) and L.pad == 0 and name in ("up1", "up2"):
                 L.wp_gb = torch.empty(int(lib().nvf_pack_g16_mfma_floats(16, L.cin, 5)), device=self.dev)
-            if _G16 and self.wide and L.k == 5 and (name, L.cin, L.cout, L.pad) in (("up1", 32, 16, 0), ("up2", 16, 16, 0),
+            if self.wide and L.k == 5 and (name, L.cin, L.cout, L.pad) in (("up1", 32, 16, 0), ("up2", 16, 16, 0),
                                                                       ("conv0", 16, 32, 2), ("up0", 8, 16, 2)):
                 L.wp_t16 = torch.empty(int(lib().nvf_pack_convT16_mfma_floats(L.cin, L.cout)), device=self.dev)
-            if _G16 and self.wide and name == "up0" and L.cin == 8 and L.cout == 16 and L.pad == 2:     # 16 -> 8 channels, rows 8..15 zero
+            if self.wide and name == "up0" and L.cin == 8 and L.cout == 16 and L.pad == 2:     # 16 -> 8 channels, rows 8..15 zero
                 L.wp_gb = torch.empty(int(lib().nvf_pack_g16_mfma_floats(16, 8, 5)), device=self.dev)
-            if _G16 and self.wide and name == "conv0" and L.cin == 16 and L.cout == 32 and L.pad == 2:
+            if self.wide and name == "conv0" and L.cin == 16 and L.cout == 32 and L.pad == 2:
                 L.wp_gb = torch.empty(int(lib().nvf_pack_g16_mfma_floats(32, 16, 5)), device=self.dev)
             self.layers[name] = L
             t = table[i]
@@ -342,9 +313,11 @@ class TrainEngine:
 
     def batch_and_prepare(self, idx_dev, q, with_rate=False, stem_mode=None):
         """_batch(idx_dev) and prepare_weights(q) -- row gather, effective weights, MFMA packings -- as ONE launch
-        (``with_rate``: + the weight-rate term's partial sums, consumed by the backward pass of the same step;
-        ``stem_mode`` = 'train' / 'eval': + the stem's forward of forward(e, stem_mode, idx_dev), which must be the next
-        call -- narrow decoder, nvf_step_head_stem)."""
+        (``with_rate``: + the weight-rate term's partial sums, consumed by the backward pass of the same step).  Returns
+        the five gathered tensors (gt, dist, gt16, gt8, e).  ``stem_mode`` = 'train' / 'eval': + the stem's forward of
+        this mini-batch in the same launch where the decoder has one (nvf_step_head_stem); a sixth member is then the
+        dict of its activations for forward(e, stem_mode, idx_dev, stem=...), or None if the caller's forward() has to
+        run the stem itself."""
         import ctypes
         srcs = [self.gt, self.dist, self.gt16, self.gt8, self.emb]
         n, rows = len(srcs), idx_dev.numel()
@@ -360,10 +333,9 @@ class TrainEngine:
                 iarr([m[1] for m in meta]), npk, (ctypes.c_void_p * n)(*[s.data_ptr() for s in srcs]),
                 (ctypes.c_void_p * n)(*[d.data_ptr() for d in dsts]), (ctypes.c_int * n)(*[s[0].numel() for s in srcs]), n,
                 idx_dev.data_ptr(), rows, ctypes.byref(self._rate_job()[0]) if with_rate else None)
-        self._stem_pre = None
-        if (stem_mode is not None and _STEM_IN_HEAD and (self.narrow or self.wide) and self.fused_stem and self.fused_latent_stem
-                and self.ch <= 8 and rows <= 32 and _NAIVE_OFF()):
-            # ... and the stem's forward of this mini-batch (forward() picks the tensors up instead of launching it)
+        o = None
+        if (stem_mode is not None and _STEM_IN_HEAD and self.fused_stem and self.fused_latent_stem and rows <= 32
+                and _NAIVE_OFF()):
             from ._lib import NvfStemHead
             net = self.net
             g2, ec, ig = net.latent_gen.gdn_2, net.entropy_coder, net.reconstructor.activation
@@ -383,11 +355,10 @@ class TrainEngine:
             sj.mode, sj.ch, sj.c0, sj.c1 = (0 if stem_mode == "train" else 1), ch, c0, c1
             check(lib().nvf_step_head_stem(*args, ctypes.byref(sj), torch.cuda.current_stream().cuda_stream),
                   "nvf_step_head_stem")
-            self._stem_pre = (idx_dev.data_ptr(), stem_mode, o)
         else:
             check(lib().nvf_step_head(*args, torch.cuda.current_stream().cuda_stream), "nvf_step_head")
         self._rate_ready = bool(with_rate)
-        return dsts
+        return dsts if stem_mode is None else dsts + [o]
 
     def prepare_weights(self, q):
         sd = self._step_dev
@@ -405,10 +376,9 @@ class TrainEngine:
             # eight waves with one column tile each (variant 5: two waves per SIMD; up1 19.3 -> 15.6 us, up2 34.0 -> 30.7 at
             # batch 16 -- and at batch 917 (the full-batch latent step; r05 sweep): up2 1115 -> 916 us, up1 389 -> 310;
             # every variant runs the same per-output fmaf chain: bit-identical)
-            var = _VAR["UP1F" if L.cin == 16 else "UP2F"] or 5
-            if train and L.wp_tr is not None and var == 5:
+            if train and L.wp_tr is not None:
                 return ops.convT3d_k5s2_mfma(x, L.wp_tr, L.b_eff, act, variant=15)
-            return ops.convT3d_k5s2_mfma(x, L.wp_t, L.b_eff, act, variant=var)
+            return ops.convT3d_k5s2_mfma(x, L.wp_t, L.b_eff, act, variant=5)
         return ops.convT3d_k5s2_fwd(x, L.w_fwd, L.b_eff, L.cout, L.pad, act)
 
     def _conv(self, L, x, act, train=False):
@@ -429,18 +399,15 @@ class TrainEngine:
             # (variant 2) at 256, 402 vs 443 at 917; at batch 16 the default tile: 12.7 vs 17.6).  Every variant runs
             # the same per-output fmaf chain, so the bits -- and encode-at-any-batch == decode-at-batch-1 -- do not change
             var = 5 if (x.shape[-1] == 19 and x.shape[0] >= 64) else None
-            if x.shape[-1] == 35 and _CONV2_FWD_VAR:
-                var = _CONV2_FWD_VAR
-            if x.shape[-1] == 19 and _VAR["C1F"] and x.shape[0] <= 64:
-                var = _VAR["C1F"]
             return ops.conv3d_k4_mfma(x, L.wp_f, L.b_eff, 0, 0, act, variant=var)
         osz = tuple(s + 2 * L.pad - L.k + 1 for s in x.shape[2:])
         return ops.conv3d_gather(x, L.w_fwd, L.b_eff, L.cout, L.k, 1, L.pad, osz, act)
 
-    def forward(self, e, mode, block_ids, defer_heads=False):
+    def forward(self, e, mode, block_ids, defer_heads=False, stem=None):
         """e [B,ch,2,2,2] latents-before-latent_gen.  Returns the dict of saved activations.  ``defer_heads``: the caller
-        runs backward() next -- at mini-batch sizes the heads' forward then rides in the launch of their loss and
-        backward-data (a["p0"..] stay None until then)."""
+        runs backward() with weight gradients next -- at mini-batch sizes the heads' forward then rides in the launch of
+        their loss and backward-data (a["p0"..] stay None until then).  ``stem``: the stem activations of this
+        mini-batch that batch_and_prepare(..., stem_mode=mode) returned (None: forward() runs the stem itself)."""
         net, Ls = self.net, self.layers
         a = {"e": e}
         g2 = net.latent_gen.gdn_2
@@ -448,9 +415,8 @@ class TrainEngine:
         sd = self._step_dev
         ig = net.reconstructor.activation
         stem_done = False
-        pre, self._stem_pre = getattr(self, "_stem_pre", None), None
-        if pre is not None and pre[0] == block_ids.data_ptr() and pre[1] == mode:
-            a.update(pre[2])                  # the step head's launch ran the latent generator, quantiser and stem
+        if stem is not None:
+            a.update(stem)                    # the step head's launch ran the latent generator, quantiser and stem
             stem_done = True
         elif e.shape[1] <= 8 and _NAIVE_OFF() and self.fused_stem and self.fused_latent_stem:   # latent generator,
             # quantiser and stem in one launch
@@ -469,7 +435,6 @@ class TrainEngine:
             a["x0"], a["lbits"], _, _, _ = ops.latent_rate(a["lat"], ec.sigma.reshape(-1), ec.mu.reshape(-1), mode,
                                                            block_ids=block_ids, seed=self.seed,
                                                            step=0 if sd is not None else self.noise_step, step_dev=sd)
-        self.overlap = self.allow_overlap and e.shape[0] <= 64   # large batches fill the chip by themselves
         if stem_done:
             pass
         elif self.fused_stem:
@@ -480,19 +445,14 @@ class TrainEngine:
             a["h0"] = ops.gdn_fwd(a["a0"], ig.beta, ig.gamma, True)
             a["y1"] = self._convT(Ls["conv0"], a["h0"], R)
         if not self.heads3:
-            self._fork()
-            with self._on_side():                   # the two coarse heads run beside the trunk
-                a["p0"] = self._conv(Ls["conv0_cls"], a["y1"], S)
+            a["p0"] = self._conv(Ls["conv0_cls"], a["y1"], S)
         a["y2"] = self._convT(Ls["up1"], a["y1"], R, train=(mode == "train"))
         a["y3"] = self._conv(Ls["conv1"], a["y2"], R, train=(mode == "train"))
         if not self.heads3:
-            self._fork()
-            with self._on_side():
-                a["p1"] = self._conv(Ls["conv1_cls"], a["y3"], S)
+            a["p1"] = self._conv(Ls["conv1_cls"], a["y3"], S)
         a["y4"] = self._convT(Ls["up2"], a["y3"], R, train=(mode == "train"))
         a["y5"] = self._conv(Ls["conv2"], a["y4"], R, train=(mode == "train"))
-        if (self.heads3 and defer_heads and _HEADS_FWD_IN_LOSS and e.shape[0] <= 32 and _NAIVE_OFF()
-                and not self.allow_overlap):
+        if self.heads3 and defer_heads and e.shape[0] <= 32 and _NAIVE_OFF():
             a["p0"] = a["p1"] = a["p2"] = None      # nvf_heads3_fwd_loss_bwd_data (backward)
         elif self.heads3:                           # all three heads in one launch, after the trunk
             hl = [Ls["conv0_cls"], Ls["conv1_cls"], Ls["conv2_cls"]]
@@ -500,22 +460,12 @@ class TrainEngine:
                                                        [L.b_eff for L in hl])
         else:
             a["p2"] = self._conv(Ls["conv2_cls"], a["y5"], S)
-        if self.overlap:
-            torch.cuda.current_stream().wait_stream(self.side)
         return a
 
     # ------------------------------------------------------------------ backward
-    def _fork(self):
-        """Side stream waits for everything issued so far on the current (main) stream."""
-        if self.overlap:
-            self.side.wait_stream(torch.cuda.current_stream())
-
-    def _on_side(self):
-        return torch.cuda.stream(self.side) if self.overlap else _NullCtx()
-
     def _wgrad_conv(self, L, g_out, x_in):
-        if (self.wide and self.winograd and _WINO16 and L.k == 4 and L.cin == 16 and L.cout == 16 and L.pad == 0
-                and g_out.shape[-1] in _WINO16_WGRAD):
+        if (self.wide and self.winograd and L.k == 4 and L.cin == 16 and L.cout == 16 and L.pad == 0
+                and g_out.shape[-1] in (32, 16)):
             # the Winograd (y, x) form (wgrad16_wino.hip): slabs for the common reduction (conv2 172 -> 100 us at batch 16)
             base = self._wg.reserve(256 * 16384 * 4)
             n = ops.wgrad16_k4_wino_partial(g_out, x_in, base, zsplit=0 if g_out.shape[-1] == 32 else 8)
@@ -534,13 +484,8 @@ class TrainEngine:
         gradient this pass writes): the matrix-core kernel leaves its channel sums as slabs for the reduction launch;
         returns (dx, True) then, (dx, False) when the caller has to sum dx itself."""
         if self.wide and L.wp_w is not None and mask is not None and addend is None and g_out.shape[-1] in (32, 16):
-            if bias_out is not None and g_out.shape[0] <= 64 and _WINO16_BIAS:
-                # the channel sums of dx (the bias gradient of the layer below) leave with the kernel's stores instead of a
-                # second pass over the 44 MB it wrote (conv2 at batch 16)
-                base = self._wg.reserve(8192 * 16 * 4)
-                dx, nparts = ops.conv3d_k4_wino16_bwd(g_out, L.wp_w, mask, bias_part=base)
-                self._wg.add_job(base, bias_out, nparts, 16)
-                return dx, True
+            # (the channel sums of dx -- the bias gradient of the layer below -- from this kernel's epilogue, bias_part=:
+            # measured neutral, the reduction launch 48.9 -> 44.0 us against + 2.7 / + 2.1 us in the two epilogues)
             dx = ops.conv3d_k4_wino16_bwd(g_out, L.wp_w, mask)
             return dx if bias_out is None else (dx, False)
         if L.wp_gb is not None:
@@ -558,16 +503,12 @@ class TrainEngine:
                 return ops.conv3d_k4_wino_bwd(g_out, L.wp_w, mask, ppc=_wino_bwd_ppc(g_out)), False
             return ops.conv3d_k4_wino_bwd(g_out, L.wp_w, mask, ppc=_wino_bwd_ppc(g_out))
         if L.wp_b is not None and g_out.shape[0] <= L.bwd_max_batch:
-            var = _CONV2_BWD_VAR if (g_out.shape[-1] == 32 and _CONV2_BWD_VAR) else None
-            if g_out.shape[-1] == 16 and _VAR["C1B"]:
-                var = _VAR["C1B"]
             if bias_out is not None and mask is not None and addend is None:
                 base = self._wg.reserve(4096 * 8 * 4)
-                dx, nparts = ops.conv3d_k4_mfma(g_out, L.wp_b, None, 3, L.bwd_pair, NONE, mask=mask, bias_part=base,
-                                                variant=var)
+                dx, nparts = ops.conv3d_k4_mfma(g_out, L.wp_b, None, 3, L.bwd_pair, NONE, mask=mask, bias_part=base)
                 self._wg.add_job(base, bias_out, nparts, 8)
                 return dx, True
-            dx = ops.conv3d_k4_mfma(g_out, L.wp_b, None, 3, L.bwd_pair, NONE, addend=addend, mask=mask, variant=var)
+            dx = ops.conv3d_k4_mfma(g_out, L.wp_b, None, 3, L.bwd_pair, NONE, addend=addend, mask=mask)
             return dx if bias_out is None else (dx, False)
         if bias_out is not None:
             return ops.conv3d_gather(g_out, L.w_bwd, None, L.cin, L.k, 1, L.k - 1 - L.pad, tuple(x_in.shape[2:]),
@@ -585,9 +526,10 @@ class TrainEngine:
             # above: 4 rows x 4 planes on eight waves (variant 5: 1027 vs 1149 us at batch 917)
             # up1 in training steps of the default engine: the two channel groups of g on different waves, 256 workgroups of
             # 2 rows x 2 planes (variant 7: another summation order, so not in the strict-trajectory engine)
-            var = 2 if (L.cin == 16 and g_out.shape[0] > 64) else (
-                _VAR["UP1B" if L.cin == 16 else "UP2B"] or ((6 if g_out.shape[0] <= 64 else 5) if L.cin == 8 else
-                                                            (7 if (self.winograd and _UP1B_KSPLIT) else None)))
+            if L.cin == 16:
+                var = 2 if g_out.shape[0] > 64 else (7 if self.winograd else None)
+            else:
+                var = 6 if g_out.shape[0] <= 64 else 5
             return ops.conv3d_s2k5_mfma(g_out, L.wp_s, L.cin, addend=addend, mask=mask, variant=var)
         return ops.conv3d_gather(g_out, L.w_bwd, None, L.cin, 5, 2, L.pad, tuple(x_in.shape[2:]), addend=addend,
                                  mask=mask)
@@ -600,13 +542,13 @@ class TrainEngine:
             raise
 
     def _backward(self, a, gt, dist, gt16, gt8, n_pts, mode, block_ids, want_w, want_emb, fuse=None):
-        """Loss (NVFPCC.py:161-196) and its gradients.  Weight grads land in self.flat_g.
-
-        Main stream: the backward-data chain.  Side stream: head backward-data (t0, t1), every weight gradient,
-        the bias sums and the weight-rate term; each side job waits for the chain tensor it consumes."""
+        """Loss (NVFPCC.py:161-196) and its gradients.  Weight grads land in self.flat_g."""
         net, Ls = self.net, self.layers
-        main = torch.cuda.current_stream()
-        self.overlap = self.allow_overlap and a["e"].shape[0] <= 64
+        heads_deferred = a.get("p2") is None
+        fused_loss = self.heads3 and a["e"].shape[0] <= 32 and _NAIVE_OFF()
+        if heads_deferred and not (want_w and fused_loss):
+            raise ValueError("forward(defer_heads=True) must be followed by a backward pass with weight gradients "
+                             "(want_w=True): the heads' forward runs in that pass's loss launch")
         self._bias_jobs = []
         self._bias_cover = []     # bias gradients some launch's own final pass writes (no channel-sum job needed)
         if self._wg is None:
@@ -615,12 +557,10 @@ class TrainEngine:
         loss = torch.empty(4, device=self.dev)   # [main, head0, head1, unused]
         nbits = torch.empty(7, device=self.dev)
         # the one-block final passes of the focal terms, the bias sums and the weight rate feed nothing inside the
-        # step: queue them and run all three in one launch at the end (single-stream schedule only)
-        defer = want_w and not self.overlap
-        ctx = self.ctx if defer else None
-        if defer:
+        # step: queue them and run all three in one launch at the end
+        ctx = self.ctx if want_w else None
+        if want_w:
             self.ctx.begin()
-        fused_loss = self.heads3 and a["e"].shape[0] <= 32 and _NAIVE_OFF()
         if not fused_loss:
             dl2, dl0, dl1 = ops.focal_loss_multi([(a["p2"], gt, dist, 0.9, 1.0), (a["p0"], gt8, None, 0.85, 0.0),
                                                   (a["p1"], gt16, None, 0.85, 0.0)], loss, ctx=ctx)
@@ -631,33 +571,28 @@ class TrainEngine:
             if self.epoch_acc is not None and want_w:
                 ops.metrics3([a["p2"], a["p0"], a["p1"]], [gt, gt8, gt16], [dist, None, None], 0.5, 0.6,
                              out=self.step_counts, ctx=ctx)
-        heads_deferred = a.get("p2") is None
         if not heads_deferred:
             step_metrics()
-        ev_t1 = ev_t0 = None
+        heads_job = None
         if self.heads3:
             hl = [Ls["conv0_cls"], Ls["conv1_cls"], Ls["conv2_cls"]]
+            head_bias_done = want_w and _HEAD_BIAS_IN_LOSS    # the heads' bias gradients: partials of the loss launch
             if heads_deferred:
                 # the heads' forward, the three focal terms, their logit gradients and the heads' backward-data: ONE launch
                 # (forward() left p0 / p1 / p2 to this call)
-                assert fused_loss and defer
                 (a["p0"], a["p1"], a["p2"]), (dl0, dl1, dl2), (t0, t1, g5) = ops.heads3_fwd_loss_bwd_data(
                     [a["y1"], a["y3"], a["y5"]], [L.w_fwd for L in hl], [L.b_eff for L in hl], [gt8, gt16, gt],
                     [None, None, dist], [0.85, 0.85, 0.9], [0.0, 0.0, 1.0], [1, 2, 0], loss, [L.w_bwd for L in hl],
-                    [None, None, a["y5"]], self.ctx,
-                    bias_outs=[L.gb for L in hl] if (want_w and _HEAD_BIAS_IN_LOSS) else None)
-                head_bias_done = want_w and _HEAD_BIAS_IN_LOSS
+                    [None, None, a["y5"]], self.ctx, bias_outs=[L.gb for L in hl] if head_bias_done else None)
                 step_metrics()
             elif fused_loss:    # the three focal terms, their logit gradients and the heads' backward-data: one launch
                 (dl0, dl1, dl2), (t0, t1, g5) = ops.heads3_loss_bwd_data(
                     [a["p0"], a["p1"], a["p2"]], [gt8, gt16, gt], [None, None, dist], [0.85, 0.85, 0.9],
                     [0.0, 0.0, 1.0], [1, 2, 0], loss, [L.w_bwd for L in hl], [L.cin for L in hl], [None, None, a["y5"]],
-                    ctx=ctx, bias_outs=[L.gb for L in hl] if (want_w and _HEAD_BIAS_IN_LOSS) else None)
-                head_bias_done = want_w and _HEAD_BIAS_IN_LOSS    # the heads' bias gradients: partials of that launch
+                    ctx=ctx, bias_outs=[L.gb for L in hl] if head_bias_done else None)
             else:
                 t0, t1, g5 = ops.heads3_bwd_data([dl0, dl1, dl2], [L.w_bwd for L in hl], [L.cin for L in hl],
                                                  [None, None, a["y5"]])
-            heads_job = None
             if want_w:
                 heads_job = ([dl0, dl1, dl2], [a["y1"], a["y3"], a["y5"]], [L.gk for L in hl])
                 if not (self.narrow and _NAIVE_OFF() and _HEADS_IN_TRUNK5):   # else: workgroups of the five-gradient launch
@@ -668,102 +603,73 @@ class TrainEngine:
                 else:
                     self._bias_jobs += [(dl2, hl[2].gb), (dl1, hl[1].gb), (dl0, hl[0].gb)]
         else:
-            self._fork()
-            with self._on_side():
-                t1 = self._dx_conv(Ls["conv1_cls"], dl1, a["y3"])
-                ev_t1 = torch.cuda.Event() if self.overlap else None
-                if ev_t1 is not None:
-                    ev_t1.record()
-                t0 = self._dx_conv(Ls["conv0_cls"], dl0, a["y1"])
-                ev_t0 = torch.cuda.Event() if self.overlap else None
-                if ev_t0 is not None:
-                    ev_t0.record()
-                if want_w:
-                    self._wgrad_conv(Ls["conv2_cls"], dl2, a["y5"])
-                    self._wgrad_conv(Ls["conv1_cls"], dl1, a["y3"])
-                    self._wgrad_conv(Ls["conv0_cls"], dl0, a["y1"])
-
-        def side_wgrad(fn, L, g, x, **kw):
-            if not want_w:
-                return
-            self._fork()
-            with self._on_side():
-                fn(L, g, x, **kw)
-
-        # wide decoder: the Winograd backward-data kernels leave the channel sums of what they write (the bias gradients
-        # of up2 / up1) as slabs for the reduction launch
-        wbias = want_w and self.wide and _WINO16_BIAS and Ls["conv2"].wp_w is not None
-
-        if not self.heads3:
+            t1 = self._dx_conv(Ls["conv1_cls"], dl1, a["y3"])
+            t0 = self._dx_conv(Ls["conv0_cls"], dl0, a["y1"])
+            if want_w:
+                self._wgrad_conv(Ls["conv2_cls"], dl2, a["y5"])
+                self._wgrad_conv(Ls["conv1_cls"], dl1, a["y3"])
+                self._wgrad_conv(Ls["conv0_cls"], dl0, a["y1"])
             g5 = self._dx_conv(Ls["conv2_cls"], dl2, a["y5"], mask=a["y5"])
-        wg3 = want_w and self.narrow and _NAIVE_OFF()      # conv2 / up2 / conv1 weight gradients in one launch
-        if not wg3:
-            side_wgrad(self._wgrad_conv, Ls["conv2"], g5, a["y4"])
+
+        # the backward-data chain; each layer's weight gradient is issued as soon as its output gradient exists, except on
+        # the narrow decoder, whose five trunk weight gradients are one launch (add_trunk5, below)
+        wg3 = want_w and self.narrow and _NAIVE_OFF()
         if wg3:     # up2's bias gradient = the channel sums of g4: left by the kernel that writes g4
             g4, up2_bias_done = self._dx_conv(Ls["conv2"], g5, a["y4"], mask=a["y4"], bias_out=Ls["up2"].gb)
-        elif wbias:
-            g4, done = self._dx_conv(Ls["conv2"], g5, a["y4"], mask=a["y4"], bias_out=Ls["up2"].gb)
-            side_wgrad(self._wgrad_convT, Ls["up2"], g4, a["y3"], bias=not done)
-        else:
-            g4 = self._dx_conv(Ls["conv2"], g5, a["y4"], mask=a["y4"])
-            side_wgrad(self._wgrad_convT, Ls["up2"], g4, a["y3"])
-        if ev_t1 is not None:
-            main.wait_event(ev_t1)
-        g3 = self._dx_convT(Ls["up2"], g4, a["y3"], mask=a["y3"], addend=t1)
-        if wg3:     # launched after the latent tail has been queued (below): the tail rides in that launch; the bias
-            # gradients of conv2 and conv1 (channel sums of g5, g3) come out of it too
             if not up2_bias_done:
                 self._bias_jobs += [(g4, Ls["up2"].gb)]
         else:
-            side_wgrad(self._wgrad_conv, Ls["conv1"], g3, a["y2"])
+            if want_w:
+                self._wgrad_conv(Ls["conv2"], g5, a["y4"])
+            g4 = self._dx_conv(Ls["conv2"], g5, a["y4"], mask=a["y4"])
+            if want_w:
+                self._wgrad_convT(Ls["up2"], g4, a["y3"])
+        g3 = self._dx_convT(Ls["up2"], g4, a["y3"], mask=a["y3"], addend=t1)
         if wg3:
             g2, up1_bias_done = self._dx_conv(Ls["conv1"], g3, a["y2"], mask=a["y2"], bias_out=Ls["up1"].gb)
-        elif wbias:
-            g2, done = self._dx_conv(Ls["conv1"], g3, a["y2"], mask=a["y2"], bias_out=Ls["up1"].gb)
-            side_wgrad(self._wgrad_convT, Ls["up1"], g2, a["y1"], bias=not done)
         else:
+            if want_w:
+                self._wgrad_conv(Ls["conv1"], g3, a["y2"])
             g2 = self._dx_conv(Ls["conv1"], g3, a["y2"], mask=a["y2"])
-            side_wgrad(self._wgrad_convT, Ls["up1"], g2, a["y1"])
-        if ev_t0 is not None:
-            main.wait_event(ev_t0)
+            if want_w:
+                self._wgrad_convT(Ls["up1"], g2, a["y1"])
         g1 = self._dx_convT(Ls["up1"], g2, a["y1"], mask=a["y1"], addend=t0)
-        stem_wg0 = want_w and self.fused_stem and defer and not wg3   # conv0's weight gradient rides in the stem's backward
+        stem_wg0 = want_w and self.fused_stem and not wg3   # conv0's weight gradient rides in the stem's backward
         if wg3:                                      # up1 and conv0 weight gradients: with the other three, below
             self._bias_jobs += ([] if up1_bias_done else [(g2, Ls["up1"].gb)]) + [(g1, Ls["conv0"].gb)]
         elif stem_wg0:
             self._bias_jobs.append((g1, Ls["conv0"].gb))
-        else:
-            side_wgrad(self._wgrad_convT, Ls["conv0"], g1, a["h0"])
+        elif want_w:
+            self._wgrad_convT(Ls["conv0"], g1, a["h0"])
         ig = net.reconstructor.activation
         gview = (lambda n: self._g(n)) if want_w else (lambda n: None)
         gamma_view = None if not want_w else self._g("reconstructor.activation.gamma").view(ig.gamma.shape)
-        self._stem_gdn_in_finals = bool(self.fused_stem and defer and want_w)
-        tail = _TAIL and defer and not want_emb and a["e"].shape[1] <= 8 and _NAIVE_OFF()
-        stem_coop = (_STEM_IN_TRUNK5 and tail and wg3 and self.fused_stem and want_w and a["e"].shape[0] <= 32
+        self._stem_gdn_in_finals = bool(self.fused_stem and want_w)
+        tail = want_w and not want_emb and a["e"].shape[1] <= 8 and _NAIVE_OFF()
+        stem_coop = (_STEM_IN_TRUNK5 and tail and wg3 and self.fused_stem and a["e"].shape[0] <= 32
                      and heads_job is not None)
+        stem_jobs = None
         if stem_coop:
             # no launch here: queued in the context, it runs inside add_trunk5's launch below (with the latent tail that
-            # consumes dx0); up0's bias gradient comes from per-block channel sums the stage leaves, not from da0
-            da0, dx0 = ops.stem_bwd_queue(g1, a["x0"], a["a0"], Ls["conv0"].w_bwd, Ls["up0"].w_bwd, ig.beta, ig.gamma,
-                                          gview("reconstructor.activation.beta"), gamma_view, Ls["up0"].gk,
-                                          Ls["up0"].gb, self._wg, self.ctx)
-        elif self.fused_stem and defer:        # its final launch is shared with the slab reduction / the final passes
+            # consumes dx0), which also takes its reduction jobs; up0's bias gradient comes from per-block channel sums
+            # the stage leaves, not from da0
+            da0, dx0, stem_jobs = ops.stem_bwd_queue(g1, a["x0"], a["a0"], Ls["conv0"].w_bwd, Ls["up0"].w_bwd, ig.beta,
+                                                     ig.gamma, gview("reconstructor.activation.beta"), gamma_view,
+                                                     Ls["up0"].gk, Ls["up0"].gb, self.ctx)
+        elif self.fused_stem and want_w:        # its final launch is shared with the slab reduction / the final passes
             da0, dx0 = ops.stem_bwd_partial(g1, a["x0"], a["a0"], Ls["conv0"].w_bwd, Ls["up0"].w_bwd, ig.beta,
                                             ig.gamma, gview("reconstructor.activation.beta"), gamma_view,
                                             Ls["up0"].gk, self._wg, ctx=ctx, h0=a["h0"] if stem_wg0 else None,
                                             dw_conv0=Ls["conv0"].gk if stem_wg0 else None)
             self._bias_jobs.append((da0, Ls["up0"].gb))
         elif self.fused_stem:
-            da0, dx0 = ops.stem_bwd(g1, a["x0"], a["a0"], Ls["conv0"].w_bwd, Ls["up0"].w_bwd, ig.beta, ig.gamma,
-                                    gview("reconstructor.activation.beta"), gamma_view,
-                                    Ls["up0"].gk if want_w else None)
-            if want_w:
-                self._bias_jobs.append((da0, Ls["up0"].gb))
+            da0, dx0 = ops.stem_bwd(g1, a["x0"], a["a0"], Ls["conv0"].w_bwd, Ls["up0"].w_bwd, ig.beta, ig.gamma)
         else:
             dh0 = self._dx_convT(Ls["conv0"], g1, a["h0"])
             da0, _, _ = ops.gdn_bwd(a["a0"], ig.beta, ig.gamma, dh0, True, gview("reconstructor.activation.beta"),
                                     gamma_view)
-            side_wgrad(self._wgrad_convT, Ls["up0"], da0, a["x0"])
+            if want_w:
+                self._wgrad_convT(Ls["up0"], da0, a["x0"])
             dx0 = self._dx_convT(Ls["up0"], da0, a["x0"])
         # latent rate (+ the decoder's gradient through the straight-through round)
         ec = net.entropy_coder
@@ -790,7 +696,8 @@ class TrainEngine:
                                                dmu_out=gview("entropy_coder.mu"))
             dh, _, _ = ops.gdn_bwd(a["h"], g2m.beta, g2m.gamma, dlat, False, gview("latent_gen.gdn_2.beta"),
                                    None if not want_w else self._g("latent_gen.gdn_2.gamma").view(g2m.gamma.shape))
-            side_wgrad(self._wgrad_conv, Ls["latent"], dh, a["e"])
+            if want_w:
+                self._wgrad_conv(Ls["latent"], dh, a["e"])
             de = self._dx_conv(Ls["latent"], dh, a["e"]) if want_emb else None
         if wg3:
             # conv2 / up2 / conv1 weight gradients, the longest launch of the step, go last of the big kernels: the
@@ -799,68 +706,63 @@ class TrainEngine:
             # gradients (small VALU kernels) fill the slots that the short matrix-core workgroups leave
             self._wg.add_trunk5([g5, a["y3"], g3, a["y1"], a["h0"]], [a["y4"], g4, a["y2"], g2, g1],
                                 [Ls["conv2"].gk, Ls["up2"].gk, Ls["conv1"].gk, Ls["up1"].gk, Ls["conv0"].gk],
-                                bias_outs=(Ls["conv2"].gb, Ls["conv1"].gb), heads=heads_job if self.heads3 else None,
+                                bias_outs=(Ls["conv2"].gb, Ls["conv1"].gb), heads=heads_job,
                                 sums=(([t for t, _ in self._bias_jobs], [o for _, o in self._bias_jobs])
-                                      if (self.heads3 and heads_job is not None and defer and self._rate_ready
-                                          and want_w and _SUMS_IN_TRUNK5) else None),
+                                      if (heads_job is not None and self._rate_ready and _SUMS_IN_TRUNK5) else None),
                                 coef=((fuse["coef_dev"], self._coef_live)
-                                      if (fuse is not None and fuse.get("coef_dev") is not None) else None))
+                                      if (fuse is not None and fuse.get("coef_dev") is not None) else None),
+                                stem_jobs=stem_jobs)
         # weight rate: bits of the 7 quantised kernels and, for the decoder update, their gradients (added to the
-        # weight gradients, so it follows the wgrads on the side stream); every bias gradient in one reduction
+        # weight gradients); every bias gradient in one reduction
         lm = net.reconstructor.likelihood_model
         g_net = self.lmbda * self.w2 / self.n_points_total
         gs, gm = self._g("reconstructor.likelihood_model.sigma"), self._g("reconstructor.likelihood_model.mu")
         kernels = [Ls[n].mod.kernel for n in TRUNK]
-        rate_head, self._rate_ready = self._rate_ready and want_w and defer, False
+        rate_head, self._rate_ready = self._rate_ready and want_w, False
         fused = None
-        self._fork()
-        with self._on_side():
-            if want_w:     # slab reduction of every weight gradient + all bias sums
-                addends = None
-                if rate_head:
-                    # the weight-rate gradient was computed by the step head: the reduction adds it while it writes the
-                    # gradients (every trunk kernel must come out of that launch; otherwise the stand-alone pass)
-                    job, addends = self._rate_job()[:2]
-                    live = {j[1] for j in self._wg.jobs if j[2] > 0}
-                    if not all(Ls[n].gk.data_ptr() in live for n in TRUNK) or len(self._wg.jobs) > 16:
-                        rate_head, addends = False, None
-                if fuse is not None and rate_head:
-                    fused = self._fused_tail(fuse, loss, a["lbits"], nbits, gs, gm)
-                sums_done = wg3 and getattr(self._wg, "sums_done", False)    # the partial bias sums rode in add_trunk5
-                one_launch = fused is not None and sums_done and rate_head
-                if one_launch:      # nothing the final passes read is written by the slab reduction: ONE launch for both
-                    ops.weight_rate_final(job, nbits, gs, gm, ctx=ctx)
-                    adam = fused[1]
-                    if fuse.get("coef_dev") is not None:     # the copy add_trunk5 staged: not the step buffer's words
-                        adam.coef_dev = self._coef_live.data_ptr()
-                    self._wg.finish_and_flush_tail(addends, adam, fused[0], fused[2])
-                elif sums_done and rate_head and fused is None:
-                    # data parallelism (the all-reduce and the step tail follow): the same pairing without the optimiser
-                    one_launch = True
-                    ops.weight_rate_final(job, nbits, gs, gm, ctx=ctx)
-                    self._wg.finish_and_flush(addends)
-                else:
-                    if sums_done:
-                        self._wg.finish_with_sums([], [], addends=addends, adam=None if fused is None else fused[1])
-                    else:
-                        self._wg.finish_with_sums([t for t, _ in self._bias_jobs], [o for _, o in self._bias_jobs],
-                                                  addends=addends, adam=None if fused is None else fused[1])
-                    if rate_head:
-                        ops.weight_rate_final(job, nbits, gs, gm, ctx=ctx)
-                    else:
-                        ops.weight_rate_batch(kernels, [Ls[n].gk for n in TRUNK], lm.sigma, lm.mu, nbits, gs, gm,
-                                              g_host=g_net * self.rate_grad_scale, ctx=ctx)
+        if want_w:     # slab reduction of every weight gradient + all bias sums
+            addends = None
+            if rate_head:
+                # the weight-rate gradient was computed by the step head: the reduction adds it while it writes the
+                # gradients (every trunk kernel must come out of that launch; otherwise the stand-alone pass)
+                job, addends = self._rate_job()[:2]
+                live = {j[1] for j in self._wg.jobs if j[2] > 0}
+                if not all(Ls[n].gk.data_ptr() in live for n in TRUNK) or len(self._wg.jobs) > 16:
+                    rate_head, addends = False, None
+            if fuse is not None and rate_head:
+                fused = self._fused_tail(fuse, loss, a["lbits"], nbits, gs, gm)
+            sums_done = wg3 and getattr(self._wg, "sums_done", False)    # the partial bias sums rode in add_trunk5
+            one_launch = fused is not None and sums_done and rate_head
+            if one_launch:      # nothing the final passes read is written by the slab reduction: ONE launch for both
+                ops.weight_rate_final(job, nbits, gs, gm, ctx=ctx)
+                adam = fused[1]
+                if fuse.get("coef_dev") is not None:     # the copy add_trunk5 staged: not the step buffer's words
+                    adam.coef_dev = self._coef_live.data_ptr()
+                self._wg.finish_and_flush_tail(addends, adam, fused[0], fused[2])
+            elif sums_done and rate_head and fused is None:
+                # data parallelism (the all-reduce and the step tail follow): the same pairing without the optimiser
+                one_launch = True
+                ops.weight_rate_final(job, nbits, gs, gm, ctx=ctx)
+                self._wg.finish_and_flush(addends)
             else:
-                one_launch = False
-                ops.weight_rate_batch(kernels, None, lm.sigma, lm.mu, nbits)
-            if defer and not one_launch:
+                if sums_done:
+                    self._wg.finish_with_sums([], [], addends=addends, adam=None if fused is None else fused[1])
+                else:
+                    self._wg.finish_with_sums([t for t, _ in self._bias_jobs], [o for _, o in self._bias_jobs],
+                                              addends=addends, adam=None if fused is None else fused[1])
+                if rate_head:
+                    ops.weight_rate_final(job, nbits, gs, gm, ctx=ctx)
+                else:
+                    ops.weight_rate_batch(kernels, [Ls[n].gk for n in TRUNK], lm.sigma, lm.mu, nbits, gs, gm,
+                                          g_host=g_net * self.rate_grad_scale, ctx=ctx)
+            if not one_launch:
                 if fused is not None:
                     self.ctx.flush_tail(fused[0], fused[2])
                 else:
                     self.ctx.flush()
+        else:
+            ops.weight_rate_batch(kernels, None, lm.sigma, lm.mu, nbits)
         self.tail_done = fused is not None
-        if self.overlap:
-            main.wait_stream(self.side)      # join: nothing below (Adam, frees) may pass the side work
         self.last = {"loss_terms": loss, "latent_bits": a["lbits"], "net_bits": nbits, "n_pts": n_pts}
         return de
 
@@ -997,11 +899,10 @@ class TrainEngine:
                 idx_dev = torch.from_numpy(idx_host).to(self.dev)
             if n_pts is None:
                 n_pts = float(self.counts[idx_host].sum())
-            gt, dist, gt16, gt8, e = self.batch_and_prepare(idx_dev, q, with_rate=not self.allow_overlap,
-                                                            stem_mode="train")
-            a = self.forward(e, "train", idx_dev, defer_heads=True)
+            gt, dist, gt16, gt8, e, stem = self.batch_and_prepare(idx_dev, q, with_rate=True, stem_mode="train")
+            a = self.forward(e, "train", idx_dev, defer_heads=True, stem=stem)
             tail = None
-            if update and self.grad_hook is None and not self.allow_overlap:
+            if update and self.grad_hook is None:
                 # single GPU: the optimiser rides in the slab reduction and the finals launch (no all-reduce in between)
                 tail = dict(coef_host=ops.adam_coefficients(self.lr, self.opt_step + 1), inv_npts_host=1.0 / n_pts)
             self.backward(a, gt, dist, gt16, gt8, n_pts, "train", idx_dev, want_w=True, want_emb=False, fuse=tail)
@@ -1091,8 +992,7 @@ class GraphedTrainStep:
     CAP = 4096       # rows of the device-resident schedule (longer schedules are loaded in pieces)
     # steps per replay of the unrolled graphs, largest first (a run of n loaded steps is replayed greedily: 57 = 3 x 16 + 8
     # + 1 is five graph launches; 20 = 16 + 4 two)
-    UNROLL = tuple(sorted({max(int(v), 1) for v in os.environ.get("NVF_GRAPH_UNROLL", "16,8,4,2").split(",") if v.strip()},
-                          reverse=True))
+    UNROLL = (16, 8, 4, 2)
 
     def __init__(self, eng, batch, q, ring=2, collective=None, unroll=None):
         self.eng, self.batch, self.q = eng, batch, q
@@ -1172,11 +1072,10 @@ class GraphedTrainStep:
 
     def _body(self, tail):
         eng = self.eng
-        gt, dist, gt16, gt8, e = eng.batch_and_prepare(self.idx, self.q, with_rate=not eng.allow_overlap,
-                                                       stem_mode="train")
-        a = eng.forward(e, "train", self.idx, defer_heads=True)
+        gt, dist, gt16, gt8, e, stem = eng.batch_and_prepare(self.idx, self.q, with_rate=True, stem_mode="train")
+        a = eng.forward(e, "train", self.idx, defer_heads=True, stem=stem)
         spec = None
-        if tail and eng.grad_hook is None and not eng.allow_overlap:      # single GPU: no launch of its own for the tail
+        if tail and eng.grad_hook is None:      # single GPU: no launch of its own for the tail
             spec = dict(coef_dev=self.coef, inv_npts_dev=self.inv_npts, sched=(self.buf, self.rows, self.cursor, self.nw))
         eng.backward(a, gt, dist, gt16, gt8, 1.0, "train", self.idx, want_w=True, want_emb=False, fuse=spec)
         self.out = a
@@ -1369,7 +1268,7 @@ class EpochDriver:
         while s < nsteps:                                # the short last batch, empty shares, or no graph at all
             ids, whole = self.nd.shard_minibatch(order, s, B, self.rank, self.world)
             n_pts = float(eng.counts[whole].sum())
-            if self.use_graph and self.world == 1 and s == nfull and len(ids) > 0 and _GRAPH_LAST:
+            if self.use_graph and self.world == 1 and s == nfull and len(ids) > 0:
                 # one GPU: the short last mini-batch (917 mod 16 = 5 blocks) replays a single-step graph of its own size
                 # instead of ~90 host launches (0.25 ms against 0.6 per epoch); same kernels, same bits
                 key = (len(ids), q)

@@ -4,16 +4,14 @@ PyTorch is plumbing here: it owns device memory and the stream; every value is c
 hand-written gfx950 kernel in libnvf_hip.so.  All tensors must be fp32, contiguous and on a
 HIP device; anything else raises (no CPU fallback).
 """
-import os
-
 import torch
 
 from ._lib import lib, check
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 # kernel variant passed to the conv / wgrad entry points: 0 = tuned LDS-tiled kernels, 1 = the
-# one-thread-per-output kernels (debug cross-check), >= 2 = alternates kept for tuning (tools/kbench.py)
-_NAIVE = int(os.environ.get("NVF_VARIANT", "0"))
+# one-thread-per-output kernels (debug cross-check, bench.py --naive), >= 2 = alternates kept for tuning (tools/kbench.py)
+_NAIVE = 0
 
 
 def set_naive(flag):
@@ -349,10 +347,10 @@ def wgrad_k4_wino(dy, x, zsplit=1, want_bias=False):
     return (dw, db) if want_bias else dw
 
 
-_MFMA_VARIANT = int(os.environ.get("NVF_MFMA_VARIANT", "0"))
+_MFMA_VARIANT = 0
 # slabs (= workgroups) of the big head's weight gradient: 512 (matrix-core kernel inside the five-gradient launch:
 # 447.7 us of step kernels against 449.6 with 256 and 450.4 with 1024); the VALU kernels did best with 256
-_HEADS_SLABS = int(os.environ.get("NVF_HEADS_SLABS", "512"))
+_HEADS_SLABS = 512
 
 
 def set_mfma_variant(v):
@@ -565,11 +563,12 @@ def stem_bwd_partial(g1, x0, a0, conv0_w_bwd, up0_w_bwd, beta_hat, gamma_hat, db
     return da0, dx0
 
 
-def stem_bwd_queue(g1, x0, a0, conv0_w_bwd, up0_w_bwd, beta_hat, gamma_hat, dbeta_out, dgamma_out, dw_up0, db_up0, wg, ctx):
+def stem_bwd_queue(g1, x0, a0, conv0_w_bwd, up0_w_bwd, beta_hat, gamma_hat, dbeta_out, dgamma_out, dw_up0, db_up0, ctx):
     """stem_bwd_partial with NO launch of its own (nvf_stem_bwd_queue): the work is queued in ``ctx`` and runs as the first
-    workgroups of the next WgradBatch.add_trunk5 launch of ``wg`` (which must carry the queued latent tail that consumes
-    dx0).  up0's weight gradient and -- from per-block channel sums the stage leaves -- its bias gradient ``db_up0`` become
-    reduction jobs of ``wg``.  Returns (da0, dx0): they exist after that launch."""
+    workgroups of the next WgradBatch.add_trunk5 launch given that context (which must carry the queued latent tail that
+    consumes dx0).  Returns (da0, dx0, jobs): da0 / dx0 exist after that launch, and ``jobs`` -- the reductions of up0's
+    weight gradient and, from per-block channel sums the stage leaves, of its bias gradient ``db_up0`` -- are that
+    launch's stem_jobs (their slabs are unwritten until it runs)."""
     import ctypes
     _f32(g1, x0, a0, conv0_w_bwd, up0_w_bwd, beta_hat, gamma_hat, dbeta_out, dgamma_out, dw_up0, db_up0)
     B, ch = x0.shape[0], x0.shape[1]
@@ -585,9 +584,7 @@ def stem_bwd_queue(g1, x0, a0, conv0_w_bwd, up0_w_bwd, beta_hat, gamma_hat, dbet
                                    _ptr(beta_hat), _ptr(gamma_hat), _ptr(da0), _ptr(dx0), _ptr(dbeta_out),
                                    _ptr(dgamma_out), ctypes.byref(slabs), ctypes.byref(nsl), ctypes.byref(bias), _ptr(ws),
                                    ws.numel(), _ptr(flags), B, ch, c0, c1, _stream()), "nvf_stem_bwd_queue")
-    wg.jobs.append((slabs.value, dw_up0.data_ptr(), nsl.value, dw_up0.numel()))
-    wg.jobs.append((bias.value, db_up0.data_ptr(), B, c0))
-    return da0, dx0
+    return da0, dx0, [(slabs.value, dw_up0.data_ptr(), nsl.value, dw_up0.numel()), (bias.value, db_up0.data_ptr(), B, c0)]
 
 
 def wgrad(p, q, k, stride, pad, out_mode=0, out=None, accumulate=False):
@@ -685,7 +682,8 @@ def heads3_fwd_loss_bwd_data(xs, w_fwds, biases, gts, dists, alphas, betas, slot
 
 class WgradBatch:
     """Weight gradients of one backward pass with a single reduction launch: ``add`` launches only the partial
-    sums (each gradient keeps its own slab region until ``finish``), ``finish`` adds all slabs in one kernel."""
+    sums (each gradient keeps its own slab region until ``finish``), ``finish`` adds all slabs in one kernel.
+    ``jobs``: (slab base address, output address, slab count, floats per slab) of every reduction pending."""
 
     def __init__(self, device, nbytes=128 << 20, ctx=None):
         self.device, self.jobs, self.offset = device, [], 0
@@ -693,18 +691,45 @@ class WgradBatch:
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
         self._retired = []      # outgrown buffers stay alive: kernels on another stream may still read them
 
-    def reserve(self, nbytes):
-        """Device address of ``nbytes`` of slab space that stays untouched until finish() (for partial sums a kernel
-        other than the weight-gradient ones leaves: see add_job)."""
-        nbytes = (int(nbytes) + 255) // 256 * 256
-        if self.offset + nbytes > self.ws.numel():
+    def _alloc(self, sizes):
+        """Base addresses of slab regions of ``sizes`` bytes (each rounded up to 256).  A workspace too small for all of
+        them is replaced by one of max(need, 2 x old) bytes; the pending jobs are reduced first, since their slabs cannot
+        move."""
+        sizes = [(int(n) + 255) // 256 * 256 for n in sizes]
+        need = sum(sizes)
+        if self.offset + need > self.ws.numel():
             if self.jobs:
                 self.finish()
             self._retired.append(self.ws)
-            self.ws = torch.empty(max(nbytes, 2 * self.ws.numel()), dtype=torch.uint8, device=self.device)
-        base = self.ws.data_ptr() + self.offset
-        self.offset += nbytes
-        return base
+            self.ws = torch.empty(max(need, 2 * self.ws.numel()), dtype=torch.uint8, device=self.device)
+        bases = []
+        for sz in sizes:
+            bases.append(self.ws.data_ptr() + self.offset)
+            self.offset += sz
+        return bases
+
+    @staticmethod
+    def _job_arrays(jobs, addends=None):
+        """The reduction entry points' view of ``jobs``: (slab bases, outputs, slab counts, floats per slab, count,
+        addends).  ``addends`` = {output address: tensor added to that gradient}; the last member is None without them."""
+        import ctypes
+        n = len(jobs)
+        arrs = [(t * n)(*[j[i] for j in jobs]) for i, t in enumerate((ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                                       ctypes.c_int))]
+        adds = None
+        if addends:
+            adds = (ctypes.c_void_p * n)(*[(addends[j[1]].data_ptr() if (j[1] in addends and j[2] > 0) else None)
+                                           for j in jobs])
+        return (*arrs, n, adds)
+
+    def _take_jobs(self):
+        jobs, self.jobs, self.offset = self.jobs, [], 0
+        return jobs
+
+    def reserve(self, nbytes):
+        """Device address of ``nbytes`` of slab space that stays untouched until finish() (for partial sums a kernel
+        other than the weight-gradient ones leaves: see add_job)."""
+        return self._alloc([nbytes])[0]
 
     def add_job(self, base, out, nslab, jtotal):
         """A reduction job over slabs someone else wrote: out[j] = sum of nslab slabs of jtotal floats at ``base``."""
@@ -717,18 +742,12 @@ class WgradBatch:
         B, a, dp, hp, wp = p.shape
         b, dq, hq, wq = q.shape[1], q.shape[2], q.shape[3], q.shape[4]
         nbytes = int(lib().nvf_wgrad_workspace(B, a, b, k, dp, hp, wp))
-        if self.offset + nbytes > self.ws.numel():
-            if self.jobs:    # cannot move slabs that are already in flight: finish them first
-                self.finish()
-            self._retired.append(self.ws)
-            self.ws = torch.empty(max(nbytes, 2 * self.ws.numel()), dtype=torch.uint8, device=self.device)
-        base = self.ws.data_ptr() + self.offset
+        base = self._alloc([nbytes])[0]
         nslab = ctypes.c_int(0)
         check(lib().nvf_wgrad_partial(_ptr(p), _ptr(q), _ptr(out), base, nbytes, B, a, b, k, stride, pad, dp, hp, wp,
                                       dq, hq, wq, out_mode, _NAIVE, ctypes.byref(nslab), _stream()),
               "nvf_wgrad_partial")
         self.jobs.append((base, out.data_ptr(), nslab.value, a * b * k ** 3))
-        self.offset += (nbytes + 255) // 256 * 256
 
     def add_mfma3(self, ps, qs, outs):
         """conv2 / up2 / conv1 weight gradients of the narrow trunk: one partial-sum launch, three reduction jobs."""
@@ -736,16 +755,7 @@ class WgradBatch:
         _f32(*ps, *qs, *outs)
         B = ps[0].shape[0]
         jt = (4096, 8000, 4096)
-        sizes = [(512 * j * 4 + 255) // 256 * 256 for j in jt]
-        if self.offset + sum(sizes) > self.ws.numel():
-            if self.jobs:
-                self.finish()
-            self._retired.append(self.ws)
-            self.ws = torch.empty(max(sum(sizes), 2 * self.ws.numel()), dtype=torch.uint8, device=self.device)
-        bases = []
-        for sz in sizes:
-            bases.append(self.ws.data_ptr() + self.offset)
-            self.offset += sz
+        bases = self._alloc([512 * j * 4 for j in jt])
         nsl = (ctypes.c_int * 3)()
         check(lib().nvf_wgrad_mfma3_partial(_parr(ps), _parr(qs), (ctypes.c_void_p * 3)(*bases), B, nsl, _ctx(self.ctx),
                                             _stream()), "nvf_wgrad_mfma3_partial")
@@ -756,16 +766,7 @@ class WgradBatch:
         import ctypes
         _f32(*ps, *qs, *outs)
         n = len(jt)
-        sizes = [(max_slabs * j * 4 + 255) // 256 * 256 for j in jt]
-        if self.offset + sum(sizes) > self.ws.numel():
-            if self.jobs:
-                self.finish()
-            self._retired.append(self.ws)
-            self.ws = torch.empty(max(sum(sizes), 2 * self.ws.numel()), dtype=torch.uint8, device=self.device)
-        bases = []
-        for sz in sizes:
-            bases.append(self.ws.data_ptr() + self.offset)
-            self.offset += sz
+        bases = self._alloc([max_slabs * j * 4 for j in jt])
         nsl = (ctypes.c_int * n)()
         check(fn(_parr(ps), _parr(qs), (ctypes.c_void_p * n)(*bases), ps[0].shape[0], nsl, _stream()), what)
         for h in range(n):
@@ -775,7 +776,7 @@ class WgradBatch:
         """up1 / conv0 weight gradients of the narrow trunk: one partial-sum launch, two reduction jobs."""
         self._grouped(lib().nvf_wgrad_up1_conv0_partial, "nvf_wgrad_up1_conv0_partial", ps, qs, outs, (16000, 16000), 512)
 
-    def add_trunk5(self, ps, qs, outs, bias_outs=None, heads=None, sums=None, coef=None):
+    def add_trunk5(self, ps, qs, outs, bias_outs=None, heads=None, sums=None, coef=None, stem_jobs=None):
         """conv2 / up2 / conv1 / up1 / conv0 weight gradients of the narrow trunk: one partial-sum launch (which also
         carries a queued latent tail), five reduction jobs.  ps/qs/outs: add_mfma3's three, then add_up1_conv0's two.
         ``bias_outs`` = (conv2's bias gradient, conv1's): the launch also leaves the channel sums of their dY (two more
@@ -783,32 +784,26 @@ class WgradBatch:
         ``heads`` = (dls, xs, outs) of add_heads3 (narrow decoder, needs bias_outs): the heads' weight gradients as
         further workgroups of the same launch.  ``sums`` = (tensors, outs) of multi_channel_sum (needs heads): its first
         pass rides in the launch too, its final pass is queued in the context (self.sums_done is set); ``coef`` =
-        (src, live): two floats the launch copies for finish_and_flush_tail's reduction."""
+        (src, live): two floats the launch copies for finish_and_flush_tail's reduction.  ``stem_jobs``: the reduction
+        jobs stem_bwd_queue returned, whose slabs this launch writes; they join the job list after the launch, ahead
+        of its own."""
         import ctypes
         _f32(*ps, *qs, *outs)
         B = ps[0].shape[0]
         self.sums_done = False
         jt = (4096, 8000, 4096, 16000, 16000) + ((8, 8) if bias_outs is not None else ())
-        sizes = [(512 * j * 4 + 255) // 256 * 256 for j in jt]
+        sizes = [512 * j * 4 for j in jt]
         if heads is not None:
             hd, hx, ho = heads
             _f32(*hd, *hx, *ho)
             hcs = [x.shape[1] for x in hx]
-            sizes += [(_HEADS_SLABS * c * 27 * 4 + 255) // 256 * 256 for c in hcs]
-        if self.offset + sum(sizes) > self.ws.numel():
-            if self.jobs:
-                self.finish()
-            self._retired.append(self.ws)
-            self.ws = torch.empty(max(sum(sizes), 2 * self.ws.numel()), dtype=torch.uint8, device=self.device)
-        bases = []
-        for sz in sizes:
-            bases.append(self.ws.data_ptr() + self.offset)
-            self.offset += sz
+            sizes += [_HEADS_SLABS * c * 27 * 4 for c in hcs]
+        bases = self._alloc(sizes)
         nsl = (ctypes.c_int * 5)()
+        hn = (ctypes.c_int * 3)()
         if heads is not None and sums is not None:
             st, so = sums
             _f32(*st, *so)
-            hn = (ctypes.c_int * 3)()
             total = sum(t.shape[1] for t in st)
             ws = workspace(lib().nvf_multi_channel_sum_workspace(total), st[0].device, "mchsum", self.ctx)
             check(lib().nvf_wgrad_trunk5_heads_sums_partial(
@@ -817,17 +812,12 @@ class WgradBatch:
                 _iarr([t.shape[1] for t in st]), _iarr([t[0, 0].numel() for t in st]), len(st), _ptr(ws), ws.numel(),
                 _ptr(coef[0]) if coef else None, _ptr(coef[1]) if coef else None, B,
                 nsl, hn, _ctx(self.ctx), _stream()), "nvf_wgrad_trunk5_heads_sums_partial")
-            for h in range(3):
-                self.jobs.append((bases[7 + h], ho[h].data_ptr(), hn[h], hcs[h] * 27))
             self.sums_done = True
         elif heads is not None:
-            hn = (ctypes.c_int * 3)()
             check(lib().nvf_wgrad_trunk5_heads_partial(
                 _parr(ps), _parr(qs), (ctypes.c_void_p * 5)(*bases[:5]), (ctypes.c_void_p * 3)(bases[5], None, bases[6]),
                 _parr(hd), _parr(hx), (ctypes.c_void_p * 3)(*bases[7:10]), _HEADS_SLABS, B, nsl, hn, _ctx(self.ctx),
                 _stream()), "nvf_wgrad_trunk5_heads_partial")
-            for h in range(3):
-                self.jobs.append((bases[7 + h], ho[h].data_ptr(), hn[h], hcs[h] * 27))
         elif bias_outs is None:
             check(lib().nvf_wgrad_trunk5_partial(_parr(ps), _parr(qs), (ctypes.c_void_p * 5)(*bases[:5]), B, nsl,
                                                  _ctx(self.ctx), _stream()), "nvf_wgrad_trunk5_partial")
@@ -836,30 +826,21 @@ class WgradBatch:
             check(lib().nvf_wgrad_trunk5_partial_bias(_parr(ps), _parr(qs), (ctypes.c_void_p * 5)(*bases[:5]),
                                                       (ctypes.c_void_p * 3)(bases[5], None, bases[6]), B, nsl,
                                                       _ctx(self.ctx), _stream()), "nvf_wgrad_trunk5_partial_bias")
-        for h in range(5):
-            self.jobs.append((bases[h], outs[h].data_ptr(), nsl[h], jt[h]))
+        self.jobs += stem_jobs or []
+        if heads is not None:
+            self.jobs += [(bases[7 + h], ho[h].data_ptr(), hn[h], hcs[h] * 27) for h in range(3)]
+        self.jobs += [(bases[h], outs[h].data_ptr(), nsl[h], jt[h]) for h in range(5)]
         if bias_outs is not None:
             self.jobs.append((bases[5], bias_outs[0].data_ptr(), nsl[0], 8))
             self.jobs.append((bases[6], bias_outs[1].data_ptr(), nsl[2], 8))
 
-    def add_heads3(self, dls, xs, outs, max_slabs=None):
+    def add_heads3(self, dls, xs, outs, max_slabs=_HEADS_SLABS):
         """Weight gradients of the three classifier heads: one partial-sum launch, three reduction jobs."""
         import ctypes
-        if max_slabs is None:
-            max_slabs = _HEADS_SLABS
         _f32(*dls, *xs, *outs)
         B = xs[0].shape[0]
         cs = [x.shape[1] for x in xs]
-        sizes = [(max_slabs * c * 27 * 4 + 255) // 256 * 256 for c in cs]
-        if self.offset + sum(sizes) > self.ws.numel():
-            if self.jobs:
-                self.finish()
-            self._retired.append(self.ws)
-            self.ws = torch.empty(max(sum(sizes), 2 * self.ws.numel()), dtype=torch.uint8, device=self.device)
-        bases = []
-        for sz in sizes:
-            bases.append(self.ws.data_ptr() + self.offset)
-            self.offset += sz
+        bases = self._alloc([max_slabs * c * 27 * 4 for c in cs])
         nsl = (ctypes.c_int * 3)()
         check(lib().nvf_heads3_wgrad_partial(_parr(dls), _parr(xs), (ctypes.c_void_p * 3)(*bases), _iarr(cs),
                                              _iarr([x.shape[-1] for x in xs]), B, max_slabs, nsl, _stream()),
@@ -872,82 +853,51 @@ class WgradBatch:
         ``addends``: {gradient data_ptr: tensor added to that gradient}; ``adam``: NvfAdamFuse applied to every weight
         gradient element written (both need the one-launch form: <= 16 jobs)."""
         import ctypes
-        jobs = self.jobs
-        if not jobs or len(jobs) > 16 or not tensors:
+        if not self.jobs or len(self.jobs) > 16 or not tensors:
             if addends or adam is not None:
                 raise RuntimeError("finish_with_sums: addends / fused Adam need the one-launch reduction")
             self.finish()
             if tensors:
                 multi_channel_sum(tensors, outs, ctx=self.ctx)
             return
-        self.jobs, self.offset = [], 0
+        jobs = self._take_jobs()
         _f32(*tensors)
         _f32(*outs)
-        n, nt = len(jobs), len(tensors)
         total = sum(t.shape[1] for t in tensors)
         ws = workspace(lib().nvf_multi_channel_sum_workspace(total), tensors[0].device, "mchsum", self.ctx)
-        adds = None
-        if addends:
-            adds = (ctypes.c_void_p * n)(*[(addends[j[1]].data_ptr() if (j[1] in addends and j[2] > 0) else None)
-                                           for j in jobs])
         check(lib().nvf_wgrad_reduce_multi_and_sums_fused(
-            (ctypes.c_void_p * n)(*[j[0] for j in jobs]), (ctypes.c_void_p * n)(*[j[1] for j in jobs]),
-            (ctypes.c_int * n)(*[j[2] for j in jobs]), (ctypes.c_int * n)(*[j[3] for j in jobs]), n, adds,
-            None if adam is None else ctypes.byref(adam),
+            *self._job_arrays(jobs, addends), None if adam is None else ctypes.byref(adam),
             _parr(tensors), _parr(outs), _iarr([t.shape[1] for t in tensors]), _iarr([t[0, 0].numel() for t in tensors]),
-            nt, tensors[0].shape[0], _ptr(ws), ws.numel(), _ctx(self.ctx), _stream()),
+            len(tensors), tensors[0].shape[0], _ptr(ws), ws.numel(), _ctx(self.ctx), _stream()),
             "nvf_wgrad_reduce_multi_and_sums_fused")
 
     def finish_and_flush_tail(self, addends, adam, tail, ranges):
         """The slab reduction (addends, fused optimiser) and the context's queued final passes + step tail in ONE
         launch (nvf_wgrad_reduce_finals_tail): for steps whose partial bias sums were made earlier (add_trunk5 sums=)."""
         import ctypes
-        jobs = self.jobs
-        n = len(jobs)
-        if not (0 < n <= 16) or self.ctx is None:
+        if not (0 < len(self.jobs) <= 16) or self.ctx is None:
             raise RuntimeError("finish_and_flush_tail: 1..16 reduction jobs and a step context are required")
-        self.jobs, self.offset = [], 0
-        adds = None
-        if addends:
-            adds = (ctypes.c_void_p * n)(*[(addends[j[1]].data_ptr() if (j[1] in addends and j[2] > 0) else None)
-                                           for j in jobs])
+        jobs = self._take_jobs()
         flat = [int(v) for r in ranges for v in r]
         arr = (ctypes.c_int64 * max(len(flat), 1))(*flat)
-        check(lib().nvf_wgrad_reduce_finals_tail(
-            (ctypes.c_void_p * n)(*[j[0] for j in jobs]), (ctypes.c_void_p * n)(*[j[1] for j in jobs]),
-            (ctypes.c_int * n)(*[j[2] for j in jobs]), (ctypes.c_int * n)(*[j[3] for j in jobs]), n, adds,
-            ctypes.byref(adam), _ctx(self.ctx), ctypes.byref(tail), arr, len(ranges), _stream()),
-            "nvf_wgrad_reduce_finals_tail")
+        check(lib().nvf_wgrad_reduce_finals_tail(*self._job_arrays(jobs, addends), ctypes.byref(adam), _ctx(self.ctx),
+                                                 ctypes.byref(tail), arr, len(ranges), _stream()),
+              "nvf_wgrad_reduce_finals_tail")
 
     def finish_and_flush(self, addends):
         """The slab reduction (with addends) and the context's queued final passes in ONE launch, no optimiser
         (nvf_wgrad_reduce_finals): data-parallel steps, whose all-reduce and step tail follow."""
-        import ctypes
-        jobs = self.jobs
-        n = len(jobs)
-        if not (0 < n <= 16) or self.ctx is None:
+        if not (0 < len(self.jobs) <= 16) or self.ctx is None:
             raise RuntimeError("finish_and_flush: 1..16 reduction jobs and a step context are required")
-        self.jobs, self.offset = [], 0
-        adds = None
-        if addends:
-            adds = (ctypes.c_void_p * n)(*[(addends[j[1]].data_ptr() if (j[1] in addends and j[2] > 0) else None)
-                                           for j in jobs])
-        check(lib().nvf_wgrad_reduce_finals(
-            (ctypes.c_void_p * n)(*[j[0] for j in jobs]), (ctypes.c_void_p * n)(*[j[1] for j in jobs]),
-            (ctypes.c_int * n)(*[j[2] for j in jobs]), (ctypes.c_int * n)(*[j[3] for j in jobs]), n, adds,
-            _ctx(self.ctx), _stream()), "nvf_wgrad_reduce_finals")
+        jobs = self._take_jobs()
+        check(lib().nvf_wgrad_reduce_finals(*self._job_arrays(jobs, addends), _ctx(self.ctx), _stream()),
+              "nvf_wgrad_reduce_finals")
 
     def finish(self):
-        import ctypes
-        jobs, self.jobs, self.offset = self.jobs, [], 0
+        jobs = self._take_jobs()
         for i in range(0, len(jobs), 16):
-            chunk = jobs[i:i + 16]
-            n = len(chunk)
-            check(lib().nvf_wgrad_reduce_multi((ctypes.c_void_p * n)(*[j[0] for j in chunk]),
-                                               (ctypes.c_void_p * n)(*[j[1] for j in chunk]),
-                                               (ctypes.c_int * n)(*[j[2] for j in chunk]),
-                                               (ctypes.c_int * n)(*[j[3] for j in chunk]), n, _stream()),
-                  "nvf_wgrad_reduce_multi")
+            bases, outs, nslabs, sizes, n, _ = self._job_arrays(jobs[i:i + 16])
+            check(lib().nvf_wgrad_reduce_multi(bases, outs, nslabs, sizes, n, _stream()), "nvf_wgrad_reduce_multi")
 
 
 def channel_sum(x, out=None, accumulate=False):

@@ -834,3 +834,29 @@ def test_stem_forward_inside_the_step_head_launch(gpu, monkeypatch, tag, batch, 
     for k in a1:
         assert torch.equal(a1[k], a0[k]), k
     assert l1 == l0 and torch.equal(g1, g0)
+
+
+def test_stem_jobs_survive_a_growing_five_gradient_launch(gpu):
+    """The queued stem backward writes up0's gradient slabs inside the five-gradient launch, so its two reduction jobs may
+    only join the job list with that launch.  When the launch has to grow the slab workspace, the reductions already
+    pending run first; up0's must not be among them (they would sum slabs nobody has written yet and be dropped).  A
+    narrow batch-16 engine whose workspace starts at 4 MiB grows it in both of its first two steps: every gradient must
+    agree with the default engine's."""
+    from nvfpcc_amd import ops
+    got = {}
+    for small in (False, True):
+        net, eng, gt, dist, emb = make("S", gpu, nblk=40)
+        if small:
+            eng._wg = ops.WgradBatch(eng.dev, nbytes=4 << 20, ctx=eng.ctx)
+        rng = np.random.default_rng(3)
+        grads = []
+        for _ in range(2):
+            eng.train_step(rng.permutation(40)[:16], 1, update=False)
+            assert not eng.ctx.stem_pending() and not eng.ctx.tail_pending()
+            grads.append(eng.flat_g.clone())
+        assert len(eng._wg._retired) == (2 if small else 0)
+        got[small] = grads
+    for step, (g_small, g_ref) in enumerate(zip(got[True], got[False])):
+        for name, (o, m) in eng.slices.items():
+            assert torch.isfinite(g_small[o:o + m]).all(), (step, name)
+            close(g_small[o:o + m], g_ref[o:o + m], tol=2e-6)
