@@ -190,6 +190,7 @@ def encode(args):
     print('[Recon] Pacc: %.4f Nacc: %.4f MSE1: %.4f PSNR1: %.4f' % (
         m[0] / max(m[1], 1), m[2] / max(m[3], 1), *_psnr1(m[4], m[5])))
     write_ply_ascii('rc_enc.ply', pts)
+    _print_pc_error(args, pts, dev)
 
 
 def decode(args):
@@ -215,6 +216,17 @@ def decode(args):
     pts, counts = reconstruct_points(net, latents[:n].contiguous(), total_pack['origins'][:n], args.thh,
                                      batch=max(int(args.batchsize), 1))
     write_ply_ascii('rc_dec.ply', pts)
+    _print_pc_error(args, pts, dev)
+
+
+def _print_pc_error(args, pts, dev):
+    """--ref_ply: symmetric D1 / D2 geometry PSNR of the written cloud against the original (nvfpcc_amd.pc_metrics)."""
+    if args.ref_ply is None:
+        return
+    from nvfpcc_amd.pc_metrics import geometry_psnr, read_ply_points
+    ref, ref_normals = read_ply_points(args.ref_ply)
+    r = geometry_psnr(ref, pts, ref_normals=ref_normals, device=dev)
+    print('[PCError] D1 PSNR: %.4f D2 PSNR: %.4f' % (r['d1_psnr'], r['d2_psnr']))
 
 
 def build_parser():
@@ -252,6 +264,8 @@ def build_parser():
     p.add_argument('--device', default='cuda', help='HIP device (the reference hard-codes cuda).')
     p.add_argument('--epochs', type=int, default=501, help='Number of epochs (the reference hard-codes 501).')
     p.add_argument('--seed', type=int, default=0, help='Seed of the counter RNG behind the q=1 / latent noise.')
+    p.add_argument('--ref_ply', default=None,
+                   help='Original cloud (ASCII PLY): encode / decode also print its D1 / D2 geometry PSNR.')
     return p
 
 

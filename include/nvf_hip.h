@@ -732,6 +732,35 @@ int nvf_threshold_compact(const float* p, float thh, const int32_t* offsets, con
 int nvf_nearest_dist2(const int32_t* pts, const int32_t* blk_off, const int32_t* origins, const int32_t* nb_off,
                       const int32_t* nb_idx, int32_t* d2out, int nblocks, void* stream);
 
+/* ---- point-cloud metrics: exact 1-NN, k-NN + PCA normals, D1 / D2 error sums (nvfpcc_amd/pc_metrics.py) -----------
+ * Geometry PSNR as pc_error defines it, for clouds of integer coordinates in [0, 1024) (the caller checks the range).
+ *   nn_Y(p)      the point of Y with the least squared distance to p; ties go to the LOWEST input index of Y.
+ *   D1(X->Y)     mean_i |x_i - nn_Y(x_i)|^2 (exact integers; equals pc_error's for clouds without duplicate points).
+ *   D2(X->Y)     mean_i ((nn_Y(x_i) - x_i) . n_X[i])^2, pc_error's point-to-plane formula.
+ * A SORTED CLOUD is int32 [n, 4] rows (x, y, z, input index) ordered by the cell key
+ *   key = ((x >> 3) << 8 | (y >> 3) << 4 | (z >> 3)) << 9 | (x & 7) << 6 | (y & 7) << 3 | (z & 7)   of the cell
+ *   (x, y, z) = (px >> 3, py >> 3, pz >> 3)  (edge 8 voxels; 64-voxel super-cells in the high bits), and cell_start
+ *   int32 [NVF_PC_CELLS + 1] is the exclusive prefix sum of the per-key counts.  The order inside a cell is free.
+ * nvf_pc_nearest: for every row of query_sorted, nn_idx / nn_d2 [n_query] at the row's input index receive the input
+ *   index of its nearest target and the squared distance (int32, exact).  Exact however far the nearest target is.
+ * nvf_pc_knn_normals: the k nearest points of every point of one cloud within itself (the point included, ordered by
+ *   (squared distance, input index)), and normals [n, 3] = the unit eigenvector of the smallest eigenvalue of their
+ *   covariance (integer sums, fp64 Jacobi), in input order; knn_idx [n, k] (may be NULL) gets the k-NN sets.
+ *   cloud_xyz int32 [n, 3] is the same cloud in input order.  3 <= k <= 32 and n >= k, else NVF_EINVAL.
+ * nvf_pc_error_sums: over i < n_query with e = target_xyz[nn_idx[i]] - query_xyz[i] (both [., 3], input order):
+ *   sums[0] = sum |e|^2 (int64), sums[1] = max |e|^2, d2_sum[0] = sum (e . n)^2 in fp64 where n = normals[i], or
+ *   normals[nn_idx[i]] when normals_of_target (normals == NULL: no D2 sum).  Fixed-order two-stage reduction:
+ *   repeated calls give the same bits.  workspace >= nvf_pc_workspace_bytes(n_query, .) bytes, 8-byte aligned. */
+#define NVF_PC_CELLS (128 * 128 * 128)
+size_t nvf_pc_workspace_bytes(int n_query, int n_target);
+int nvf_pc_nearest(const int32_t* query_sorted, int n_query, const int32_t* target_sorted, const int32_t* cell_start,
+                   int n_target, int32_t* nn_idx, int32_t* nn_d2, void* stream);
+int nvf_pc_knn_normals(const int32_t* cloud_sorted, const int32_t* cell_start, const int32_t* cloud_xyz, int n, int k,
+                       float* normals, int32_t* knn_idx, void* stream);
+int nvf_pc_error_sums(const int32_t* query_xyz, int n_query, const int32_t* target_xyz, const int32_t* nn_idx,
+                      const float* normals, int normals_of_target, int64_t* sums, double* d2_sum, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,10 @@ PROTOTYPES = {
     "nvf_nearest_dist2": (I, [P, P, P, P, P, P, I, P]),
     "nvf_threshold_count": (I, [P, F, P, I, I, P]),
     "nvf_threshold_compact": (I, [P, F, P, P, P, I, I, P]),
+    "nvf_pc_workspace_bytes": (Z, [I, I]),
+    "nvf_pc_nearest": (I, [P, I, P, P, I, P, P, P]),
+    "nvf_pc_knn_normals": (I, [P, P, P, I, I, P, P, P]),
+    "nvf_pc_error_sums": (I, [P, I, P, P, P, I, P, P, P, Z, P]),
 }
 
 
