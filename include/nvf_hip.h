@@ -387,15 +387,21 @@ int nvf_wgrad_mfma3_partial(const float* const* ps, const float* const* qs, floa
                             int* nslabs, NvfStepCtx* ctx, void* stream);
 
 /* up1's and conv0's weight gradients of the narrow trunk in one launch (partial sums): job 0 = up1 (p = X [B,16,8^3],
- * q = dY [B,8,19^3]), job 1 = conv0 (p = X [B,8,4^3], q = dY [B,16,8^3]); slabs[j]: up to 512 slabs of 16000 floats */
+ * q = dY [B,8,19^3]), job 1 = conv0 (p = X [B,8,4^3], q = dY [B,16,8^3]).  slabs[j] must hold 512 slabs of 16000
+ * floats; nslabs[j] <= 512 at every batch (above 512 work items a workgroup walks several).  Both jobs are VALU tile
+ * kernels in the direct summation order. */
 int nvf_wgrad_up1_conv0_partial(const float* const* ps, const float* const* qs, float* const* slabs, int batch,
                                 int* nslabs, void* stream);
 
 /* the five weight gradients of the narrow trunk above the stem in ONE launch (partial sums): jobs 0-2 as
  * nvf_wgrad_mfma3_partial (conv2, up2, conv1), jobs 3-4 as nvf_wgrad_up1_conv0_partial (up1, conv0): the two small VALU
  * jobs fill the slots the short matrix-core workgroups leave while conv2's are still running.  slabs[0..2]: 512 slabs of
- * 4096 / 8000 / 4096 floats, slabs[3..4]: up to 512 slabs of 16000 floats; nslabs[5].  Results identical to the two
- * separate launches.  Like nvf_wgrad_mfma3_partial it carries a queued latent tail as its first workgroup. */
+ * 4096 / 8000 / 4096 floats, slabs[3..4]: 512 slabs of 16000 floats; nslabs[5], every entry <= 512 at every batch.
+ * conv0 (job 4) takes one of two forms: on the matrix cores with one slab per block (nslabs[4] = batch) when
+ * batch <= 512 and the context does not ask for the direct forms; otherwise the tile job of
+ * nvf_wgrad_up1_conv0_partial, capped at 512 slabs.  The matrix-core form sums in another order: it agrees with the
+ * separate launch to fp32 rounding, not bit for bit; the tile form keeps the direct summation order.  Like
+ * nvf_wgrad_mfma3_partial it carries a queued latent tail as its first workgroup. */
 int nvf_wgrad_trunk5_partial(const float* const* ps, const float* const* qs, float* const* slabs, int batch,
                              int* nslabs, NvfStepCtx* ctx, void* stream);
 /* ... and, with bias_slabs[0] / bias_slabs[2] non-NULL (entry 1 is ignored), the per-workgroup channel sums of conv2's

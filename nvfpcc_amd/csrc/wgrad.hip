@@ -1067,7 +1067,7 @@ static int launch_trunk_wgrads(const float* const* ps, const float* const* qs, f
       WgDims d{};
       d.batch = batch; d.bc = 8; d.items = batch * (WgUp1::W / WgUp1::TZ) * (WgUp1::W / WgUp1::TY);
       int up1_cap = nvf_tune_int("NVF_UP1_CAP", 64);
-      if (up1_cap < 1) up1_cap = 64;
+      if (up1_cap < 1 || up1_cap > kMaxSlabs) up1_cap = 64;     // (a tuning build's knob cannot outgrow slabs[3])
       int n = d.items < up1_cap ? d.items : up1_cap;
       d.items_per_wg = (d.items + n - 1) / n;
       n = (d.items + d.items_per_wg - 1) / d.items_per_wg;
@@ -1078,8 +1078,10 @@ static int launch_trunk_wgrads(const float* const* ps, const float* const* qs, f
     }
 #endif
     // conv0's gradient on the matrix cores too (conv0_wgrad_mfma_body: one workgroup and one slab per block) unless the
-    // caller's context asks for the direct forms (another summation order)
-    if (!(nvf_ctx_ok(ctx) && ctx->direct_forms) && nvf_tune_int("NVF_CONV0_WG_MFMA", 1)) {
+    // caller's context asks for the direct forms (another summation order) -- and only while its one slab per block
+    // fits the region: slabs[4] holds kMaxSlabs slabs, and the regions behind it belong to other jobs of this launch.
+    // Above kMaxSlabs blocks the tile job fill_up1_conv0 prepared stays (capped at kMaxSlabs, several items a workgroup).
+    if (!(nvf_ctx_ok(ctx) && ctx->direct_forms) && batch <= kMaxSlabs && nvf_tune_int("NVF_CONV0_WG_MFMA", 1)) {
       u.conv0_mfma = 5 * batch;
       u.nx[1] = 0;
       nslabs[4] = batch;
@@ -1139,7 +1141,11 @@ extern "C" int nvf_wgrad_mfma3_partial(const float* const* ps, const float* cons
 
 // ... and jobs 3, 4 = up1 (p = X [B,16,8^3], q = dY [B,8,19^3]), conv0 (p = X [B,8,4^3], q = dY [B,16,8^3]) of
 // nvf_wgrad_up1_conv0_partial in the same launch: all five weight gradients of the narrow trunk above the stem.
-// slabs[3], slabs[4]: up to 512 slabs of 16000 floats.  Same results as the two separate launches.
+// slabs[3], slabs[4]: room for 512 slabs of 16000 floats each; no job reports more than 512.  conv2 / up2 / conv1 / up1
+// give the bits of nvf_wgrad_mfma3_partial and of the direct forms' choices there.  conv0 runs on the matrix cores (one
+// slab per block) at batch <= 512 unless the context asks for the direct forms, and agrees with
+// nvf_wgrad_up1_conv0_partial to rounding, not bit for bit; above 512 blocks, or with the direct forms, it is the tile
+// job capped at 512 slabs.
 extern "C" int nvf_wgrad_trunk5_partial(const float* const* ps, const float* const* qs, float* const* slabs, int batch,
                                         int* nslabs, NvfStepCtx* ctx, void* stream) {
   return launch_trunk_wgrads(ps, qs, slabs, batch, nslabs, 5, ctx, stream);

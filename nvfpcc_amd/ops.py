@@ -726,6 +726,14 @@ class WgradBatch:
         jobs, self.jobs, self.offset = self.jobs, [], 0
         return jobs
 
+    @staticmethod
+    def _check_slabs(what, counts, caps):
+        """A launch that reports more slabs than the region allocated for them holds has written over its neighbours:
+        nothing computed from this workspace can be trusted."""
+        for i, (n, cap) in enumerate(zip(counts, caps)):
+            if not 0 <= n <= cap:
+                raise RuntimeError(f"{what}: job {i} reports {n} slabs, its region holds {cap}")
+
     def reserve(self, nbytes):
         """Device address of ``nbytes`` of slab space that stays untouched until finish() (for partial sums a kernel
         other than the weight-gradient ones leaves: see add_job)."""
@@ -759,6 +767,7 @@ class WgradBatch:
         nsl = (ctypes.c_int * 3)()
         check(lib().nvf_wgrad_mfma3_partial(_parr(ps), _parr(qs), (ctypes.c_void_p * 3)(*bases), B, nsl, _ctx(self.ctx),
                                             _stream()), "nvf_wgrad_mfma3_partial")
+        self._check_slabs("nvf_wgrad_mfma3_partial", nsl, (512,) * 3)
         for h in range(3):
             self.jobs.append((bases[h], outs[h].data_ptr(), nsl[h], jt[h]))
 
@@ -769,6 +778,7 @@ class WgradBatch:
         bases = self._alloc([max_slabs * j * 4 for j in jt])
         nsl = (ctypes.c_int * n)()
         check(fn(_parr(ps), _parr(qs), (ctypes.c_void_p * n)(*bases), ps[0].shape[0], nsl, _stream()), what)
+        self._check_slabs(what, nsl, (max_slabs,) * n)
         for h in range(n):
             self.jobs.append((bases[h], outs[h].data_ptr(), nsl[h], jt[h]))
 
@@ -826,6 +836,9 @@ class WgradBatch:
             check(lib().nvf_wgrad_trunk5_partial_bias(_parr(ps), _parr(qs), (ctypes.c_void_p * 5)(*bases[:5]),
                                                       (ctypes.c_void_p * 3)(bases[5], None, bases[6]), B, nsl,
                                                       _ctx(self.ctx), _stream()), "nvf_wgrad_trunk5_partial_bias")
+        self._check_slabs("add_trunk5", nsl, (512,) * 5)
+        if heads is not None:
+            self._check_slabs("add_trunk5 (heads)", hn, (_HEADS_SLABS,) * 3)
         self.jobs += stem_jobs or []
         if heads is not None:
             self.jobs += [(bases[7 + h], ho[h].data_ptr(), hn[h], hcs[h] * 27) for h in range(3)]
@@ -845,6 +858,7 @@ class WgradBatch:
         check(lib().nvf_heads3_wgrad_partial(_parr(dls), _parr(xs), (ctypes.c_void_p * 3)(*bases), _iarr(cs),
                                              _iarr([x.shape[-1] for x in xs]), B, max_slabs, nsl, _stream()),
               "nvf_heads3_wgrad_partial")
+        self._check_slabs("nvf_heads3_wgrad_partial", nsl, (max_slabs,) * 3)
         for h in range(3):
             self.jobs.append((bases[h], outs[h].data_ptr(), nsl[h], cs[h] * 27))
 

@@ -21,7 +21,7 @@ def gpu():
     return torch.device("cuda")
 
 
-def make(tag, gpu, nblk=6):
+def make(tag, gpu, nblk=6, winograd=None):
     from nvfpcc_amd import network
     from nvfpcc_amd.engine import TrainEngine
     from nvfpcc_amd.model import Net
@@ -37,7 +37,7 @@ def make(tag, gpu, nblk=6):
     gt = torch.from_numpy(gts).float().to(gpu)
     dist = torch.from_numpy(dists).float().to(gpu)
     emb = make_emb(nblk, cfg["ch"], cfg["emb_seed"]).to(gpu)
-    eng = TrainEngine(net, gt, dist, n_points_total=917 * 936.0, emb=emb, seed=0, **H)
+    eng = TrainEngine(net, gt, dist, n_points_total=917 * 936.0, emb=emb, seed=0, winograd=winograd, **H)
     return net, eng, gt, dist, emb
 
 
@@ -194,6 +194,96 @@ def test_full_size_step_is_the_sum_of_its_mini_batches(gpu):
     for name, (off, n) in eng.slices.items():
         close(g_all[off:off + n], acc[off:off + n], tol=2e-4)
     assert np.isfinite(loss_all)
+
+
+def _block_sums(eng):
+    """The block-summed loss terms of the last step: the three focal terms and the latent bits (float64, host)."""
+    return torch.cat([eng.last["loss_terms"][:3].double().cpu(), eng.last["latent_bits"].double().cpu().reshape(-1)])
+
+
+def _whole_and_mini_batches(eng, nblk, mini=16):
+    """One ``nblk``-block step and the float64 sum of its ``mini``-block steps (same noise draw, weight-rate term counted
+    once): (gradient, block-summed loss terms) of both."""
+    whole = list(range(nblk))
+    n_pts = float(eng.counts[whole].sum())
+    eng.noise_step = 0
+    eng.train_step(whole, 2, update=False, n_pts=n_pts)
+    g_all, t_all = eng.flat_g.clone(), _block_sums(eng)
+    assert nblk % mini == 0
+    eng.rate_grad_scale = float(mini) / nblk
+    acc = torch.zeros_like(g_all, dtype=torch.float64)
+    t_acc = torch.zeros_like(t_all)
+    for r in range(nblk // mini):
+        eng.noise_step = 0
+        eng.train_step(whole[mini * r:mini * (r + 1)], 2, update=False, n_pts=n_pts)
+        acc += eng.flat_g.double()
+        t_acc += _block_sums(eng)
+    eng.rate_grad_scale = 1.0
+    return g_all, t_all, acc, t_acc
+
+
+@pytest.mark.parametrize("tag", ["S", "W"])
+def test_528_block_step_is_the_sum_of_its_mini_batches(tag, gpu):
+    """The property of test_full_size_step_is_the_sum_of_its_mini_batches one past the last switch point: at 528 = 33 x 16
+    blocks every slab region of the weight gradients is at its 512-slab capacity (the narrow trunk's conv0 leaves the
+    matrix cores for the capped tile job, the heads' and the wide layers' workgroups walk several items) and the bias sums
+    run in groups of five blocks.  Both decoders, q = 2, per parameter slice at the 256-block test's 2e-4; the focal terms
+    and the latent bits (sums over blocks) at the 2e-5 test_train_step_gradients_equal_autograd_path puts on the loss."""
+    net, eng, gt, dist, emb = make(tag, gpu, nblk=528)
+    g_all, t_all, acc, t_acc = _whole_and_mini_batches(eng, 528)
+    assert torch.isfinite(g_all).all()
+    print(f"{tag} 528: loss terms rel err {((t_all - t_acc).abs() / t_acc.abs()).max().item():.2e}")
+    assert ((t_all - t_acc).abs() <= 2e-5 * t_acc.abs()).all(), (t_all, t_acc)
+    worst = max((float((g_all[o:o + n].double() - acc[o:o + n]).abs().max() / max(float(acc[o:o + n].abs().max()), 1e-12)), name)
+                for name, (o, n) in eng.slices.items())
+    print(f"{tag} 528: worst slice {worst[1]} rel err {worst[0]:.2e}")
+    for name, (off, n) in eng.slices.items():
+        close(g_all[off:off + n], acc[off:off + n], tol=2e-4)
+
+
+def test_528_block_step_default_forms_equal_the_direct_forms(gpu):
+    """The narrow 528-block step of the default engine against TrainEngine(winograd=False) on the same blocks: the direct
+    forms take the capped tile job for conv0 and no Winograd kernel anywhere -- an independent path through the same
+    step.  Two fp32 evaluations of one 528-block gradient: per slice at the 2e-4 the suite puts on such a pair
+    (test_full_size_step_is_the_sum_of_its_mini_batches), block-summed loss terms at 2e-5."""
+    got = {}
+    for wino in (None, False):
+        net, eng, gt, dist, emb = make("S", gpu, nblk=528, winograd=wino)
+        whole = list(range(528))
+        eng.train_step(whole, 2, update=False, n_pts=float(eng.counts[whole].sum()))
+        got[wino] = (eng.flat_g.clone(), _block_sums(eng), eng.slices)
+        assert torch.isfinite(got[wino][0]).all()
+        del net, eng
+        torch.cuda.empty_cache()
+    (g_w, t_w, slices), (g_d, t_d, _) = got[None], got[False]
+    assert ((t_w - t_d).abs() <= 2e-5 * t_d.abs()).all(), (t_w, t_d)
+    worst = max((float((g_w[o:o + n] - g_d[o:o + n]).abs().max() / max(float(g_d[o:o + n].abs().max()), 1e-12)), name)
+                for name, (o, n) in slices.items())
+    print(f"S 528 default vs direct: worst slice {worst[1]} rel err {worst[0]:.2e}")
+    for name, (off, n) in slices.items():
+        close(g_w[off:off + n], g_d[off:off + n], tol=2e-4)
+
+
+@pytest.mark.parametrize("batch", [33, 65])
+@pytest.mark.parametrize("tag", ["S", "W"])
+def test_train_step_one_past_a_switch_point_equals_autograd_path(tag, batch, gpu):
+    """test_train_step_gradients_equal_autograd_path one past the 32-block switch (the heads' one-launch forward + loss +
+    backward-data, the stem's backward inside the five-gradient launch and the one-launch loss all stop at 32 blocks) and
+    the 64-block one (tuned tile kernels of the gather / transposed convolutions, up2's variant)."""
+    net, eng, gt, dist, emb = make(tag, gpu, nblk=70)
+    idx = [int(i) for i in np.random.default_rng(batch).permutation(70)[:batch]]
+    n_pts = float(eng.counts[idx].sum())
+    loss_ref, g_ref, _ = module_grads(net, eng, emb, gt, dist, idx, n_pts)
+    eng.flat_g.zero_()
+    eng.train_step(idx, 2, update=False)
+    assert torch.isfinite(eng.flat_g).all()
+    print(f"{tag} {batch}: loss rel err {abs(eng.loss_value() - loss_ref) / abs(loss_ref):.2e}")
+    assert abs(eng.loss_value() - loss_ref) < 2e-5 * abs(loss_ref)
+    worst = max((float((eng.flat_g[o:o + n] - g_ref[o:o + n]).abs().max() / max(float(g_ref[o:o + n].abs().max()), 1e-12)), name)
+                for name, (o, n) in eng.slices.items())
+    print(f"{tag} {batch}: worst slice {worst[1]} rel err {worst[0]:.2e}")
+    for name, (off, n) in eng.slices.items():
+        close(eng.flat_g[off:off + n], g_ref[off:off + n])
 
 
 def test_weight_noise_and_latent_noise_are_reproducible(gpu):

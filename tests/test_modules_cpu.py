@@ -67,3 +67,35 @@ def test_dataset_permutation_and_epoch_order(tmp_path):
     ds2 = LoadedVoxelDataset(prefix + "_l5_origins.npy", prefix + "_l5_gt_grid.npy", prefix + "_l5_dist.npy",
                              shuffle=False)
     assert ds2[3][0].item() == 3
+
+
+@pytest.mark.parametrize("a,b,k,stride,pad,n", [(8, 8, 4, 1, 0, 7), (8, 8, 5, 2, 0, 4), (16, 8, 5, 2, 0, 3), (8, 16, 5, 2, 2, 4),
+                                               (1, 8, 3, 1, 1, 6)])
+def test_shifted_slice_reference_equals_torch_autograd(a, b, k, stride, pad, n):
+    """tests/wgrad_ref64.py (the float64 reference of the batch-edge GPU tests) against torch's own float64 convolution
+    backward, for every (k, stride, pad) the decoder has and as running sums over batch prefixes with a chunk smaller than a
+    prefix.  Stride-1 layers: p = dY, q = X of F.conv3d (dw as [out, in]); stride 2: p = X, q = dY of F.conv_transpose3d."""
+    import torch.nn.functional as F
+    from tests.wgrad_ref64 import wgrad_ref64, channel_sum_ref64
+    g = torch.Generator().manual_seed(a + 3 * b + k)
+    B, ends = 5, [2, 3, 5]
+    if stride == 1:
+        x = torch.randn(B, b, n + k - 1 - 2 * pad, n + k - 1 - 2 * pad, n + k - 1 - 2 * pad, generator=g)
+        gy = torch.randn(B, a, n, n, n, generator=g)
+        p, q = gy, x
+    else:
+        x = torch.randn(B, a, n, n, n, generator=g)
+        m = 2 * (n - 1) + 5 - 2 * pad + (1 if pad else 0)          # output_padding 1 on the padded layers (4^3 -> 8^3)
+        gy = torch.randn(B, b, m, m, m, generator=g)
+        p, q = x, gy
+    got = wgrad_ref64(p, q, k, stride, pad, ends=ends, chunk_bytes=1)
+    sums = channel_sum_ref64(q, ends)
+    for e, dw, s in zip(ends, got, sums):
+        if stride == 1:
+            w = torch.zeros(a, b, k, k, k, dtype=torch.float64, requires_grad=True)
+            F.conv3d(x[:e].double(), w, None, 1, pad).backward(gy[:e].double())
+        else:
+            w = torch.zeros(a, b, 5, 5, 5, dtype=torch.float64, requires_grad=True)
+            F.conv_transpose3d(x[:e].double(), w, None, 2, pad, 1 if pad else 0).backward(gy[:e].double())
+        assert (dw - w.grad).abs().max().item() < 1e-12 * max(w.grad.abs().max().item(), 1.0)
+        assert torch.allclose(s, q[:e].double().sum(dim=(0, 2, 3, 4)), rtol=1e-13, atol=1e-12)
