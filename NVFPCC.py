@@ -9,7 +9,11 @@ engine (nvfpcc_amd/engine.py) instead of a DataLoader + autograd loop.
         --load_weights 0500_quantized_q4.ckpt --load_emb ckpts/0500_emb.ckpt --thh 0.65 --pack_fn pack.pk
     python NVFPCC.py decode pack.pk --batchsize 1 --chanstr 8,16,8,8 --ch 3 --thh 0.64
 
-Additions over the reference (all optional): --device, --epochs, --seed; multi-GPU training when launched
+    python NVFPCC.py encode longdress_vox10_1300.ply ... --thh_mode count     # threshold chosen here, carried in pack.pk
+    python NVFPCC.py decode pack.pk --batchsize 1 --chanstr 8,16,8,8 --ch 3   # no --thh needed then
+
+Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --thh_mode (count | block-count | d1:
+nvfpcc_amd/thh_select.py picks the occupancy threshold at encode time and a `thh_pack` key carries it); multi-GPU training when launched
 through torch.distributed.run (one process per GPU, leaf blocks sharded, one RCCL all-reduce per step).
 Headless: no GUI window, no IPython shell.
 """
@@ -175,22 +179,63 @@ def encode(args):
         info = net.get_latent_code(emb)
     print('Estimated bit rate: ', info['latent_likelihood'].sum())
     latent_pack = latent_codec.arithmetic_enc(info['quantized_latent'], info['sigma'], info['mu'])
+    total_pack = {'net_weight_pack': net_weight_pack, 'origins': np_origins, 'latent_pack': latent_pack}
+    batch = max(int(args.batchsize), 1)
+    thh, sel = args.thh, None
+    if args.thh_mode not in (None, 'fixed'):
+        sel = _select_threshold(args.thh_mode, net, info['quantized_latent'].detach(), data, np_origins, dev, batch)
+        thh = sel['t']
+        total_pack['thh_pack'] = sel['pack']
     with open(args.pack_fn, 'wb') as f:
-        pickle.dump({'net_weight_pack': net_weight_pack, 'origins': np_origins, 'latent_pack': latent_pack}, f)
+        pickle.dump(total_pack, f)
     print('Start to reconstruct')
-    pts, counts = reconstruct_points(net, info['quantized_latent'].detach(), np_origins, args.thh,
-                                     batch=max(int(args.batchsize), 1))
+    pts, counts = reconstruct_points(net, info['quantized_latent'].detach(), np_origins, thh, batch=batch)
     gt, dist = data.to_device(dev)
     with torch.no_grad():
         out = torch.cat([net.reconstruct(info['quantized_latent'][i:i + 64].contiguous(), 2)
                          for i in range(0, len(data), 64)], 0)
-    m = ops.metrics(out, gt, dist, args.thh, args.thh).cpu().numpy()
+    if isinstance(thh, torch.Tensor):       # one threshold per block: the six sums block by block
+        m = torch.zeros(6, device=dev)
+        for b, t in enumerate(thh.tolist()):
+            ops.metrics(out[b:b + 1], gt[b:b + 1], dist[b:b + 1], t, t, out=m, accumulate=True)
+        m = m.cpu().numpy()
+    else:
+        m = ops.metrics(out, gt, dist, thh, thh).cpu().numpy()
     latent_bits = len(latent_pack['latent_byte_stream']) * 8
-    print('[Latent code] Gross bpp: %.4f' % ((latent_bits + net_bits) / data.N))
+    side_bits = 0 if sel is None else 8 * len(sel['pack'])
+    if sel is not None:
+        print(sel['line'])
+    print('[Latent code] Gross bpp: %.4f' % ((latent_bits + net_bits + side_bits) / data.N))
     print('[Recon] Pacc: %.4f Nacc: %.4f MSE1: %.4f PSNR1: %.4f' % (
         m[0] / max(m[1], 1), m[2] / max(m[3], 1), *_psnr1(m[4], m[5])))
     write_ply_ascii('rc_enc.ply', pts)
     _print_pc_error(args, pts, dev)
+
+
+def _select_threshold(mode, net, latents, data, origins, dev, batch):
+    """--thh_mode count | block-count | d1 at the encoder: the eval forward of every block stays resident and
+    nvfpcc_amd.thh_select picks the threshold(s).  -> {'t': float | tensor [N_leaf], 'pack': bytes, 'line': str}."""
+    from nvfpcc_amd import thh_select as ts
+    ts.check_resident(latents.shape[0])
+    with torch.no_grad():
+        p_all = torch.cat([net.reconstruct(latents[i:i + batch].contiguous(), 2)
+                           for i in range(0, latents.shape[0], batch)], 0)
+    k_b = data.gt_grid.reshape(data.N_leaf, -1).astype(bool).sum(1)
+    if mode == 'block-count':
+        sel = ts.choose(mode, p_all, block_counts=k_b)
+    elif mode == 'count':
+        sel = ts.choose(mode, p_all, n_points=int(data.N))
+    else:
+        gt8 = torch.from_numpy(np.ascontiguousarray(data.gt_grid != 0).astype(np.uint8)).to(dev)
+        sel = ts.choose(mode, p_all, origins=origins, n_points=int(data.N), gt=gt8,
+                        d2=ts.d2_from_dist(data.dist).to(dev).contiguous())
+    if sel['note']:
+        print('[Threshold] ' + sel['note'])
+    decided, t = sel['mode'], sel['t']
+    if decided == 'block-count':
+        return {'t': t, 'pack': ts.write_thh_pack(decided, block_counts=k_b),
+                'line': ts.threshold_line(decided, block_counts=k_b, thresholds=t.cpu().numpy())}
+    return {'t': t, 'pack': ts.write_thh_pack(decided, t=t), 'line': ts.threshold_line(decided, t=t)}
 
 
 def decode(args):
@@ -213,8 +258,23 @@ def decode(args):
     latents = latent_codec.arithmetic_dec(total_pack['latent_pack']).to(dev)
     n = int(args.N)
     print('Start to reconstruct')
-    pts, counts = reconstruct_points(net, latents[:n].contiguous(), total_pack['origins'][:n], args.thh,
-                                     batch=max(int(args.batchsize), 1))
+    thh, block_counts, used = args.thh, None, []
+    side = total_pack.get('thh_pack')
+    if side is None and args.thh_mode not in (None, 'fixed'):
+        raise SystemExit(f"decode --thh_mode {args.thh_mode}: {args.input} carries no thh_pack (it was encoded without "
+                         f"--thh_mode); decode it with --thh instead")
+    if side is not None and args.thh_mode != 'fixed':
+        from nvfpcc_amd import thh_select as ts
+        mode, value = ts.read_thh_pack(side)
+        if mode == 'block-count':
+            block_counts = value[:n]
+        else:
+            thh = value
+            print(ts.threshold_line(mode, t=thh))
+    pts, counts = reconstruct_points(net, latents[:n].contiguous(), total_pack['origins'][:n], thh,
+                                     batch=max(int(args.batchsize), 1), block_counts=block_counts, thh_out=used)
+    if block_counts is not None:
+        print(ts.threshold_line('block-count', block_counts=block_counts, thresholds=torch.cat(used).cpu().numpy()))
     write_ply_ascii('rc_dec.ply', pts)
     _print_pc_error(args, pts, dev)
 
@@ -264,6 +324,11 @@ def build_parser():
     p.add_argument('--device', default='cuda', help='HIP device (the reference hard-codes cuda).')
     p.add_argument('--epochs', type=int, default=501, help='Number of epochs (the reference hard-codes 501).')
     p.add_argument('--seed', type=int, default=0, help='Seed of the counter RNG behind the q=1 / latent noise.')
+    p.add_argument('--thh_mode', default=None, choices=['fixed', 'count', 'block-count', 'd1'],
+                   help='How the occupancy threshold is chosen.  Absent: --thh, nothing added to the pack.  encode: '
+                        'count = keep as many voxels as the input has points; block-count = the same per block; '
+                        'd1 = the candidate with the best symmetric D1 PSNR.  The choice travels in the pack '
+                        '(thh_pack) and decode uses it; decode --thh_mode fixed ignores it and uses --thh.')
     p.add_argument('--ref_ply', default=None,
                    help='Original cloud (ASCII PLY): encode / decode also print its D1 / D2 geometry PSNR.')
     return p

@@ -767,6 +767,29 @@ int nvf_pc_error_sums(const int32_t* query_xyz, int n_query, const int32_t* targ
                       const float* normals, int normals_of_target, int64_t* sums, double* d2_sum, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ---- occupancy selection (nvfpcc_amd/thh_select.py, csrc/occ_select.hip) -------------------------------------------
+ * The sort key of a probability is its bit pattern (monotone for floats >= 0; -0.0 counts as +0.0).  A key above the
+ * bits of 1.0f (NaN, a negative value, a value over 1) is an input error: such voxels go into no bin and are counted
+ * in bad[b] (uint32 [batch], always written); the caller raises on a non-zero total.  All sums are integers.
+ * nvf_occ_hist: p [batch, voxels]; bin = (key >> shift) & (2^nbits - 1), 1 <= nbits <= 11, shift + nbits <= 32.
+ *   prefix (may be NULL) uint32 [batch]: block b counts only voxels with key >> (shift + nbits) == prefix[b].
+ *   count uint32 [batch, 2^nbits].  Riders, each pair NULL or not together: d2 int32 [batch, voxels] with values in
+ *   [0, 2^25) -> sum_d2 uint64 [batch, 2^nbits]; gt uint8 [batch, voxels] (non-zero = occupied) -> count_gt uint32
+ *   [batch, 2^nbits].  Three calls (shift, nbits) = (21, 11), (10, 11), (0, 10) walk the key from the top.
+ * nvf_occ_hist_edges: the same with bin = number of edges e with p > e: edges float [nedges] ascending on the
+ *   device, 1 <= nedges <= 2047, rows of nedges + 1 bins.  The voxels with p > edges[i] are the bins above i.
+ * nvf_threshold_count_v / nvf_threshold_compact_v: nvf_threshold_count / nvf_threshold_compact with one threshold per
+ *   block, thh float [batch] on the device. */
+int nvf_occ_hist(const float* p, int batch, int voxels, int shift, int nbits, const uint32_t* prefix,
+                 const int32_t* d2, const uint8_t* gt, uint32_t* count, uint64_t* sum_d2, uint32_t* count_gt,
+                 uint32_t* bad, void* stream);
+int nvf_occ_hist_edges(const float* p, int batch, int voxels, const float* edges, int nedges, const int32_t* d2,
+                       const uint8_t* gt, uint32_t* count, uint64_t* sum_d2, uint32_t* count_gt, uint32_t* bad,
+                       void* stream);
+int nvf_threshold_count_v(const float* p, const float* thh, int32_t* counts, int batch, int voxels, void* stream);
+int nvf_threshold_compact_v(const float* p, const float* thh, const int32_t* offsets, const int32_t* origins,
+                            int32_t* coords, int batch, int dim, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

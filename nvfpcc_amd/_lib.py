@@ -131,6 +131,10 @@ PROTOTYPES = {
     "nvf_pc_nearest": (I, [P, I, P, P, I, P, P, P]),
     "nvf_pc_knn_normals": (I, [P, P, P, I, I, P, P, P]),
     "nvf_pc_error_sums": (I, [P, I, P, P, P, I, P, P, P, Z, P]),
+    "nvf_occ_hist": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P]),
+    "nvf_occ_hist_edges": (I, [P, I, I, P, I, P, P, P, P, P, P, P]),
+    "nvf_threshold_count_v": (I, [P, P, P, I, I, P]),
+    "nvf_threshold_compact_v": (I, [P, P, P, P, P, I, I, P]),
 }
 
 

@@ -1264,17 +1264,76 @@ def uniform(shape, device, seed, stream_id):
 
 # ---------------------------------------------------------------- occupancy -> points
 def threshold_points(p, thh, origins=None):
-    """p [B,1,D,D,D] -> int32 [n,3] points (origin + (z,y,x)) in (b,z,y,x) raster order, plus per-block counts."""
+    """p [B,1,D,D,D] -> int32 [n,3] points (origin + (z,y,x)) in (b,z,y,x) raster order, plus per-block counts.
+    thh: a float (one threshold for all blocks), or a float32 tensor [B] on the device (one per block)."""
     _f32(p)
     B, dim = p.shape[0], p.shape[-1]
+    per_block = isinstance(thh, torch.Tensor)
+    if per_block:
+        _f32(thh)
+        if thh.shape != (B,):
+            raise RuntimeError(f"per-block thresholds must have shape ({B},), got {tuple(thh.shape)}")
     counts = torch.empty(B, dtype=torch.int32, device=p.device)
-    check(lib().nvf_threshold_count(_ptr(p), float(thh), _ptr(counts), B, dim ** 3, _stream()),
-          "nvf_threshold_count")
+    if per_block:
+        check(lib().nvf_threshold_count_v(_ptr(p), _ptr(thh), _ptr(counts), B, dim ** 3, _stream()),
+              "nvf_threshold_count_v")
+    else:
+        check(lib().nvf_threshold_count(_ptr(p), float(thh), _ptr(counts), B, dim ** 3, _stream()),
+              "nvf_threshold_count")
     offsets = (torch.cumsum(counts, 0, dtype=torch.int32) - counts).contiguous()
     total = int(counts.sum().item())
     coords = torch.empty((max(total, 1), 3), dtype=torch.int32, device=p.device)
     if origins is not None:
         origins = origins.to(device=p.device, dtype=torch.int32).contiguous()
-    check(lib().nvf_threshold_compact(_ptr(p), float(thh), _ptr(offsets), _ptr(origins), _ptr(coords), B, dim,
-                                      _stream()), "nvf_threshold_compact")
+    if per_block:
+        check(lib().nvf_threshold_compact_v(_ptr(p), _ptr(thh), _ptr(offsets), _ptr(origins), _ptr(coords), B, dim,
+                                            _stream()), "nvf_threshold_compact_v")
+    else:
+        check(lib().nvf_threshold_compact(_ptr(p), float(thh), _ptr(offsets), _ptr(origins), _ptr(coords), B, dim,
+                                          _stream()), "nvf_threshold_compact")
     return coords[:total], counts
+
+
+def _occ_riders(p, d2, gt, nbins):
+    B = p.shape[0]
+    _chk(d2, gt)
+    for t, dt, what in ((d2, torch.int32, "d2"), (gt, torch.uint8, "gt")):
+        if t is not None and (t.dtype != dt or t.numel() != p.numel()):
+            raise RuntimeError(f"{what} must be {dt} with one value per voxel of p")
+    sum_d2 = None if d2 is None else torch.empty((B, nbins), dtype=torch.int64, device=p.device)
+    count_gt = None if gt is None else torch.empty((B, nbins), dtype=torch.int32, device=p.device)
+    return sum_d2, count_gt
+
+
+def occ_hist(p, shift=None, nbits=None, prefix=None, d2=None, gt=None, edges=None):
+    """Per-block histogram of the probabilities p [B, ...] (float32 in [0, 1]) -> (count int32 [B, bins], sum_d2 int64
+    [B, bins] or None, count_gt int32 [B, bins] or None, bad int32 [B]).
+
+    Radix form: bin = (bits(p) >> shift) & (2^nbits - 1); prefix int32 [B] (optional) keeps, in block b, only the voxels
+    whose key bits above the digit equal prefix[b].  Edge form (edges float32 [E] ascending, instead of shift / nbits):
+    bin = number of edges below p, E + 1 bins.  Riders: d2 int32 and gt uint8, one value per voxel.  bad[b] counts the
+    voxels of block b that are NaN or outside [0, 1]: they are in no bin, and the caller decides (include/nvf_hip.h)."""
+    _f32(p)
+    B = p.shape[0]
+    voxels = p.numel() // max(B, 1)
+    bad = torch.empty(B, dtype=torch.int32, device=p.device)
+    if edges is not None:
+        _f32(edges)
+        if shift is not None or nbits is not None or prefix is not None:
+            raise RuntimeError("occ_hist takes either edges or (shift, nbits[, prefix])")
+        nbins = edges.numel() + 1
+        count = torch.empty((B, nbins), dtype=torch.int32, device=p.device)
+        sum_d2, count_gt = _occ_riders(p, d2, gt, nbins)
+        check(lib().nvf_occ_hist_edges(_ptr(p), B, voxels, _ptr(edges), edges.numel(), _ptr(d2), _ptr(gt), _ptr(count),
+                                       _ptr(sum_d2), _ptr(count_gt), _ptr(bad), _stream()), "nvf_occ_hist_edges")
+        return count, sum_d2, count_gt, bad
+    if prefix is not None:
+        _chk(prefix)
+        if prefix.dtype != torch.int32 or prefix.shape != (B,):
+            raise RuntimeError(f"prefix must be int32 of shape ({B},)")
+    nbins = 1 << int(nbits)
+    count = torch.empty((B, nbins), dtype=torch.int32, device=p.device)
+    sum_d2, count_gt = _occ_riders(p, d2, gt, nbins)
+    check(lib().nvf_occ_hist(_ptr(p), B, voxels, int(shift), int(nbits), _ptr(prefix), _ptr(d2), _ptr(gt), _ptr(count),
+                             _ptr(sum_d2), _ptr(count_gt), _ptr(bad), _stream()), "nvf_occ_hist")
+    return count, sum_d2, count_gt, bad

@@ -11,18 +11,35 @@ from . import ops
 
 
 @torch.no_grad()
-def reconstruct_points(net, latents, origins, thh, batch=64, q=2):
+def reconstruct_points(net, latents, origins, thh, batch=64, q=2, block_counts=None, thh_out=None):
     """latents [N,ch,2,2,2] (already rounded) on the device -> (int64 [n,3] points, per-block counts).
 
     Voxel coordinate order inside a block is (d0, d1, d2) of the 32^3 grid, the order
-    torch.nonzero(out[b, 0] > thh) yields; points = coords + origins[b] (NVFPCC.py:535-538, 635-637)."""
+    torch.nonzero(out[b, 0] > thh) yields; points = coords + origins[b] (NVFPCC.py:535-538, 635-637).
+
+    Per-block thresholds (optional): thh may be a float32 tensor [N], one threshold per block; or block_counts (int
+    [N]) asks for them from the probabilities themselves -- block b keeps its block_counts[b] most probable voxels,
+    ties included (thh_select.threshold_for_count; thh is then ignored).  thh_out, a list, receives the per-block
+    thresholds used, batch by batch."""
     dev = latents.device
     origins = torch.as_tensor(np.asarray(origins)).to(torch.int32)
+    if block_counts is not None:
+        from .thh_select import threshold_for_count
+        block_counts = torch.as_tensor(np.asarray(block_counts)).to(device=dev, dtype=torch.int64)
+    elif isinstance(thh, torch.Tensor):
+        thh = thh.to(device=dev, dtype=torch.float32)
     pts, counts = [], []
     for lo in range(0, latents.shape[0], batch):
         hi = min(lo + batch, latents.shape[0])
         out = net.reconstruct(latents[lo:hi].contiguous(), q)
-        p, c = ops.threshold_points(out, thh, origins[lo:hi].to(dev))
+        t = thh
+        if block_counts is not None:
+            t = threshold_for_count(out, block_counts[lo:hi])
+        elif isinstance(thh, torch.Tensor):
+            t = thh[lo:hi].contiguous()
+        if thh_out is not None and isinstance(t, torch.Tensor):
+            thh_out.append(t)
+        p, c = ops.threshold_points(out, t, origins[lo:hi].to(dev))
         pts.append(p.cpu())
         counts.append(c.cpu())
     return torch.cat(pts, 0).long().numpy(), torch.cat(counts, 0).numpy()
