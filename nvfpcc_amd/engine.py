@@ -16,7 +16,9 @@ Result-preserving shortcuts taken from the reference's own data flow: the mini-b
 uses the latent gradients (they are zeroed at NVFPCC.py:226) and the latent phase never uses the
 decoder weight gradients (zeroed at NVFPCC.py:150), so each phase skips the half it discards.
 """
+import functools
 import os
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -58,9 +60,52 @@ _STEM_IN_HEAD = True
 _HEADS_IN_TRUNK5 = True     # heads' weight gradients as workgroups of the five-gradient launch (narrow decoder)
 
 
-def _NAIVE_OFF():
-    """The one-launch groupings bypass the variant switch of the per-layer entry points: only with the tuned kernels."""
-    return ops._NAIVE == 0
+class StepPlan(NamedTuple):
+    """The launches one step consists of (plan_step).  batch_and_prepare, forward and backward branch on these fields only."""
+    want_w: bool                # decoder gradients (the mini-batch phase)
+    want_emb: bool              # latent gradients (the latent phase)
+    stem_fwd: str               # "head": in the step head's launch / "latent": with the latent generator / "fused" / "layers"
+    latent_fwd_fused: bool      # latent generator + quantiser in one launch (where the stem's forward did not take them)
+    heads: str                  # "deferred": forward too in the loss launch / "fused_loss" / "heads3" / "layers"
+    head_bias_in_loss: bool     # the heads' bias gradients are partials of the loss launch
+    heads_in_trunk5: bool       # the heads' weight gradients are workgroups of the five-gradient launch
+    trunk5: bool                # the five trunk weight gradients in one launch (add_trunk5); else per layer
+    conv0_wgrad_in_stem: bool   # conv0's weight gradient rides in the stem's backward
+    stem_bwd: str               # "queued": inside the five-gradient launch / "partial" / "plain" / "layers"
+    tail_queued: bool           # the latent tail rides in the next weight-gradient launch; else three launches
+    sums_in_trunk5: bool        # partial bias sums inside the five-gradient launch (where the step head carried the rate job)
+    fused_optimiser: bool       # Adam + epoch sums inside the slab reduction and the finals launch (single GPU)
+
+
+@functools.lru_cache(maxsize=None)
+def plan_step(narrow, wide, winograd, fused_stem, fused_latent_stem, heads3, ch, batch, want_w, want_emb, fuse, hook,
+              naive, head_bias_in_loss, sums_in_trunk5, stem_in_trunk5, stem_in_head, heads_in_trunk5,
+              step_head=False, defer_heads=False):
+    """Which launches a step of ``batch`` blocks consists of, from the engine's class flags, the caller's request (``fuse``:
+    it handed over the optimiser's coefficients; ``step_head``: batch_and_prepare(stem_mode=...) ran; ``defer_heads``:
+    forward(defer_heads=True)), ops._NAIVE and the five module switches.  No tensors.  What launch_trunk_wgrads (wgrad.hip)
+    answers with NVF_EINVAL is an implication between the fields (tests/test_step_plan.py).  ``winograd`` and the 64-block
+    switch points select kernel forms inside a launch (_conv, _dx_conv, _dx_convT), never a launch."""
+    # the one-launch groupings bypass the variant switch of the per-layer entry points: only with the tuned kernels
+    tuned = naive == 0
+    small = batch <= 32         # the cooperative launches keep one arrival counter per block, 32 of them
+    stem_fwd = ("head" if step_head and stem_in_head and fused_stem and fused_latent_stem and small and tuned else
+                "latent" if ch <= 8 and tuned and fused_stem and fused_latent_stem else
+                "fused" if fused_stem else "layers")
+    fused_loss = heads3 and small and tuned
+    heads = (("deferred" if defer_heads and want_w else "fused_loss") if fused_loss else
+             "heads3" if heads3 else "layers")
+    trunk5 = want_w and narrow and tuned
+    in_trunk5 = trunk5 and heads3 and heads_in_trunk5
+    tail = want_w and not want_emb and ch <= 8 and tuned
+    stem_bwd = ("queued" if stem_in_trunk5 and tail and in_trunk5 and fused_stem and small else
+                "layers" if not fused_stem else "partial" if want_w else "plain")
+    return StepPlan(want_w=want_w, want_emb=want_emb, stem_fwd=stem_fwd, latent_fwd_fused=ch <= 8 and tuned, heads=heads,
+                    head_bias_in_loss=want_w and head_bias_in_loss and fused_loss, heads_in_trunk5=in_trunk5,
+                    trunk5=trunk5, conv0_wgrad_in_stem=want_w and fused_stem and not trunk5, stem_bwd=stem_bwd,
+                    tail_queued=tail, sums_in_trunk5=in_trunk5 and sums_in_trunk5, fused_optimiser=fuse and not hook)
+
+
 TRUNK = ("up0", "conv0", "up1", "conv1", "up2", "conv2", "conv2_cls")
 HEADS = ("conv1_cls", "conv0_cls")
 # layers whose backward-data also runs on the matrix cores: name -> (pair axis, largest batch it is used for)
@@ -140,7 +185,6 @@ class TrainEngine:
         self._rate_retired = []   # outgrown weight-rate buffers stay referenced (kernels in flight)
         self._graphs_captured = 0  # GraphedTrainStep instances that baked this engine's buffers into a graph
         self.tail_done = False    # the last backward pass applied the optimiser itself (fused tail)
-        self._stem_gdn_in_finals = False
         self._tail_ranges = {}    # gradient index ranges no fused launch covers, per set of covered intervals
         self.collective_mode = None   # "graph" / "host": where GraphedTrainStep puts the all-reduce (dist.attach)
         # the three classifier heads go through the one-launch kernels (instantiated for the two decoders of BASELINE.json);
@@ -255,29 +299,26 @@ class TrainEngine:
             t["nbias"] = m.b.numel()
         row = {name: i for i, (name, _, _) in enumerate(mods)}
         self._rows = row
-        named = list(self.layers.items())
-        jobs = [(L.w_fwd, L.wp_f, 0, L.cin, 8) for _, L in named if L.wp_f is not None]
-        meta = [(row[nm], 0) for nm, L in named if L.wp_f is not None]
-        jobs += [(L.w_bwd, L.wp_b, L.bwd_pair, L.cout, 8) for _, L in named if L.wp_b is not None]
-        meta += [(row[nm], 1) for nm, L in named if L.wp_b is not None]
         wk, wc = (41, 16) if self.wide else (40, 8)          # Winograd packing of the decoder class
-        jobs += [(L.w_bwd, L.wp_w, wk, L.cout, wc) for _, L in named if L.wp_w is not None]
-        meta += [(row[nm], 1) for nm, L in named if L.wp_w is not None]
-        jobs += [(L.w_fwd, L.wp_wf, wk, L.cin, wc) for _, L in named if L.wp_wf is not None]
-        meta += [(row[nm], 0) for nm, L in named if L.wp_wf is not None]
-        jobs += [(L.w_fwd, L.wp_t, 10, L.cin, 8) for _, L in named if L.wp_t is not None]
-        meta += [(row[nm], 0) for nm, L in named if L.wp_t is not None]
-        jobs += [(L.w_fwd, L.wp_tr, 12, L.cin, 8) for _, L in named if L.wp_tr is not None]
-        meta += [(row[nm], 0) for nm, L in named if L.wp_tr is not None]
-        jobs += [(L.w_bwd, L.wp_s, 20, L.cout, L.cin) for _, L in named if L.wp_s is not None]
-        meta += [(row[nm], 1) for nm, L in named if L.wp_s is not None]
-        # 16-row gather forms: kind 30 (k = 4) / 31 (k = 5), c0 = input channels of the gather, c1 = its output channels
-        jobs += [(L.w_fwd, L.wp_gf, 30, L.cin, L.cout) for _, L in named if L.wp_gf is not None]
-        meta += [(row[nm], 0) for nm, L in named if L.wp_gf is not None]
-        jobs += [(L.w_bwd, L.wp_gb, 30 if L.k == 4 else 31, L.cout, L.cin) for _, L in named if L.wp_gb is not None]
-        meta += [(row[nm], 1) for nm, L in named if L.wp_gb is not None]
-        jobs += [(L.w_fwd, L.wp_t16, 11, L.cin, L.cout) for _, L in named if L.wp_t16 is not None]
-        meta += [(row[nm], 0) for nm, L in named if L.wp_t16 is not None]
+        # (_Layer slot, source, (pack kind, c0, c1)): slot by slot, layers in table order, is the job order inside
+        # nvf_pack_mfma_all / nvf_step_head
+        packs = (("wp_f", "w_fwd", lambda L: (0, L.cin, 8)),
+                 ("wp_b", "w_bwd", lambda L: (L.bwd_pair, L.cout, 8)),
+                 ("wp_w", "w_bwd", lambda L: (wk, L.cout, wc)),
+                 ("wp_wf", "w_fwd", lambda L: (wk, L.cin, wc)),
+                 ("wp_t", "w_fwd", lambda L: (10, L.cin, 8)),
+                 ("wp_tr", "w_fwd", lambda L: (12, L.cin, 8)),
+                 ("wp_s", "w_bwd", lambda L: (20, L.cout, L.cin)),
+                 # 16-row gather forms: kind 30 (k = 4) / 31 (k = 5), c0 = input channels of the gather, c1 = its output channels
+                 ("wp_gf", "w_fwd", lambda L: (30, L.cin, L.cout)),
+                 ("wp_gb", "w_bwd", lambda L: (30 if L.k == 4 else 31, L.cout, L.cin)),
+                 ("wp_t16", "w_fwd", lambda L: (11, L.cin, L.cout)))
+        jobs, meta = [], []
+        for slot, src, form in packs:
+            for nm, L in self.layers.items():
+                if getattr(L, slot) is not None:
+                    jobs.append((getattr(L, src), getattr(L, slot)) + form(L))
+                    meta.append((row[nm], int(src == "w_bwd")))
         assert len(jobs) <= 16
         self._mfma_jobs = jobs
         self._mfma_job_layers = meta           # (layer-table row, 0 = w_fwd / 1 = w_bwd) of each job's source
@@ -311,6 +352,23 @@ class TrainEngine:
             self._rate = (job, add, key, dk, part)
         return self._rate
 
+    def _plan(self, batch, want_w=False, want_emb=False, fuse=False, step_head=False, defer_heads=False):
+        """plan_step for this engine, with the module switches and ops._NAIVE as they are NOW (tests and bench.py assign them)."""
+        return plan_step(self.narrow, self.wide, self.winograd, self.fused_stem, self.fused_latent_stem, self.heads3,
+                         self.ch, batch, want_w, want_emb, fuse, self.grad_hook is not None, ops._NAIVE,
+                         _HEAD_BIAS_IN_LOSS, _SUMS_IN_TRUNK5, _STEM_IN_TRUNK5, _STEM_IN_HEAD, _HEADS_IN_TRUNK5,
+                         step_head, defer_heads)
+
+    def _noise(self):
+        """(step, step_dev) of the counter RNG: the host's counter, or 0 and the device word a captured graph reads."""
+        sd = self._step_dev
+        return (0 if sd is not None else self.noise_step), sd
+
+    def _ec(self):
+        """The entropy coder's (sigma, mu), flattened."""
+        ec = self.net.entropy_coder
+        return ec.sigma.reshape(-1), ec.mu.reshape(-1)
+
     def batch_and_prepare(self, idx_dev, q, with_rate=False, stem_mode=None):
         """_batch(idx_dev) and prepare_weights(q) -- row gather, effective weights, MFMA packings -- as ONE launch
         (``with_rate``: + the weight-rate term's partial sums, consumed by the backward pass of the same step).  Returns
@@ -322,20 +380,18 @@ class TrainEngine:
         srcs = [self.gt, self.dist, self.gt16, self.gt8, self.emb]
         n, rows = len(srcs), idx_dev.numel()
         dsts = [torch.empty((rows,) + tuple(s.shape[1:]), device=s.device) for s in srcs]
-        sd = self._step_dev
+        step, sd = self._noise()
         jobs, meta = self._mfma_jobs, self._mfma_job_layers
         npk = len(jobs)
         iarr = lambda xs: (ctypes.c_int * max(len(xs), 1))(*xs)
-        args = (self.table.data_ptr(), self.nlayers, int(q), self.seed, 0 if sd is not None else self.noise_step,
-                None if sd is None else sd.data_ptr(),
+        args = (self.table.data_ptr(), self.nlayers, int(q), self.seed, step, None if sd is None else sd.data_ptr(),
                 (ctypes.c_void_p * max(npk, 1))(*[j[1].data_ptr() for j in jobs]), iarr([j[2] for j in jobs]),
                 iarr([j[3] for j in jobs]), iarr([j[4] for j in jobs]), iarr([m[0] for m in meta]),
                 iarr([m[1] for m in meta]), npk, (ctypes.c_void_p * n)(*[s.data_ptr() for s in srcs]),
                 (ctypes.c_void_p * n)(*[d.data_ptr() for d in dsts]), (ctypes.c_int * n)(*[s[0].numel() for s in srcs]), n,
                 idx_dev.data_ptr(), rows, ctypes.byref(self._rate_job()[0]) if with_rate else None)
         o = None
-        if (stem_mode is not None and _STEM_IN_HEAD and self.fused_stem and self.fused_latent_stem and rows <= 32
-                and _NAIVE_OFF()):
+        if self._plan(rows, step_head=stem_mode is not None).stem_fwd == "head":
             from ._lib import NvfStemHead
             net = self.net
             g2, ec, ig = net.latent_gen.gdn_2, net.entropy_coder, net.reconstructor.activation
@@ -361,9 +417,9 @@ class TrainEngine:
         return dsts if stem_mode is None else dsts + [o]
 
     def prepare_weights(self, q):
-        sd = self._step_dev
-        check(lib().nvf_prepare_weights(self.table.data_ptr(), self.nlayers, int(q), self.seed,
-                                        0 if sd is not None else self.noise_step, None if sd is None else sd.data_ptr(),
+        step, sd = self._noise()
+        check(lib().nvf_prepare_weights(self.table.data_ptr(), self.nlayers, int(q), self.seed, step,
+                                        None if sd is None else sd.data_ptr(),
                                         torch.cuda.current_stream().cuda_stream), "nvf_prepare_weights")
         if self._mfma_jobs:
             ops.pack_mfma_all(self._mfma_jobs)      # conv1, conv2, up1, up2: every MFMA weight layout, one launch
@@ -410,51 +466,43 @@ class TrainEngine:
         mini-batch that batch_and_prepare(..., stem_mode=mode) returned (None: forward() runs the stem itself)."""
         net, Ls = self.net, self.layers
         a = {"e": e}
+        # (defer_heads is the caller's promise of a weight-gradient backward pass; backward() holds it to that)
+        plan = self._plan(e.shape[0], want_w=defer_heads, step_head=stem is not None, defer_heads=defer_heads)
         g2 = net.latent_gen.gdn_2
-        ec = net.entropy_coder
-        sd = self._step_dev
         ig = net.reconstructor.activation
-        stem_done = False
-        if stem is not None:
+        step, sd = self._noise()
+        noise = dict(block_ids=block_ids, seed=self.seed, step=step, step_dev=sd)
+        if plan.stem_fwd == "head":
             a.update(stem)                    # the step head's launch ran the latent generator, quantiser and stem
-            stem_done = True
-        elif e.shape[1] <= 8 and _NAIVE_OFF() and self.fused_stem and self.fused_latent_stem:   # latent generator,
-            # quantiser and stem in one launch
+        elif plan.stem_fwd == "latent":       # latent generator, quantiser and stem in one launch
             (a["h"], a["lat"], a["x0"], a["lbits"], a["a0"], a["h0"], a["y1"]) = ops.stem_latent_fwd(
-                e, Ls["latent"].w_fwd, Ls["latent"].b_eff, g2.beta, g2.gamma, ec.sigma.reshape(-1), ec.mu.reshape(-1),
-                mode, Ls["up0"].w_fwd, Ls["up0"].b_eff, ig.beta, ig.gamma, Ls["conv0"].w_fwd, Ls["conv0"].b_eff,
-                block_ids=block_ids, seed=self.seed, step=0 if sd is not None else self.noise_step, step_dev=sd)
-            stem_done = True
-        elif e.shape[1] <= 8 and _NAIVE_OFF():         # latent generator + quantiser in one launch
+                e, Ls["latent"].w_fwd, Ls["latent"].b_eff, g2.beta, g2.gamma, *self._ec(), mode, Ls["up0"].w_fwd,
+                Ls["up0"].b_eff, ig.beta, ig.gamma, Ls["conv0"].w_fwd, Ls["conv0"].b_eff, **noise)
+        elif plan.latent_fwd_fused:           # latent generator + quantiser in one launch
             a["h"], a["lat"], a["x0"], a["lbits"] = ops.latent_fwd(
-                e, Ls["latent"].w_fwd, Ls["latent"].b_eff, g2.beta, g2.gamma, ec.sigma.reshape(-1), ec.mu.reshape(-1),
-                mode, block_ids=block_ids, seed=self.seed, step=0 if sd is not None else self.noise_step, step_dev=sd)
+                e, Ls["latent"].w_fwd, Ls["latent"].b_eff, g2.beta, g2.gamma, *self._ec(), mode, **noise)
         else:
             a["h"] = self._conv(Ls["latent"], e, NONE)
             a["lat"] = ops.gdn_fwd(a["h"], g2.beta, g2.gamma, False)
-            a["x0"], a["lbits"], _, _, _ = ops.latent_rate(a["lat"], ec.sigma.reshape(-1), ec.mu.reshape(-1), mode,
-                                                           block_ids=block_ids, seed=self.seed,
-                                                           step=0 if sd is not None else self.noise_step, step_dev=sd)
-        if stem_done:
-            pass
-        elif self.fused_stem:
+            a["x0"], a["lbits"], _, _, _ = ops.latent_rate(a["lat"], *self._ec(), mode, **noise)
+        if plan.stem_fwd == "fused":
             a["a0"], a["h0"], a["y1"] = ops.stem_fwd(a["x0"], Ls["up0"].w_fwd, Ls["up0"].b_eff, ig.beta, ig.gamma,
                                                      Ls["conv0"].w_fwd, Ls["conv0"].b_eff)
-        else:
+        elif plan.stem_fwd == "layers":
             a["a0"] = self._convT(Ls["up0"], a["x0"], NONE)
             a["h0"] = ops.gdn_fwd(a["a0"], ig.beta, ig.gamma, True)
             a["y1"] = self._convT(Ls["conv0"], a["h0"], R)
-        if not self.heads3:
+        if plan.heads == "layers":
             a["p0"] = self._conv(Ls["conv0_cls"], a["y1"], S)
         a["y2"] = self._convT(Ls["up1"], a["y1"], R, train=(mode == "train"))
         a["y3"] = self._conv(Ls["conv1"], a["y2"], R, train=(mode == "train"))
-        if not self.heads3:
+        if plan.heads == "layers":
             a["p1"] = self._conv(Ls["conv1_cls"], a["y3"], S)
         a["y4"] = self._convT(Ls["up2"], a["y3"], R, train=(mode == "train"))
         a["y5"] = self._conv(Ls["conv2"], a["y4"], R, train=(mode == "train"))
-        if self.heads3 and defer_heads and e.shape[0] <= 32 and _NAIVE_OFF():
+        if plan.heads == "deferred":
             a["p0"] = a["p1"] = a["p2"] = None      # nvf_heads3_fwd_loss_bwd_data (backward)
-        elif self.heads3:                           # all three heads in one launch, after the trunk
+        elif plan.heads != "layers":                # all three heads in one launch, after the trunk
             hl = [Ls["conv0_cls"], Ls["conv1_cls"], Ls["conv2_cls"]]
             a["p0"], a["p1"], a["p2"] = ops.heads3_fwd([a["y1"], a["y3"], a["y5"]], [L.w_fwd for L in hl],
                                                        [L.b_eff for L in hl])
@@ -463,7 +511,7 @@ class TrainEngine:
         return a
 
     # ------------------------------------------------------------------ backward
-    def _wgrad_conv(self, L, g_out, x_in):
+    def _wgrad_conv(self, L, g_out, x_in, sums):
         if (self.wide and self.winograd and L.k == 4 and L.cin == 16 and L.cout == 16 and L.pad == 0
                 and g_out.shape[-1] in (32, 16)):
             # the Winograd (y, x) form (wgrad16_wino.hip): slabs for the common reduction (conv2 172 -> 100 us at batch 16)
@@ -472,49 +520,47 @@ class TrainEngine:
             self._wg.add_job(base, L.gk, n, 16384)
         else:
             self._wg.add(g_out, x_in, L.k, 1, L.pad, 0, L.gk)
-        self._bias_jobs.append((g_out, L.gb))
+        sums.append((g_out, L.gb))
 
-    def _wgrad_convT(self, L, g_out, x_in, bias=True):
+    def _wgrad_convT(self, L, g_out, x_in, sums):
         self._wg.add(x_in, g_out, 5, 2, L.pad, 0, L.gk)
-        if bias:        # (False: the kernel that wrote g_out left its channel sums as slabs, see _dx_conv)
-            self._bias_jobs.append((g_out, L.gb))
+        sums.append((g_out, L.gb))
 
-    def _dx_conv(self, L, g_out, x_in, mask=None, addend=None, bias_out=None):
+    def _dx_conv(self, L, g_out, x_in, mask=None, addend=None, bias_out=None, sums=None):
         """Backward-data of a 4^3 convolution.  ``bias_out``: the bias gradient of the layer BELOW (whose masked output
-        gradient this pass writes): the matrix-core kernel leaves its channel sums as slabs for the reduction launch;
-        returns (dx, True) then, (dx, False) when the caller has to sum dx itself."""
+        gradient dx this pass writes).  Where the matrix-core kernel leaves dx's channel sums as slabs, they become a job of
+        the reduction launch; everywhere else (dx, bias_out) joins ``sums``, the step's list for the channel-sum pass."""
+        slabs = False
         if self.wide and L.wp_w is not None and mask is not None and addend is None and g_out.shape[-1] in (32, 16):
             # (the channel sums of dx -- the bias gradient of the layer below -- from this kernel's epilogue, bias_part=:
             # measured neutral, the reduction launch 48.9 -> 44.0 us against + 2.7 / + 2.1 us in the two epilogues)
             dx = ops.conv3d_k4_wino16_bwd(g_out, L.wp_w, mask)
-            return dx if bias_out is None else (dx, False)
-        if L.wp_gb is not None:
+        elif L.wp_gb is not None:
             dx = ops.conv3d_g16_mfma(g_out, L.wp_gb, None, L.cin, 4, 1, 3, tuple(x_in.shape[2:]), addend=addend,
                                      mask=mask)
-            return dx if bias_out is None else (dx, False)
-        if L.wp_w is not None and mask is not None and addend is None and g_out.shape[-1] in (32, 16):
-            if bias_out is not None:
+        elif L.wp_w is not None and mask is not None and addend is None and g_out.shape[-1] in (32, 16):
+            if bias_out is not None and g_out.shape[0] <= 64:
                 # (one slab of 8 sums per work unit: 126 units per block in conv2's default kernel, conv_wino1.hip)
-                base = self._wg.reserve(16384 * 8 * 4) if g_out.shape[0] <= 64 else None
-                if base is not None:
-                    dx, nparts = ops.conv3d_k4_wino_bwd(g_out, L.wp_w, mask, bias_part=base)
-                    self._wg.add_job(base, bias_out, nparts, 8)
-                    return dx, True
-                return ops.conv3d_k4_wino_bwd(g_out, L.wp_w, mask, ppc=_wino_bwd_ppc(g_out)), False
-            return ops.conv3d_k4_wino_bwd(g_out, L.wp_w, mask, ppc=_wino_bwd_ppc(g_out))
-        if L.wp_b is not None and g_out.shape[0] <= L.bwd_max_batch:
+                base = self._wg.reserve(16384 * 8 * 4)
+                dx, nparts = ops.conv3d_k4_wino_bwd(g_out, L.wp_w, mask, bias_part=base)
+                self._wg.add_job(base, bias_out, nparts, 8)
+                slabs = True
+            else:
+                dx = ops.conv3d_k4_wino_bwd(g_out, L.wp_w, mask, ppc=_wino_bwd_ppc(g_out))
+        elif L.wp_b is not None and g_out.shape[0] <= L.bwd_max_batch:
             if bias_out is not None and mask is not None and addend is None:
                 base = self._wg.reserve(4096 * 8 * 4)
                 dx, nparts = ops.conv3d_k4_mfma(g_out, L.wp_b, None, 3, L.bwd_pair, NONE, mask=mask, bias_part=base)
                 self._wg.add_job(base, bias_out, nparts, 8)
-                return dx, True
-            dx = ops.conv3d_k4_mfma(g_out, L.wp_b, None, 3, L.bwd_pair, NONE, addend=addend, mask=mask)
-            return dx if bias_out is None else (dx, False)
-        if bias_out is not None:
-            return ops.conv3d_gather(g_out, L.w_bwd, None, L.cin, L.k, 1, L.k - 1 - L.pad, tuple(x_in.shape[2:]),
-                                     addend=addend, mask=mask), False
-        return ops.conv3d_gather(g_out, L.w_bwd, None, L.cin, L.k, 1, L.k - 1 - L.pad, tuple(x_in.shape[2:]),
-                                 addend=addend, mask=mask)
+                slabs = True
+            else:
+                dx = ops.conv3d_k4_mfma(g_out, L.wp_b, None, 3, L.bwd_pair, NONE, addend=addend, mask=mask)
+        else:
+            dx = ops.conv3d_gather(g_out, L.w_bwd, None, L.cin, L.k, 1, L.k - 1 - L.pad, tuple(x_in.shape[2:]),
+                                   addend=addend, mask=mask)
+        if bias_out is not None and not slabs:
+            sums.append((dx, bias_out))
+        return dx
 
     def _dx_convT(self, L, g_out, x_in, mask=None, addend=None):
         if L.wp_gb is not None:
@@ -542,15 +588,13 @@ class TrainEngine:
             raise
 
     def _backward(self, a, gt, dist, gt16, gt8, n_pts, mode, block_ids, want_w, want_emb, fuse=None):
-        """Loss (NVFPCC.py:161-196) and its gradients.  Weight grads land in self.flat_g."""
-        net, Ls = self.net, self.layers
-        heads_deferred = a.get("p2") is None
-        fused_loss = self.heads3 and a["e"].shape[0] <= 32 and _NAIVE_OFF()
-        if heads_deferred and not (want_w and fused_loss):
+        """Loss (NVFPCC.py:161-196) and its gradients.  Weight grads land in self.flat_g.  The phases run in launch order;
+        what they return stays referenced here until the last launch has been enqueued (queued stages write it late)."""
+        deferred = a.get("p2") is None
+        plan = self._plan(a["e"].shape[0], want_w, want_emb, fuse is not None, defer_heads=deferred)
+        if deferred and plan.heads != "deferred":
             raise ValueError("forward(defer_heads=True) must be followed by a backward pass with weight gradients "
                              "(want_w=True): the heads' forward runs in that pass's loss launch")
-        self._bias_jobs = []
-        self._bias_cover = []     # bias gradients some launch's own final pass writes (no channel-sum job needed)
         if self._wg is None:
             # (wide decoder: 125 MiB of slabs at batch 16 -- a workspace that had to grow mid-step would be reallocated)
             self._wg = ops.WgradBatch(self.dev, nbytes=(256 if self.wide else 128) << 20, ctx=self.ctx)    # partial sums now, ONE reduction launch for all ten
@@ -558,12 +602,41 @@ class TrainEngine:
         nbits = torch.empty(7, device=self.dev)
         # the one-block final passes of the focal terms, the bias sums and the weight rate feed nothing inside the
         # step: queue them and run all three in one launch at the end
-        ctx = self.ctx if want_w else None
         if want_w:
             self.ctx.begin()
-        if not fused_loss:
-            dl2, dl0, dl1 = ops.focal_loss_multi([(a["p2"], gt, dist, 0.9, 1.0), (a["p0"], gt8, None, 0.85, 0.0),
-                                                  (a["p1"], gt16, None, 0.85, 0.0)], loss, ctx=ctx)
+        sums = []       # (tensor, bias gradient): the channel sums still to take, in the order the reduction gets them
+        t0, t1, g5, heads_job = self._bwd_loss_heads(plan, a, gt, dist, gt16, gt8, loss, sums)
+        g4, g3, g2, g1 = self._bwd_trunk(plan, a, t0, t1, g5, sums)
+        da0, dx0, stem_jobs = self._bwd_stem(plan, a, g1, sums)
+        de, tail = self._bwd_latent(plan, a, dx0, n_pts, mode, block_ids, sums)
+        sums_done = False
+        if plan.trunk5:
+            # conv2 / up2 / conv1 weight gradients, the longest launch of the step, go last of the big kernels: the
+            # queued latent tail (a 30 us chain of three dependent stages in ONE workgroup) runs as its first workgroup
+            # and is hidden behind them instead of being the critical path of the slab reduction; up1's and conv0's
+            # gradients (small VALU kernels) fill the slots that the short matrix-core workgroups leave
+            Ls = self.layers
+            sums_done = plan.sums_in_trunk5 and self._rate_ready
+            self._wg.add_trunk5([g5, a["y3"], g3, a["y1"], a["h0"]], [a["y4"], g4, a["y2"], g2, g1],
+                                [Ls["conv2"].gk, Ls["up2"].gk, Ls["conv1"].gk, Ls["up1"].gk, Ls["conv0"].gk],
+                                bias_outs=(Ls["conv2"].gb, Ls["conv1"].gb), heads=heads_job,
+                                sums=([t for t, _ in sums], [o for _, o in sums]) if sums_done else None,
+                                coef=((fuse["coef_dev"], self._coef_live)
+                                      if (fuse is not None and fuse.get("coef_dev") is not None) else None),
+                                stem_jobs=stem_jobs)
+        last = {"loss_terms": loss, "latent_bits": a["lbits"], "net_bits": nbits, "n_pts": n_pts}
+        self._bwd_finish(plan, sums, sums_done, last, fuse)
+        self.last = last
+        return de
+
+    def _bwd_loss_heads(self, plan, a, gt, dist, gt16, gt8, loss, sums):
+        """The three focal terms, their logit gradients and the heads' backward-data.  Returns (t0, t1, g5, heads_job): the
+        heads' share of dy1 / dy3, dy5, and the heads' weight-gradient job where add_trunk5 takes it (None: launched here)."""
+        Ls = self.layers
+        want_w = plan.want_w
+        ctx = self.ctx if want_w else None
+        hl = [Ls["conv0_cls"], Ls["conv1_cls"], Ls["conv2_cls"]]
+
         def step_metrics():
             # logging counts of NVFPCC.py:174-179, 190-221 (tp / ap / tn / an of the main output and of both heads at 0.5,
             # sse / denom at 0.6): one partial-sum launch, the final pass rides in the finals launch; nvf_step_tail turns
@@ -571,225 +644,197 @@ class TrainEngine:
             if self.epoch_acc is not None and want_w:
                 ops.metrics3([a["p2"], a["p0"], a["p1"]], [gt, gt8, gt16], [dist, None, None], 0.5, 0.6,
                              out=self.step_counts, ctx=ctx)
-        if not heads_deferred:
+        bias_outs = [L.gb for L in hl] if plan.head_bias_in_loss else None
+        terms = ([gt8, gt16, gt], [None, None, dist], [0.85, 0.85, 0.9], [0.0, 0.0, 1.0], [1, 2, 0], loss, [L.w_bwd for L in hl])
+        if plan.heads == "deferred":
+            # the heads' forward, the three focal terms, their logit gradients and the heads' backward-data: ONE launch
+            # (forward() left p0 / p1 / p2 to this call)
+            (a["p0"], a["p1"], a["p2"]), (dl0, dl1, dl2), (t0, t1, g5) = ops.heads3_fwd_loss_bwd_data(
+                [a["y1"], a["y3"], a["y5"]], [L.w_fwd for L in hl], [L.b_eff for L in hl], *terms, [None, None, a["y5"]],
+                self.ctx, bias_outs=bias_outs)
             step_metrics()
-        heads_job = None
-        if self.heads3:
-            hl = [Ls["conv0_cls"], Ls["conv1_cls"], Ls["conv2_cls"]]
-            head_bias_done = want_w and _HEAD_BIAS_IN_LOSS    # the heads' bias gradients: partials of the loss launch
-            if heads_deferred:
-                # the heads' forward, the three focal terms, their logit gradients and the heads' backward-data: ONE launch
-                # (forward() left p0 / p1 / p2 to this call)
-                (a["p0"], a["p1"], a["p2"]), (dl0, dl1, dl2), (t0, t1, g5) = ops.heads3_fwd_loss_bwd_data(
-                    [a["y1"], a["y3"], a["y5"]], [L.w_fwd for L in hl], [L.b_eff for L in hl], [gt8, gt16, gt],
-                    [None, None, dist], [0.85, 0.85, 0.9], [0.0, 0.0, 1.0], [1, 2, 0], loss, [L.w_bwd for L in hl],
-                    [None, None, a["y5"]], self.ctx, bias_outs=[L.gb for L in hl] if head_bias_done else None)
-                step_metrics()
-            elif fused_loss:    # the three focal terms, their logit gradients and the heads' backward-data: one launch
-                (dl0, dl1, dl2), (t0, t1, g5) = ops.heads3_loss_bwd_data(
-                    [a["p0"], a["p1"], a["p2"]], [gt8, gt16, gt], [None, None, dist], [0.85, 0.85, 0.9],
-                    [0.0, 0.0, 1.0], [1, 2, 0], loss, [L.w_bwd for L in hl], [L.cin for L in hl], [None, None, a["y5"]],
-                    ctx=ctx, bias_outs=[L.gb for L in hl] if head_bias_done else None)
-            else:
-                t0, t1, g5 = ops.heads3_bwd_data([dl0, dl1, dl2], [L.w_bwd for L in hl], [L.cin for L in hl],
-                                                 [None, None, a["y5"]])
-            if want_w:
-                heads_job = ([dl0, dl1, dl2], [a["y1"], a["y3"], a["y5"]], [L.gk for L in hl])
-                if not (self.narrow and _NAIVE_OFF() and _HEADS_IN_TRUNK5):   # else: workgroups of the five-gradient launch
-                    self._wg.add_heads3(*heads_job)
-                    heads_job = None
-                if fused_loss and head_bias_done:
-                    self._bias_cover += [L.gb for L in hl]
-                else:
-                    self._bias_jobs += [(dl2, hl[2].gb), (dl1, hl[1].gb), (dl0, hl[0].gb)]
+        elif plan.heads == "fused_loss":    # the three focal terms, their logit gradients and the heads' backward-data: one launch
+            step_metrics()
+            (dl0, dl1, dl2), (t0, t1, g5) = ops.heads3_loss_bwd_data(
+                [a["p0"], a["p1"], a["p2"]], *terms, [L.cin for L in hl], [None, None, a["y5"]], ctx=ctx, bias_outs=bias_outs)
         else:
+            dl2, dl0, dl1 = ops.focal_loss_multi([(a["p2"], gt, dist, 0.9, 1.0), (a["p0"], gt8, None, 0.85, 0.0),
+                                                  (a["p1"], gt16, None, 0.85, 0.0)], loss, ctx=ctx)
+            step_metrics()
+        if plan.heads == "layers":
             t1 = self._dx_conv(Ls["conv1_cls"], dl1, a["y3"])
             t0 = self._dx_conv(Ls["conv0_cls"], dl0, a["y1"])
             if want_w:
-                self._wgrad_conv(Ls["conv2_cls"], dl2, a["y5"])
-                self._wgrad_conv(Ls["conv1_cls"], dl1, a["y3"])
-                self._wgrad_conv(Ls["conv0_cls"], dl0, a["y1"])
+                self._wgrad_conv(Ls["conv2_cls"], dl2, a["y5"], sums)
+                self._wgrad_conv(Ls["conv1_cls"], dl1, a["y3"], sums)
+                self._wgrad_conv(Ls["conv0_cls"], dl0, a["y1"], sums)
             g5 = self._dx_conv(Ls["conv2_cls"], dl2, a["y5"], mask=a["y5"])
+            return t0, t1, g5, None
+        if plan.heads == "heads3":
+            t0, t1, g5 = ops.heads3_bwd_data([dl0, dl1, dl2], [L.w_bwd for L in hl], [L.cin for L in hl],
+                                             [None, None, a["y5"]])
+        heads_job = None
+        if want_w:
+            heads_job = ([dl0, dl1, dl2], [a["y1"], a["y3"], a["y5"]], [L.gk for L in hl])
+            if not plan.heads_in_trunk5:
+                self._wg.add_heads3(*heads_job)
+                heads_job = None
+            if not plan.head_bias_in_loss:
+                sums += [(dl2, hl[2].gb), (dl1, hl[1].gb), (dl0, hl[0].gb)]
+        return t0, t1, g5, heads_job
 
-        # the backward-data chain; each layer's weight gradient is issued as soon as its output gradient exists, except on
-        # the narrow decoder, whose five trunk weight gradients are one launch (add_trunk5, below)
-        wg3 = want_w and self.narrow and _NAIVE_OFF()
-        if wg3:     # up2's bias gradient = the channel sums of g4: left by the kernel that writes g4
-            g4, up2_bias_done = self._dx_conv(Ls["conv2"], g5, a["y4"], mask=a["y4"], bias_out=Ls["up2"].gb)
-            if not up2_bias_done:
-                self._bias_jobs += [(g4, Ls["up2"].gb)]
-        else:
-            if want_w:
-                self._wgrad_conv(Ls["conv2"], g5, a["y4"])
-            g4 = self._dx_conv(Ls["conv2"], g5, a["y4"], mask=a["y4"])
-            if want_w:
-                self._wgrad_convT(Ls["up2"], g4, a["y3"])
+    def _bwd_trunk(self, plan, a, t0, t1, g5, sums):
+        """The backward-data chain g4 .. g1; each layer's weight gradient is issued as soon as its output gradient exists,
+        except with plan.trunk5 (one launch, add_trunk5): up2's / up1's bias gradients = the channel sums of g4 / g2 then."""
+        Ls = self.layers
+        each = plan.want_w and not plan.trunk5
+        if each:
+            self._wgrad_conv(Ls["conv2"], g5, a["y4"], sums)
+        g4 = self._dx_conv(Ls["conv2"], g5, a["y4"], mask=a["y4"], bias_out=Ls["up2"].gb if plan.trunk5 else None, sums=sums)
+        if each:
+            self._wgrad_convT(Ls["up2"], g4, a["y3"], sums)
         g3 = self._dx_convT(Ls["up2"], g4, a["y3"], mask=a["y3"], addend=t1)
-        if wg3:
-            g2, up1_bias_done = self._dx_conv(Ls["conv1"], g3, a["y2"], mask=a["y2"], bias_out=Ls["up1"].gb)
-        else:
-            if want_w:
-                self._wgrad_conv(Ls["conv1"], g3, a["y2"])
-            g2 = self._dx_conv(Ls["conv1"], g3, a["y2"], mask=a["y2"])
-            if want_w:
-                self._wgrad_convT(Ls["up1"], g2, a["y1"])
+        if each:
+            self._wgrad_conv(Ls["conv1"], g3, a["y2"], sums)
+        g2 = self._dx_conv(Ls["conv1"], g3, a["y2"], mask=a["y2"], bias_out=Ls["up1"].gb if plan.trunk5 else None, sums=sums)
+        if each:
+            self._wgrad_convT(Ls["up1"], g2, a["y1"], sums)
         g1 = self._dx_convT(Ls["up1"], g2, a["y1"], mask=a["y1"], addend=t0)
-        stem_wg0 = want_w and self.fused_stem and not wg3   # conv0's weight gradient rides in the stem's backward
-        if wg3:                                      # up1 and conv0 weight gradients: with the other three, below
-            self._bias_jobs += ([] if up1_bias_done else [(g2, Ls["up1"].gb)]) + [(g1, Ls["conv0"].gb)]
-        elif stem_wg0:
-            self._bias_jobs.append((g1, Ls["conv0"].gb))
-        elif want_w:
-            self._wgrad_convT(Ls["conv0"], g1, a["h0"])
-        ig = net.reconstructor.activation
-        gview = (lambda n: self._g(n)) if want_w else (lambda n: None)
-        gamma_view = None if not want_w else self._g("reconstructor.activation.gamma").view(ig.gamma.shape)
-        self._stem_gdn_in_finals = bool(self.fused_stem and want_w)
-        tail = want_w and not want_emb and a["e"].shape[1] <= 8 and _NAIVE_OFF()
-        stem_coop = (_STEM_IN_TRUNK5 and tail and wg3 and self.fused_stem and a["e"].shape[0] <= 32
-                     and heads_job is not None)
-        stem_jobs = None
-        if stem_coop:
-            # no launch here: queued in the context, it runs inside add_trunk5's launch below (with the latent tail that
+        if plan.trunk5 or plan.conv0_wgrad_in_stem:      # conv0's weight gradient: in add_trunk5 / in the stem's backward
+            sums.append((g1, Ls["conv0"].gb))
+        elif plan.want_w:
+            self._wgrad_convT(Ls["conv0"], g1, a["h0"], sums)
+        return g4, g3, g2, g1
+
+    def _gdn_grads(self, prefix, mod, want_w):
+        """(d beta, d gamma) views of a GDN's parameter gradients in flat_g, or (None, None) without weight gradients."""
+        if not want_w:
+            return None, None
+        return self._g(prefix + ".beta"), self._g(prefix + ".gamma").view(mod.gamma.shape)
+
+    def _bwd_stem(self, plan, a, g1, sums):
+        """conv0^T -> IGDN' -> up0^T with up0's (and, plan.conv0_wgrad_in_stem, conv0's) gradients.  Returns (da0, dx0,
+        stem_jobs): the reduction jobs of a queued stem for add_trunk5, else None."""
+        Ls = self.layers
+        ig = self.net.reconstructor.activation
+        dbeta, dgamma = self._gdn_grads("reconstructor.activation", ig, plan.want_w)
+        if plan.stem_bwd == "queued":
+            # no launch here: queued in the context, it runs inside add_trunk5's launch (with the latent tail that
             # consumes dx0), which also takes its reduction jobs; up0's bias gradient comes from per-block channel sums
             # the stage leaves, not from da0
-            da0, dx0, stem_jobs = ops.stem_bwd_queue(g1, a["x0"], a["a0"], Ls["conv0"].w_bwd, Ls["up0"].w_bwd, ig.beta,
-                                                     ig.gamma, gview("reconstructor.activation.beta"), gamma_view,
-                                                     Ls["up0"].gk, Ls["up0"].gb, self.ctx)
-        elif self.fused_stem and want_w:        # its final launch is shared with the slab reduction / the final passes
+            return ops.stem_bwd_queue(g1, a["x0"], a["a0"], Ls["conv0"].w_bwd, Ls["up0"].w_bwd, ig.beta, ig.gamma, dbeta,
+                                      dgamma, Ls["up0"].gk, Ls["up0"].gb, self.ctx)
+        if plan.stem_bwd == "partial":          # its final launch is shared with the slab reduction / the final passes
+            wg0 = plan.conv0_wgrad_in_stem
             da0, dx0 = ops.stem_bwd_partial(g1, a["x0"], a["a0"], Ls["conv0"].w_bwd, Ls["up0"].w_bwd, ig.beta,
-                                            ig.gamma, gview("reconstructor.activation.beta"), gamma_view,
-                                            Ls["up0"].gk, self._wg, ctx=ctx, h0=a["h0"] if stem_wg0 else None,
-                                            dw_conv0=Ls["conv0"].gk if stem_wg0 else None)
-            self._bias_jobs.append((da0, Ls["up0"].gb))
-        elif self.fused_stem:
+                                            ig.gamma, dbeta, dgamma, Ls["up0"].gk, self._wg, ctx=self.ctx,
+                                            h0=a["h0"] if wg0 else None, dw_conv0=Ls["conv0"].gk if wg0 else None)
+            sums.append((da0, Ls["up0"].gb))
+        elif plan.stem_bwd == "plain":
             da0, dx0 = ops.stem_bwd(g1, a["x0"], a["a0"], Ls["conv0"].w_bwd, Ls["up0"].w_bwd, ig.beta, ig.gamma)
         else:
             dh0 = self._dx_convT(Ls["conv0"], g1, a["h0"])
-            da0, _, _ = ops.gdn_bwd(a["a0"], ig.beta, ig.gamma, dh0, True, gview("reconstructor.activation.beta"),
-                                    gamma_view)
-            if want_w:
-                self._wgrad_convT(Ls["up0"], da0, a["x0"])
+            da0, _, _ = ops.gdn_bwd(a["a0"], ig.beta, ig.gamma, dh0, True, dbeta, dgamma)
+            if plan.want_w:
+                self._wgrad_convT(Ls["up0"], da0, a["x0"], sums)
             dx0 = self._dx_convT(Ls["up0"], da0, a["x0"])
-        # latent rate (+ the decoder's gradient through the straight-through round)
-        ec = net.entropy_coder
-        sd = self._step_dev
+        return da0, dx0, None
+
+    def _bwd_latent(self, plan, a, dx0, n_pts, mode, block_ids, sums):
+        """Latent rate (+ the decoder's gradient through the straight-through round), the latent GDN and the 1x1x1 layer.
+        Returns (de, tail): the latent gradient (plan.want_emb), and the tensors of a queued tail."""
+        Ls = self.layers
+        want_w = plan.want_w
+        step, sd = self._noise()
         g_lat = self.lmbda * self.w1 / n_pts if self._g_lat_dev is None else 1.0
-        g2m = net.latent_gen.gdn_2
-        if tail:
+        g2m = self.net.latent_gen.gdn_2
+        dsigma, dmu = (self._g("entropy_coder.sigma"), self._g("entropy_coder.mu")) if want_w else (None, None)
+        dbeta, dgamma = self._gdn_grads("latent_gen.gdn_2", g2m, want_w)
+        if plan.tail_queued:
             # three dependent launches on [B, ch, 2^3] tensors -> one workgroup of the next weight-gradient launch
             # (or of the slab reduction); dlat / dh / dx0 stay referenced until that launch has been enqueued
             dlat, dh = torch.empty_like(a["lat"]), torch.empty_like(a["h"])
-            ops.latent_tail_queue(self.ctx, a["lat"], ec.sigma.reshape(-1), ec.mu.reshape(-1), mode, block_ids, dx0, dlat,
-                                  gview("entropy_coder.sigma"), gview("entropy_coder.mu"), self._g_lat_dev, g_lat,
-                                  self.seed, 0 if sd is not None else self.noise_step, sd, a["h"], g2m.beta, g2m.gamma,
-                                  dh, gview("latent_gen.gdn_2.beta"),
-                                  self._g("latent_gen.gdn_2.gamma").view(g2m.gamma.shape), a["e"], Ls["latent"].gk,
-                                  Ls["latent"].gb)
-            de = None
-        else:
-            _, _, dlat, _, _ = ops.latent_rate(a["lat"], ec.sigma.reshape(-1), ec.mu.reshape(-1), mode,
-                                               block_ids=block_ids, want_grad=True, g_host=g_lat,
-                                               g_dev=self._g_lat_dev, seed=self.seed,
-                                               step=0 if sd is not None else self.noise_step, step_dev=sd,
-                                               dx_addend=dx0, dsigma_out=gview("entropy_coder.sigma"),
-                                               dmu_out=gview("entropy_coder.mu"))
-            dh, _, _ = ops.gdn_bwd(a["h"], g2m.beta, g2m.gamma, dlat, False, gview("latent_gen.gdn_2.beta"),
-                                   None if not want_w else self._g("latent_gen.gdn_2.gamma").view(g2m.gamma.shape))
-            if want_w:
-                self._wgrad_conv(Ls["latent"], dh, a["e"])
-            de = self._dx_conv(Ls["latent"], dh, a["e"]) if want_emb else None
-        if wg3:
-            # conv2 / up2 / conv1 weight gradients, the longest launch of the step, go last of the big kernels: the
-            # queued latent tail (a 30 us chain of three dependent stages in ONE workgroup) runs as its first workgroup
-            # and is hidden behind them instead of being the critical path of the slab reduction; up1's and conv0's
-            # gradients (small VALU kernels) fill the slots that the short matrix-core workgroups leave
-            self._wg.add_trunk5([g5, a["y3"], g3, a["y1"], a["h0"]], [a["y4"], g4, a["y2"], g2, g1],
-                                [Ls["conv2"].gk, Ls["up2"].gk, Ls["conv1"].gk, Ls["up1"].gk, Ls["conv0"].gk],
-                                bias_outs=(Ls["conv2"].gb, Ls["conv1"].gb), heads=heads_job,
-                                sums=(([t for t, _ in self._bias_jobs], [o for _, o in self._bias_jobs])
-                                      if (heads_job is not None and self._rate_ready and _SUMS_IN_TRUNK5) else None),
-                                coef=((fuse["coef_dev"], self._coef_live)
-                                      if (fuse is not None and fuse.get("coef_dev") is not None) else None),
-                                stem_jobs=stem_jobs)
-        # weight rate: bits of the 7 quantised kernels and, for the decoder update, their gradients (added to the
-        # weight gradients); every bias gradient in one reduction
-        lm = net.reconstructor.likelihood_model
-        g_net = self.lmbda * self.w2 / self.n_points_total
-        gs, gm = self._g("reconstructor.likelihood_model.sigma"), self._g("reconstructor.likelihood_model.mu")
-        kernels = [Ls[n].mod.kernel for n in TRUNK]
-        rate_head, self._rate_ready = self._rate_ready and want_w, False
-        fused = None
-        if want_w:     # slab reduction of every weight gradient + all bias sums
-            addends = None
-            if rate_head:
-                # the weight-rate gradient was computed by the step head: the reduction adds it while it writes the
-                # gradients (every trunk kernel must come out of that launch; otherwise the stand-alone pass)
-                job, addends = self._rate_job()[:2]
-                live = {j[1] for j in self._wg.jobs if j[2] > 0}
-                if not all(Ls[n].gk.data_ptr() in live for n in TRUNK) or len(self._wg.jobs) > 16:
-                    rate_head, addends = False, None
-            if fuse is not None and rate_head:
-                fused = self._fused_tail(fuse, loss, a["lbits"], nbits, gs, gm)
-            sums_done = wg3 and getattr(self._wg, "sums_done", False)    # the partial bias sums rode in add_trunk5
-            one_launch = fused is not None and sums_done and rate_head
-            if one_launch:      # nothing the final passes read is written by the slab reduction: ONE launch for both
-                ops.weight_rate_final(job, nbits, gs, gm, ctx=ctx)
-                adam = fused[1]
-                if fuse.get("coef_dev") is not None:     # the copy add_trunk5 staged: not the step buffer's words
-                    adam.coef_dev = self._coef_live.data_ptr()
-                self._wg.finish_and_flush_tail(addends, adam, fused[0], fused[2])
-            elif sums_done and rate_head and fused is None:
-                # data parallelism (the all-reduce and the step tail follow): the same pairing without the optimiser
-                one_launch = True
-                ops.weight_rate_final(job, nbits, gs, gm, ctx=ctx)
-                self._wg.finish_and_flush(addends)
-            else:
-                if sums_done:
-                    self._wg.finish_with_sums([], [], addends=addends, adam=None if fused is None else fused[1])
-                else:
-                    self._wg.finish_with_sums([t for t, _ in self._bias_jobs], [o for _, o in self._bias_jobs],
-                                              addends=addends, adam=None if fused is None else fused[1])
-                if rate_head:
-                    ops.weight_rate_final(job, nbits, gs, gm, ctx=ctx)
-                else:
-                    ops.weight_rate_batch(kernels, [Ls[n].gk for n in TRUNK], lm.sigma, lm.mu, nbits, gs, gm,
-                                          g_host=g_net * self.rate_grad_scale, ctx=ctx)
-            if not one_launch:
-                if fused is not None:
-                    self.ctx.flush_tail(fused[0], fused[2])
-                else:
-                    self.ctx.flush()
-        else:
-            ops.weight_rate_batch(kernels, None, lm.sigma, lm.mu, nbits)
-        self.tail_done = fused is not None
-        self.last = {"loss_terms": loss, "latent_bits": a["lbits"], "net_bits": nbits, "n_pts": n_pts}
-        return de
+            ops.latent_tail_queue(self.ctx, a["lat"], *self._ec(), mode, block_ids, dx0, dlat, dsigma, dmu,
+                                  self._g_lat_dev, g_lat, self.seed, step, sd, a["h"], g2m.beta, g2m.gamma, dh, dbeta,
+                                  dgamma, a["e"], Ls["latent"].gk, Ls["latent"].gb)
+            return None, (dlat, dh)
+        _, _, dlat, _, _ = ops.latent_rate(a["lat"], *self._ec(), mode, block_ids=block_ids, want_grad=True, g_host=g_lat,
+                                           g_dev=self._g_lat_dev, seed=self.seed, step=step, step_dev=sd,
+                                           dx_addend=dx0, dsigma_out=dsigma, dmu_out=dmu)
+        dh, _, _ = ops.gdn_bwd(a["h"], g2m.beta, g2m.gamma, dlat, False, dbeta, dgamma)
+        if want_w:
+            self._wgrad_conv(Ls["latent"], dh, a["e"], sums)
+        return (self._dx_conv(Ls["latent"], dh, a["e"]) if plan.want_emb else None), None
 
-    def _fused_tail(self, tail, loss, lbits, nbits, gs, gm):
+    def _bwd_finish(self, plan, sums, sums_done, last, fuse):
+        """Weight rate (bits of the 7 quantised kernels and, for the decoder update, their gradients, added to the weight
+        gradients), slab reduction, bias sums, final passes and -- single GPU -- the optimiser.  ``sums_done``: the partial
+        bias sums rode in add_trunk5."""
+        Ls, nbits = self.layers, last["net_bits"]
+        lm = self.net.reconstructor.likelihood_model
+        kernels = [Ls[n].mod.kernel for n in TRUNK]
+        rate_head, self._rate_ready = self._rate_ready and plan.want_w, False
+        self.tail_done = False
+        if not plan.want_w:
+            ops.weight_rate_batch(kernels, None, lm.sigma, lm.mu, nbits)
+            return
+        gs, gm = self._g("reconstructor.likelihood_model.sigma"), self._g("reconstructor.likelihood_model.mu")
+        addends = fused = None
+        if rate_head:
+            # the weight-rate gradient was computed by the step head: the reduction adds it while it writes the
+            # gradients (every trunk kernel must come out of that launch; otherwise the stand-alone pass)
+            job, addends = self._rate_job()[:2]
+            live = {out for out, _ in self._wg.live_outputs()}
+            if not all(Ls[n].gk.data_ptr() in live for n in TRUNK) or len(self._wg.jobs) > 16:
+                rate_head, addends = False, None
+        if plan.fused_optimiser and rate_head:
+            fused = tail, adam, ranges = self._fused_tail(plan, fuse, sums, last, gs, gm)
+            self.tail_done = True
+        # nothing the final passes read is written by the slab reduction: ONE launch for both where the bias partials exist
+        one_launch = sums_done and rate_head
+        if not one_launch:
+            todo = [] if sums_done else sums
+            self._wg.finish_with_sums([t for t, _ in todo], [o for _, o in todo], addends=addends,
+                                      adam=adam if fused else None)
+        if rate_head:
+            ops.weight_rate_final(job, nbits, gs, gm, ctx=self.ctx)
+        else:
+            g_net = self.lmbda * self.w2 / self.n_points_total
+            ops.weight_rate_batch(kernels, [Ls[n].gk for n in TRUNK], lm.sigma, lm.mu, nbits, gs, gm,
+                                  g_host=g_net * self.rate_grad_scale, ctx=self.ctx)
+        if one_launch and fused:
+            if fuse.get("coef_dev") is not None:     # the copy add_trunk5 staged: not the step buffer's words
+                adam.coef_dev = self._coef_live.data_ptr()
+            self._wg.finish_and_flush_tail(addends, adam, tail, ranges)
+        elif one_launch:    # data parallelism (the all-reduce and the step tail follow): the same pairing without the optimiser
+            self._wg.finish_and_flush(addends)
+        elif fused:
+            self.ctx.flush_tail(tail, ranges)
+        else:
+            self.ctx.flush()
+
+    def _tail_kw(self, last):
+        """The step_tail arguments every form of the optimiser tail shares: the optimiser state, the statistics inputs of
+        the step ``last`` (only while epoch statistics are on), the accumulators and the arrival counter."""
+        stats = self.epoch_acc is not None
+        return dict(p=self.flat_p, g=self.flat_g, m=self.flat_m, v=self.flat_v,
+                    loss_terms=last["loss_terms"] if stats else None, lbits=last["latent_bits"] if stats else None,
+                    nbits=last["net_bits"] if stats else None, nbits_scale=1.0 / self.n_points_total,
+                    counts=self.step_counts if stats else None, acc=self.epoch_acc, done=self._tail_done)
+
+    def _fused_tail(self, plan, tail, sums, last, gs, gm):
         """(NvfStepTail, NvfAdamFuse, uncovered ranges) for a step whose optimiser rides in the slab reduction (weight
         gradients) and in the finals launch (everything those final passes write + the ranges): single-GPU steps only.
         ``tail``: dict(coef_dev= / coef_host=, inv_npts_dev= / inv_npts_host=, sched=)."""
-        stats = self.epoch_acc is not None
-        t = ops.step_tail_args(self.flat_p, self.flat_g, self.flat_m, self.flat_v, tail.get("coef_dev"),
-                               tail.get("coef_host", (0.0, 0.0)), loss_terms=loss if stats else None,
-                               lbits=lbits if stats else None, nbits=nbits if stats else None,
-                               inv_npts_dev=tail.get("inv_npts_dev"), inv_npts_host=tail.get("inv_npts_host", 1.0),
-                               nbits_scale=1.0 / self.n_points_total, counts=self.step_counts if stats else None,
-                               acc=self.epoch_acc, done=self._tail_done, sched=tail.get("sched"))
-        base, esz = self.flat_g.data_ptr(), 4
-        cover = []
-        for j in self._wg.jobs:
-            if j[2] > 0:
-                cover.append(((j[1] - base) // esz, (j[1] - base) // esz + j[3]))
-        for o in [o for _, o in self._bias_jobs] + self._bias_cover:
-            cover.append(((o.data_ptr() - base) // esz, (o.data_ptr() - base) // esz + o.numel()))
-        for g1 in (gs, gm):
-            cover.append(((g1.data_ptr() - base) // esz, (g1.data_ptr() - base) // esz + g1.numel()))
-        if self._stem_gdn_in_finals:
-            for name in ("reconstructor.activation.beta", "reconstructor.activation.gamma"):
-                off, cnt = self.slices[name]
-                cover.append((off, off + cnt))
+        t = ops.step_tail_args(**tail, **self._tail_kw(last))
+        outs = [o for _, o in sums] + [gs, gm]
+        if plan.head_bias_in_loss:      # written by the loss launch's own final pass (no channel-sum job)
+            outs += [self.layers[n].gb for n in ("conv0_cls", "conv1_cls", "conv2_cls")]
+        if plan.stem_bwd in ("queued", "partial"):      # the stem's IGDN gradients: a deferred final pass
+            outs += [self._g("reconstructor.activation.beta"), self._g("reconstructor.activation.gamma")]
+        base = self.flat_g.data_ptr()
+        cover = [((ptr - base) // 4, (ptr - base) // 4 + cnt)
+                 for ptr, cnt in self._wg.live_outputs() + [(o.data_ptr(), o.numel()) for o in outs]]
         n = self.flat_g.numel()
         key = tuple(sorted(c for c in cover if 0 <= c[0] < n))
         ranges = self._tail_ranges.get(key)
@@ -860,14 +905,8 @@ class TrainEngine:
         if self.grad_hook is not None:
             self.grad_hook(self.flat_gx)
         self.opt_step += 1
-        t = self.last
-        stats = self.epoch_acc is not None
-        ops.step_tail(self.flat_p, self.flat_g, self.flat_m, self.flat_v, None,
-                      ops.adam_coefficients(self.lr, self.opt_step),
-                      loss_terms=t["loss_terms"] if stats else None, lbits=t["latent_bits"] if stats else None,
-                      nbits=t["net_bits"] if stats else None, inv_npts_host=1.0 / n_pts,
-                      nbits_scale=1.0 / self.n_points_total, counts=self.step_counts if stats else None,
-                      acc=self.epoch_acc, done=self._tail_done)
+        ops.step_tail(coef_host=ops.adam_coefficients(self.lr, self.opt_step), inv_npts_host=1.0 / n_pts,
+                      **self._tail_kw(self.last))
 
     def _idle_backward(self):
         """A rank whose share of a short last mini-batch is empty (NVFPCC.py:149 with 917 mod 16 = 5 blocks on 8
@@ -1087,13 +1126,8 @@ class GraphedTrainStep:
         eng = self.eng
         if eng.grad_hook is not None:
             eng.grad_hook(eng.flat_gx)
-        t = self.last
-        stats = eng.epoch_acc is not None
-        ops.step_tail(eng.flat_p, eng.flat_g, eng.flat_m, eng.flat_v, self.coef,
-                      loss_terms=t["loss_terms"] if stats else None, lbits=t["latent_bits"] if stats else None,
-                      nbits=t["net_bits"] if stats else None, inv_npts_dev=self.inv_npts,
-                      nbits_scale=1.0 / eng.n_points_total, counts=eng.step_counts if stats else None,
-                      acc=eng.epoch_acc, done=eng._tail_done, sched=(self.buf, self.rows, self.cursor, self.nw))
+        ops.step_tail(coef_dev=self.coef, inv_npts_dev=self.inv_npts, sched=(self.buf, self.rows, self.cursor, self.nw),
+                      **eng._tail_kw(self.last))
 
     def stage_schedule(self, steps):
         """Host half of load_schedule: validates `steps` and fills the rows (block ids, noise steps, rate and Adam

@@ -690,6 +690,11 @@ class WgradBatch:
         self.ctx = ctx          # StepCtx: a queued latent tail rides in add_mfma3 / add_trunk5 / finish_with_sums
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
         self._retired = []      # outgrown buffers stay alive: kernels on another stream may still read them
+        self.sums_done = False  # the last add_trunk5 launch carried the partial bias sums (sums=)
+
+    def live_outputs(self):
+        """(output address, floats) of every pending reduction that has slabs to add."""
+        return [(out, n) for _, out, nslab, n in self.jobs if nslab > 0]
 
     def _alloc(self, sizes):
         """Base addresses of slab regions of ``sizes`` bytes (each rounded up to 256).  A workspace too small for all of
@@ -757,34 +762,28 @@ class WgradBatch:
               "nvf_wgrad_partial")
         self.jobs.append((base, out.data_ptr(), nslab.value, a * b * k ** 3))
 
-    def add_mfma3(self, ps, qs, outs):
-        """conv2 / up2 / conv1 weight gradients of the narrow trunk: one partial-sum launch, three reduction jobs."""
+    def _grouped(self, what, launch, outs, jt, max_slabs):
+        """One partial-sum launch for len(jt) gradients of jt[h] floats, ``launch(slab bases, slab counts)``, and a
+        reduction job for each."""
         import ctypes
-        _f32(*ps, *qs, *outs)
-        B = ps[0].shape[0]
-        jt = (4096, 8000, 4096)
-        bases = self._alloc([512 * j * 4 for j in jt])
-        nsl = (ctypes.c_int * 3)()
-        check(lib().nvf_wgrad_mfma3_partial(_parr(ps), _parr(qs), (ctypes.c_void_p * 3)(*bases), B, nsl, _ctx(self.ctx),
-                                            _stream()), "nvf_wgrad_mfma3_partial")
-        self._check_slabs("nvf_wgrad_mfma3_partial", nsl, (512,) * 3)
-        for h in range(3):
-            self.jobs.append((bases[h], outs[h].data_ptr(), nsl[h], jt[h]))
-
-    def _grouped(self, fn, what, ps, qs, outs, jt, max_slabs):
-        import ctypes
-        _f32(*ps, *qs, *outs)
         n = len(jt)
         bases = self._alloc([max_slabs * j * 4 for j in jt])
         nsl = (ctypes.c_int * n)()
-        check(fn(_parr(ps), _parr(qs), (ctypes.c_void_p * n)(*bases), ps[0].shape[0], nsl, _stream()), what)
+        check(launch((ctypes.c_void_p * n)(*bases), nsl), what)
         self._check_slabs(what, nsl, (max_slabs,) * n)
-        for h in range(n):
-            self.jobs.append((bases[h], outs[h].data_ptr(), nsl[h], jt[h]))
+        self.jobs += [(bases[h], outs[h].data_ptr(), nsl[h], jt[h]) for h in range(n)]
+
+    def add_mfma3(self, ps, qs, outs):
+        """conv2 / up2 / conv1 weight gradients of the narrow trunk: one partial-sum launch, three reduction jobs."""
+        _f32(*ps, *qs, *outs)
+        self._grouped("nvf_wgrad_mfma3_partial", lambda bases, nsl: lib().nvf_wgrad_mfma3_partial(
+            _parr(ps), _parr(qs), bases, ps[0].shape[0], nsl, _ctx(self.ctx), _stream()), outs, (4096, 8000, 4096), 512)
 
     def add_up1_conv0(self, ps, qs, outs):
         """up1 / conv0 weight gradients of the narrow trunk: one partial-sum launch, two reduction jobs."""
-        self._grouped(lib().nvf_wgrad_up1_conv0_partial, "nvf_wgrad_up1_conv0_partial", ps, qs, outs, (16000, 16000), 512)
+        _f32(*ps, *qs, *outs)
+        self._grouped("nvf_wgrad_up1_conv0_partial", lambda bases, nsl: lib().nvf_wgrad_up1_conv0_partial(
+            _parr(ps), _parr(qs), bases, ps[0].shape[0], nsl, _stream()), outs, (16000, 16000), 512)
 
     def add_trunk5(self, ps, qs, outs, bias_outs=None, heads=None, sums=None, coef=None, stem_jobs=None):
         """conv2 / up2 / conv1 / up1 / conv0 weight gradients of the narrow trunk: one partial-sum launch (which also
@@ -849,18 +848,11 @@ class WgradBatch:
 
     def add_heads3(self, dls, xs, outs, max_slabs=_HEADS_SLABS):
         """Weight gradients of the three classifier heads: one partial-sum launch, three reduction jobs."""
-        import ctypes
         _f32(*dls, *xs, *outs)
-        B = xs[0].shape[0]
         cs = [x.shape[1] for x in xs]
-        bases = self._alloc([max_slabs * c * 27 * 4 for c in cs])
-        nsl = (ctypes.c_int * 3)()
-        check(lib().nvf_heads3_wgrad_partial(_parr(dls), _parr(xs), (ctypes.c_void_p * 3)(*bases), _iarr(cs),
-                                             _iarr([x.shape[-1] for x in xs]), B, max_slabs, nsl, _stream()),
-              "nvf_heads3_wgrad_partial")
-        self._check_slabs("nvf_heads3_wgrad_partial", nsl, (max_slabs,) * 3)
-        for h in range(3):
-            self.jobs.append((bases[h], outs[h].data_ptr(), nsl[h], cs[h] * 27))
+        self._grouped("nvf_heads3_wgrad_partial", lambda bases, nsl: lib().nvf_heads3_wgrad_partial(
+            _parr(dls), _parr(xs), bases, _iarr(cs), _iarr([x.shape[-1] for x in xs]), xs[0].shape[0], max_slabs, nsl,
+            _stream()), outs, [c * 27 for c in cs], max_slabs)
 
     def finish_with_sums(self, tensors, outs, addends=None, adam=None):
         """finish() and multi_channel_sum(tensors, outs) with the reduction and the partial bias sums in one launch.

@@ -950,3 +950,38 @@ def test_stem_jobs_survive_a_growing_five_gradient_launch(gpu):
         for name, (o, m) in eng.slices.items():
             assert torch.isfinite(g_small[o:o + m]).all(), (step, name)
             close(g_small[o:o + m], g_ref[o:o + m], tol=2e-6)
+
+
+def test_the_narrow_training_step_is_these_library_calls(gpu, monkeypatch):
+    """The default single-GPU training step of the narrow decoder at batch 16, as the list of C-ABI calls it makes (recorded
+    at the commit before the step's launches were planned in one place, engine.plan_step): 12 launches (README) and 8 calls
+    that launch nothing -- workspace sizes, the Adam coefficients, the start of the deferred final passes, the weight rate's
+    final pass queued among them, and the stem's backward and the latent tail queued into the five-gradient launch."""
+    from nvfpcc_amd import _lib as L
+    net, eng, gt, dist, emb = make("S", gpu, nblk=40)
+    real, calls = L.lib(), []
+
+    class Recorder:
+        def __getattr__(self, name):
+            if name.startswith("nvf_"):
+                calls.append(name)
+            return getattr(real, name)
+    monkeypatch.setattr(L, "_lib", Recorder())
+    eng.train_step(np.arange(16), 1)
+    monkeypatch.setattr(L, "_lib", real)
+    torch.cuda.synchronize()
+    no_launch = ["nvf_adam_coefficients", "nvf_finals_begin", "nvf_reduce_workspace", "nvf_stem_bwd_workspace_for",
+                 "nvf_stem_bwd_queue", "nvf_latent_tail_queue", "nvf_multi_channel_sum_workspace",
+                 "nvf_weight_rate_batch_final"]
+    assert calls == [
+        "nvf_step_head_stem",
+        "nvf_convT3d_k5s2_mfma", "nvf_conv3d_k4_mfma", "nvf_convT3d_k5s2_mfma", "nvf_conv3d_k4_wino_fwd",
+        "nvf_adam_coefficients", "nvf_finals_begin", "nvf_reduce_workspace",
+        "nvf_heads3_fwd_loss_bwd_data",
+        "nvf_conv3d_k4_wino_bwd", "nvf_conv3d_s2k5_mfma", "nvf_conv3d_k4_wino_bwd", "nvf_conv3d_s2k5_mfma",
+        "nvf_stem_bwd_workspace_for", "nvf_stem_bwd_queue", "nvf_latent_tail_queue", "nvf_multi_channel_sum_workspace",
+        "nvf_wgrad_trunk5_heads_sums_partial",
+        "nvf_weight_rate_batch_final",
+        "nvf_wgrad_reduce_finals_tail"]
+    assert len([c for c in calls if c not in no_launch]) == 12
+    assert eng.tail_done and eng.opt_step == 1
