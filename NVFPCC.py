@@ -12,7 +12,10 @@ engine (nvfpcc_amd/engine.py) instead of a DataLoader + autograd loop.
     python NVFPCC.py encode longdress_vox10_1300.ply ... --thh_mode count     # threshold chosen here, carried in pack.pk
     python NVFPCC.py decode pack.pk --batchsize 1 --chanstr 8,16,8,8 --ch 3   # no --thh needed then
 
-Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --thh_mode (count | block-count | d1:
+    python NVFPCC.py train cloud.ply --from_ply ...                            # no get_octree / util_get_grids run, no .npy
+    python NVFPCC.py encode cloud.ply --from_ply --pack_octree ...             # leaves travel as octree bytes; decode needs no --N
+
+Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --pack_octree, --thh_mode (count | block-count | d1:
 nvfpcc_amd/thh_select.py picks the occupancy threshold at encode time and a `thh_pack` key carries it); multi-GPU training when launched
 through torch.distributed.run (one process per GPU, leaf blocks sharded, one RCCL all-reduce per step).
 Headless: no GUI window, no IPython shell.
@@ -69,15 +72,27 @@ def _psnr1(sse, denom):
         return mse1, 20 * np.log10(1023 / np.sqrt(mse1 / 3))
 
 
+def _load_data(args, dev, shuffle=True):
+    """The dataset of `args.input`: the three `*_l5_*.npy` files next to it, or -- with --from_ply -- the cloud itself,
+    pre-processed on the device (nothing is read from or written to disk besides the PLY).  -> (dataset, the
+    DevicePreprocess or None)."""
+    from nvfpcc_amd.dataloader import LoadedVoxelDataset
+    if getattr(args, 'from_ply', False):
+        from nvfpcc_amd import preprocess as pp
+        pre = pp.preprocess_device(pp.read_ply_xyz(args.input), dev)
+        return LoadedVoxelDataset.from_device(pre, shuffle=shuffle), pre
+    fid = args.input[:-4]
+    return LoadedVoxelDataset(f'{fid}_l5_origins.npy', f'{fid}_l5_gt_grid.npy', f'{fid}_l5_dist.npy',
+                              shuffle=shuffle), None
+
+
 def train(args):
     from nvfpcc_amd import dist as nd, ops
-    from nvfpcc_amd.dataloader import LoadedVoxelDataset
     from nvfpcc_amd.engine import TrainEngine, EpochDriver
     dev, rank, world = _device(args)
     say = print if rank == 0 else (lambda *a, **k: None)
     say(f'Rate loss = {args.w1} * b1 + b2 + {args.w2} * b3')
-    fid = args.input[:-4]
-    data = LoadedVoxelDataset(f'{fid}_l5_origins.npy', f'{fid}_l5_gt_grid.npy', f'{fid}_l5_dist.npy')
+    data, _ = _load_data(args, dev)
     say('Using lambda: ', args.lmbda)
     net = _build_net(args, dev)
     gt, dist = data.to_device(dev)
@@ -163,11 +178,9 @@ TEST_LINE = ('[Epoch %04d TEST %.1f seconds] Loss: %.4e PosiPenal: %.4f PosiGain
 def encode(args):
     """Pack everything the decoder needs (NVFPCC.py:395-554)."""
     from nvfpcc_amd import ops, weight_codec, latent_codec
-    from nvfpcc_amd.dataloader import LoadedVoxelDataset
     from nvfpcc_amd.recon import reconstruct_points, write_ply_ascii
     dev, rank, world = _device(args)
-    fid = args.input[:-4]
-    data = LoadedVoxelDataset(f'{fid}_l5_origins.npy', f'{fid}_l5_gt_grid.npy', f'{fid}_l5_dist.npy', shuffle=False)
+    data, pre = _load_data(args, dev, shuffle=False)
     net = _build_net(args, dev)
     net_weight_pack = weight_codec.enc_dec_from_file(args.load_weights, qp=int(args.qp))
     net_bits = len(net_weight_pack['bit_stream']) * 8
@@ -179,7 +192,12 @@ def encode(args):
         info = net.get_latent_code(emb)
     print('Estimated bit rate: ', info['latent_likelihood'].sum())
     latent_pack = latent_codec.arithmetic_enc(info['quantized_latent'], info['sigma'], info['mu'])
-    total_pack = {'net_weight_pack': net_weight_pack, 'origins': np_origins, 'latent_pack': latent_pack}
+    if getattr(args, 'pack_octree', False):                  # the partition as octree bytes instead of 6 raw bytes per leaf
+        from nvfpcc_amd import preprocess as pp
+        octree_pack = pre.octree_pack() if pre is not None else pp.octree_pack_from_origins(np_origins)
+        total_pack = {'net_weight_pack': net_weight_pack, 'latent_pack': latent_pack, 'octree_pack': octree_pack}
+    else:
+        total_pack = {'net_weight_pack': net_weight_pack, 'origins': np_origins, 'latent_pack': latent_pack}
     batch = max(int(args.batchsize), 1)
     thh, sel = args.thh, None
     if args.thh_mode not in (None, 'fixed'):
@@ -202,7 +220,7 @@ def encode(args):
     else:
         m = ops.metrics(out, gt, dist, thh, thh).cpu().numpy()
     latent_bits = len(latent_pack['latent_byte_stream']) * 8
-    side_bits = 0 if sel is None else 8 * len(sel['pack'])
+    side_bits = (0 if sel is None else 8 * len(sel['pack'])) + 8 * len(total_pack.get('octree_pack', b''))
     if sel is not None:
         print(sel['line'])
     print('[Latent code] Gross bpp: %.4f' % ((latent_bits + net_bits + side_bits) / data.N))
@@ -256,7 +274,13 @@ def decode(args):
     net.load_state_dict(nd_, strict=False)
     net = net.to(dev)
     latents = latent_codec.arithmetic_dec(total_pack['latent_pack']).to(dev)
-    n = int(args.N)
+    if 'octree_pack' in total_pack:         # the leaves and their count come from the pack, not from --N
+        from nvfpcc_amd.preprocess import read_octree_pack
+        origins = read_octree_pack(total_pack['octree_pack']).astype(np.int16)
+        n = origins.shape[0]
+    else:
+        n = int(args.N)
+        origins = total_pack['origins'][:n]
     print('Start to reconstruct')
     thh, block_counts, used = args.thh, None, []
     side = total_pack.get('thh_pack')
@@ -271,7 +295,7 @@ def decode(args):
         else:
             thh = value
             print(ts.threshold_line(mode, t=thh))
-    pts, counts = reconstruct_points(net, latents[:n].contiguous(), total_pack['origins'][:n], thh,
+    pts, counts = reconstruct_points(net, latents[:n].contiguous(), origins, thh,
                                      batch=max(int(args.batchsize), 1), block_counts=block_counts, thh_out=used)
     if block_counts is not None:
         print(ts.threshold_line('block-count', block_counts=block_counts, thresholds=torch.cat(used).cpu().numpy()))
@@ -329,6 +353,13 @@ def build_parser():
                         'count = keep as many voxels as the input has points; block-count = the same per block; '
                         'd1 = the candidate with the best symmetric D1 PSNR.  The choice travels in the pack '
                         '(thh_pack) and decode uses it; decode --thh_mode fixed ignores it and uses --thh.')
+    # opt-in switches: absent from the namespace unless given, so a command line without them parses as it always did
+    p.add_argument('--from_ply', action='store_true', default=argparse.SUPPRESS,
+                   help='train / encode: the input is the cloud itself (ASCII PLY, 10-bit coordinates); it is '
+                        'pre-processed on the device and no *_l5_*.npy file is read or written.')
+    p.add_argument('--pack_octree', action='store_true', default=argparse.SUPPRESS,
+                   help='encode: carry the leaf cubes in the pack as octree occupancy bytes (octree_pack, counted in '
+                        'Gross bpp) instead of raw origins; decode then needs no --N.')
     p.add_argument('--ref_ply', default=None,
                    help='Original cloud (ASCII PLY): encode / decode also print its D1 / D2 geometry PSNR.')
     return p

@@ -790,6 +790,38 @@ int nvf_threshold_count_v(const float* p, const float* thh, int32_t* counts, int
 int nvf_threshold_compact_v(const float* p, const float* thh, const int32_t* offsets, const int32_t* origins,
                             int32_t* coords, int batch, int dim, void* stream);
 
+/* ---- pre-processing on the device (nvfpcc_amd/preprocess.py: preprocess_device, csrc/pp_device.hip) ----------------
+ * From int32 [P,3] points with 10-bit coordinates to everything nvf_nearest_dist2 and the trainer take, without a host
+ * pass.  A CELL CODE is the 15-bit Morton code of a level-5 cell (x >> 5, y >> 5, z >> 5), x in the lowest bit of each
+ * level: the reference's traversal order of the leaves is ascending cell code.  Every result is an OR or an integer
+ * count, so repeated calls give the same bits.  Call order: keys, (sort the keys ascending), tree, blocks, neighbours.
+ * nvf_pp_keys: clears bitmap6 and meta, then per point keys[i] = cell code << 15 | (x & 31) << 10 | (y & 31) << 5 |
+ *   (z & 31), the point's bit in bitmap6 (uint32 [8192], 16-byte aligned: bit = cell code << 3 | child index of the
+ *   16^3 cell, so byte c holds the eight children of cell c), and meta[1] += 1 for a point with a coordinate outside
+ *   [0, 1024) (its key is 0x7fffffff; the caller raises on a non-zero count).
+ * nvf_pp_tree: origins int32 [N,3] (room for 32768 rows) in traversal order; rank_tab uint32 [2048] = the level-5
+ *   bitmap and the number of set bits before each of its words (block id of a cell = a prefix popcount);
+ *   octree_bytes uint8 [NVF_PP_OCT_BYTES]: the child-occupancy bytes of level L (bit i = child i), breadth first,
+ *   start at byte (8^L - 1) / 7; nb_off int32 [N+1] (room for 32769) the row offsets of the candidate lists.
+ *   meta int32 [NVF_PP_META_INTS]: [0] N, [1] rejected points, [2..7] bytes of level 0..5, [8] nb_off[N], [9] occupied
+ *   voxels (distinct points; written by nvf_pp_blocks).
+ * nvf_pp_blocks: sorted_keys -> pts int32 [P,3] sorted by block and blk_off int32 [N+1] (room for 32769); N is read
+ *   from meta on the device.
+ * nvf_pp_neighbours: nb_idx int32 [nb_off[N]]: per block the occupied blocks within +-2 block steps, the block itself
+ *   first, then by squared block distance ((dx, dy, dz) lexicographic among equals).
+ * nvf_pp_grids: dist[i] = sqrtf(d2[i]) correctly rounded, gt[i] = (d2[i] == 0) as 1.0f / 0.0f, i < n; d2 in [0, 2^24);
+ *   pointers 16-byte aligned; dist may be the buffer of d2 itself. */
+#define NVF_PP_META_INTS 16
+#define NVF_PP_OCT_BYTES 37449
+int nvf_pp_keys(const int32_t* pts, int npts, int32_t* keys, uint32_t* bitmap6, int32_t* meta, void* stream);
+int nvf_pp_tree(const uint32_t* bitmap6, int32_t* origins, uint32_t* rank_tab, uint8_t* octree_bytes, int32_t* nb_off,
+                int32_t* meta, void* stream);
+int nvf_pp_blocks(const int32_t* sorted_keys, int npts, const uint32_t* rank_tab, int32_t* meta, int32_t* pts,
+                  int32_t* blk_off, void* stream);
+int nvf_pp_neighbours(const int32_t* origins, const uint32_t* rank_tab, const int32_t* nb_off, int32_t* nb_idx,
+                      int nblocks, void* stream);
+int nvf_pp_grids(const int32_t* d2, float* dist, float* gt, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,30 @@ class LoadedVoxelDataset(torch.utils.data.Dataset):
         self.N = self.gt_grid.sum()              # occupied voxels = input points (b_net's denominator, NVFPCC.py:162)
         print(f"[data] {self.N_leaf} leaf blocks, {self.N} points")
 
+    @classmethod
+    def from_device(cls, pre, shuffle=True):
+        """The dataset of a cloud pre-processed on the device (preprocess.preprocess_device): the grids stay where they
+        are and `to_device` hands them out; the numpy views `gt_grid` / `dist` of the file-based dataset are built on
+        first use only."""
+        self = cls.__new__(cls)
+        torch.utils.data.Dataset.__init__(self)
+        self.shuffle = shuffle
+        self._resident = (pre.gt, pre.dist)
+        self.origins = pre.origins.cpu().numpy().astype(np.float64)
+        self.N_leaf = self.origins.shape[0]
+        self.N = np.uint64(pre.n_points)
+        print(f"[data] {self.N_leaf} leaf blocks, {self.N} points")
+        return self
+
+    def __getattr__(self, name):
+        # reached only when the attribute is missing: the lazy host copies of a device-resident dataset
+        if name in ("gt_grid", "dist") and "_resident" in self.__dict__:
+            gt, dist = self._resident
+            value = gt.cpu().numpy().astype(np.uint8) if name == "gt_grid" else dist.cpu().numpy()
+            self.__dict__[name] = value
+            return value
+        raise AttributeError(name)
+
     def permute(self, idx):
         return (idx * self.MAGIC) % self.N_leaf if self.shuffle else idx
 
@@ -33,6 +57,12 @@ class LoadedVoxelDataset(torch.utils.data.Dataset):
 
     # ---- MI355X-native feeding: everything resident on the device ----
     def to_device(self, device):
+        if "_resident" in self.__dict__:
+            gt, dist = self._resident
+            want = torch.device(device)
+            if gt.device.type != want.type or want.index not in (None, gt.device.index):
+                raise RuntimeError(f"the dataset is resident on {gt.device}, not on {device}")
+            return gt, dist
         gt, dist = self.get_all()
         return gt.to(device), dist.to(device)
 

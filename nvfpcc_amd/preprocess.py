@@ -7,6 +7,9 @@
   * per-cube occupancy and distance grids: dist = Euclidean distance of every voxel of every cube to the
     nearest input point, gt_grid = (dist == 0), axes (x, y, z) (util_get_grids.py:19-46) -- the distances come
     from the gfx950 kernel nvf_nearest_dist2 instead of 30 M KD-tree queries in a Python loop.
+
+`preprocess_device` does both on the device (csrc/pp_device.hip) and leaves the float32 grids there for the trainer;
+`write_octree_pack` / `read_octree_pack` carry the partition in pack.pk as octree bytes instead of raw origins.
 """
 import numpy as np
 import torch
@@ -123,3 +126,179 @@ def preprocess(ply_path, level=5, device="cuda"):
     np.save(f"{fid}_l5_gt_grid", gt)
     np.save(f"{fid}_l5_dist", dist)
     return origins, gt, dist
+
+
+# ---------------------------------------------------------------- the octree as bytes (host side, <= a few thousand nodes)
+# A node's eight children are one byte (bit i = child i = character i of the reference's string); the nodes of a level
+# in traversal order are the cells of that level in ascending Morton code (x in the lowest bit of each level).
+OCTREE_PACK_LEVELS = 5          # levels 0..4: the children of level 4 are the leaf cubes
+
+
+def _morton(cells, levels):
+    return _child_path_key(np.asarray(cells, np.int64), levels)
+
+
+def _unmorton(codes, levels):
+    codes = np.asarray(codes, np.int64)
+    out = np.zeros((codes.shape[0], 3), np.int64)
+    for bit in range(levels):
+        for axis in range(3):
+            out[:, axis] |= ((codes >> (3 * bit + axis)) & 1) << bit
+    return out
+
+
+def octree_level_bytes(points):
+    """The child-occupancy bytes of levels 0..5, breadth first, one `bytes` per level: what octree_level5's string
+    holds, eight characters to the byte."""
+    pts = np.asarray(points, np.int64).reshape(-1, 3)
+    if pts.shape[0] == 0:
+        raise ValueError("empty cloud")
+    if pts.min() < 0 or pts.max() >= ROOT:
+        raise ValueError("coordinates must lie in [0, 1024)")
+    codes = np.unique(_morton(pts >> 4, 6))                      # occupied level-6 cells
+    levels = []
+    for _ in range(6):
+        parents, inverse = np.unique(codes >> 3, return_inverse=True)
+        b = np.zeros(parents.shape[0], np.uint8)
+        np.bitwise_or.at(b, inverse, (1 << (codes & 7)).astype(np.uint8))
+        levels.append(b.tobytes())
+        codes = parents
+    return levels[::-1]
+
+
+def subtree_from_level_bytes(levels):
+    """Per-level bytes -> the reference's `*_l5_subtree.txt` string."""
+    return "".join("".join(map(str, np.unpackbits(np.frombuffer(b, np.uint8), bitorder="little").tolist()))
+                   for b in levels)
+
+
+def write_octree_pack(levels):
+    """The `octree_pack` entry of pack.pk: one header byte (the number of levels that follow) + the bytes of levels
+    0..4.  Its length times 8 is the side information the encoder adds to Gross bpp."""
+    levels = [bytes(b) for b in levels[:OCTREE_PACK_LEVELS]]
+    if len(levels) != OCTREE_PACK_LEVELS:
+        raise ValueError(f"octree_pack needs the bytes of levels 0..{OCTREE_PACK_LEVELS - 1}")
+    return bytes([OCTREE_PACK_LEVELS]) + b"".join(levels)
+
+
+def read_octree_pack(data):
+    """octree_pack -> origins int64 [N,3] of the leaf cubes in the reference's traversal order.  Every node byte is
+    read exactly once; a stream that is short, long, or holds a node without children raises ValueError."""
+    data = np.frombuffer(bytes(data), np.uint8)
+    if data.size < 1 or int(data[0]) != OCTREE_PACK_LEVELS:
+        raise ValueError("octree_pack: unknown header byte")
+    codes, at = np.zeros(1, np.int64), 1
+    for level in range(OCTREE_PACK_LEVELS):
+        n = codes.shape[0]
+        if at + n > data.size:
+            raise ValueError(f"octree_pack: truncated at level {level}")
+        b = data[at:at + n]
+        at += n
+        if not b.all():
+            raise ValueError(f"octree_pack: a node of level {level} has no children")
+        kids = np.unpackbits(b[:, None], axis=1, bitorder="little").astype(bool)      # [n, 8], column i = child i
+        codes = (codes[:, None] * 8 + np.arange(8))[kids]                            # row-major: ascending code
+    if at != data.size:
+        raise ValueError("octree_pack: bytes left over after the last level")
+    return _unmorton(codes, OCTREE_PACK_LEVELS) * LEAF
+
+
+def octree_pack_from_origins(origins):
+    """The pack of a partition given by its leaf origins (the file-based encoder has nothing else)."""
+    return write_octree_pack(octree_level_bytes(np.asarray(origins, np.int64))[:OCTREE_PACK_LEVELS])
+
+
+# ---------------------------------------------------------------- the whole pre-processing on the device
+MAX_LEAVES = (ROOT // LEAF) ** 3
+OCT_BYTES = 37449               # NVF_PP_OCT_BYTES: level L starts at byte (8^L - 1) / 7
+META_INTS = 16                  # NVF_PP_META_INTS
+
+
+class DevicePreprocess:
+    """What preprocess_device leaves on the device.  origins int32 [N,3] (traversal order), blk_off int32 [N+1],
+    points int32 [P,3] sorted by block, (nb_off, nb_idx) the candidate lists, gt / dist float32 [N,1,32,32,32],
+    n_points = occupied voxels.  octree_bytes (six `bytes`, level 0..5) and subtree are fetched when first asked."""
+
+    def __init__(self, origins, blk_off, points, nb_off, nb_idx, gt, dist, n_points, oct_dev, level_counts):
+        self.origins, self.blk_off, self.points, self.nb_off, self.nb_idx = origins, blk_off, points, nb_off, nb_idx
+        self.gt, self.dist, self.n_points = gt, dist, int(n_points)
+        self._oct_dev, self._level_counts = oct_dev, [int(c) for c in level_counts]
+        self._octree_bytes = self._subtree = None
+
+    @property
+    def octree_bytes(self):
+        if self._octree_bytes is None:
+            raw = self._oct_dev.cpu().numpy().tobytes()
+            starts = [(8 ** lv - 1) // 7 for lv in range(6)]
+            self._octree_bytes = tuple(raw[s:s + c] for s, c in zip(starts, self._level_counts))
+        return self._octree_bytes
+
+    @property
+    def subtree(self):
+        if self._subtree is None:
+            self._subtree = subtree_from_level_bytes(self.octree_bytes)
+        return self._subtree
+
+    def octree_pack(self):
+        return write_octree_pack(self.octree_bytes)
+
+
+def grids_from_d2(d2, in_place=False):
+    """int32 squared distances -> (gt, dist) float32 of the same shape: dist = sqrtf(d2), gt = (d2 == 0).  in_place:
+    dist takes d2's memory (d2 is gone afterwards)."""
+    if not d2.is_cuda or not d2.is_contiguous() or d2.dtype != torch.int32:
+        raise RuntimeError("grids_from_d2 needs a contiguous int32 tensor on the HIP device")
+    dist = d2.view(torch.float32) if in_place else torch.empty(d2.shape, dtype=torch.float32, device=d2.device)
+    gt = torch.empty(d2.shape, dtype=torch.float32, device=d2.device)
+    if d2.numel():
+        check(lib().nvf_pp_grids(d2.data_ptr(), dist.data_ptr(), gt.data_ptr(), d2.numel(),
+                                 torch.cuda.current_stream().cuda_stream), "nvf_pp_grids")
+    return gt, dist
+
+
+def preprocess_device(points, device="cuda"):
+    """octree_level5 + build_grids on the device: integer points [P,3] (numpy or tensor, 10-bit coordinates, duplicates
+    allowed) -> DevicePreprocess.  The host reads one 64-byte record (N, the count of rejected points, the list
+    sizes); nothing that scales with P or with the voxels crosses the bus after the points went up."""
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("preprocess_device runs on the HIP device only; there is no CPU fallback")
+    t = points if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points))
+    if t.dim() != 2 or t.shape[1] != 3 or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise ValueError("points must be an integer array of shape [P, 3]")
+    npts = t.shape[0]
+    if npts == 0:
+        raise ValueError("empty cloud")
+    if npts >= 1 << 30:
+        raise ValueError("too many points")
+    t = t.to(dev)
+    if t.dtype != torch.int32:
+        t = t.to(torch.int64).clamp(-1, ROOT).to(torch.int32)               # out of range stays out of range in 32 bits
+    t = t.contiguous()
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream().cuda_stream
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        keys, bitmap6, meta = i32(npts), i32(8192), i32(META_INTS)
+        origins, tab, nb_off, blk_off = i32(MAX_LEAVES, 3), i32(2048), i32(MAX_LEAVES + 1), i32(MAX_LEAVES + 1)
+        oct_dev = torch.empty(OCT_BYTES, dtype=torch.uint8, device=dev)
+        spts = i32(npts, 3)
+        L = lib()
+        check(L.nvf_pp_keys(t.data_ptr(), npts, keys.data_ptr(), bitmap6.data_ptr(), meta.data_ptr(), st), "nvf_pp_keys")
+        skeys = torch.sort(keys).values                          # plumbing: equal keys are equal points
+        check(L.nvf_pp_tree(bitmap6.data_ptr(), origins.data_ptr(), tab.data_ptr(), oct_dev.data_ptr(),
+                            nb_off.data_ptr(), meta.data_ptr(), st), "nvf_pp_tree")
+        check(L.nvf_pp_blocks(skeys.data_ptr(), npts, tab.data_ptr(), meta.data_ptr(), spts.data_ptr(),
+                              blk_off.data_ptr(), st), "nvf_pp_blocks")
+        m = meta.cpu().tolist()                                  # the one host sync of the call
+        n, bad, level_counts, nb_total, voxels = m[0], m[1], m[2:8], m[8], m[9]
+        if bad:
+            raise ValueError(f"coordinates must lie in [0, 1024): {bad} points do not")
+        origins, nb_off, blk_off = origins[:n], nb_off[:n + 1], blk_off[:n + 1]
+        nb_idx = i32(nb_total)
+        check(L.nvf_pp_neighbours(origins.data_ptr(), tab.data_ptr(), nb_off.data_ptr(), nb_idx.data_ptr(), n, st),
+              "nvf_pp_neighbours")
+        d2 = i32(n, 1, LEAF, LEAF, LEAF)
+        check(L.nvf_nearest_dist2(spts.data_ptr(), blk_off.data_ptr(), origins.data_ptr(), nb_off.data_ptr(),
+                                  nb_idx.data_ptr(), d2.data_ptr(), n, st), "nvf_nearest_dist2")
+        gt, dist = grids_from_d2(d2, in_place=True)
+    return DevicePreprocess(origins, blk_off, spts, nb_off, nb_idx, gt, dist, voxels, oct_dev, level_counts)
