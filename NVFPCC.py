@@ -14,8 +14,9 @@ engine (nvfpcc_amd/engine.py) instead of a DataLoader + autograd loop.
 
     python NVFPCC.py train cloud.ply --from_ply ...                            # no get_octree / util_get_grids run, no .npy
     python NVFPCC.py encode cloud.ply --from_ply --pack_octree ...             # leaves travel as octree bytes; decode needs no --N
+    python NVFPCC.py train cloud_vox11.ply --from_ply --bits 11 ...            # 11 or 12 bits per axis (--from_ply only)
 
-Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --pack_octree, --thh_mode (count | block-count | d1:
+Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --bits, --pack_octree, --thh_mode (count | block-count | d1:
 nvfpcc_amd/thh_select.py picks the occupancy threshold at encode time and a `thh_pack` key carries it); multi-GPU training when launched
 through torch.distributed.run (one process per GPU, leaf blocks sharded, one RCCL all-reduce per step).
 Headless: no GUI window, no IPython shell.
@@ -66,10 +67,27 @@ def _build_net(args, dev):
     return Net(args, param_model, args.ch, channel_str=args.chanstr).to(dev)
 
 
-def _psnr1(sse, denom):
+def _psnr1(sse, denom, peak=1023):
     with np.errstate(divide="ignore", invalid="ignore"):     # 0 / 0 prints nan, as in the reference (NVFPCC.py:259-260)
         mse1 = np.float64(sse) / np.float64(denom)
-        return mse1, 20 * np.log10(1023 / np.sqrt(mse1 / 3))
+        return mse1, 20 * np.log10(peak / np.sqrt(mse1 / 3))
+
+
+def _bits(args):
+    """--bits of train / encode (10 when absent) after the checks that need no device: what the deeper partition does
+    not reach exits here, with its reason, before any GPU work."""
+    bits = getattr(args, 'bits', 10)
+    if bits > 10:
+        if not getattr(args, 'from_ply', False):
+            raise SystemExit(f"--bits {bits} needs --from_ply: the *_l5_*.npy route (get_octree.py, util_get_grids.py) "
+                             f"is 10-bit only")
+        if args.ref_ply is not None:
+            raise SystemExit(f"--ref_ply with --bits {bits} is not supported: the D1 / D2 metrics (nvfpcc_amd.pc_metrics) "
+                             f"index a dense grid of a 1024^3 volume and stop at 10 bits per axis")
+        if args.thh_mode == 'd1':
+            raise SystemExit(f"--thh_mode d1 with --bits {bits} is not supported: it scores its candidates with "
+                             f"nvfpcc_amd.pc_metrics, which stops at 10 bits per axis; use count or block-count")
+    return bits
 
 
 def _load_data(args, dev, shuffle=True):
@@ -79,7 +97,7 @@ def _load_data(args, dev, shuffle=True):
     from nvfpcc_amd.dataloader import LoadedVoxelDataset
     if getattr(args, 'from_ply', False):
         from nvfpcc_amd import preprocess as pp
-        pre = pp.preprocess_device(pp.read_ply_xyz(args.input), dev)
+        pre = pp.preprocess_device(pp.read_ply_xyz(args.input), dev, bits=getattr(args, 'bits', 10))
         return LoadedVoxelDataset.from_device(pre, shuffle=shuffle), pre
     fid = args.input[:-4]
     return LoadedVoxelDataset(f'{fid}_l5_origins.npy', f'{fid}_l5_gt_grid.npy', f'{fid}_l5_dist.npy',
@@ -89,6 +107,7 @@ def _load_data(args, dev, shuffle=True):
 def train(args):
     from nvfpcc_amd import dist as nd, ops
     from nvfpcc_amd.engine import TrainEngine, EpochDriver
+    peak = (1 << _bits(args)) - 1
     dev, rank, world = _device(args)
     say = print if rank == 0 else (lambda *a, **k: None)
     say(f'Rate loss = {args.w1} * b1 + b2 + {args.w2} * b3')
@@ -121,7 +140,7 @@ def train(args):
         nd.allgather_rows_(eng.emb, rank, world)
         # NaN guards of NVFPCC.py:199-212 are checked here, on the summed counters (raises ValueError)
         acc = eng.read_epoch_stats(reduce=nd.allreduce_sum_ if world > 1 else None, world=world)
-        say(TRAIN_LINE % ((epoch, time.time() - t0) + tuple(eng.train_log_fields(acc, nsteps))))
+        say(TRAIN_LINE % ((epoch, time.time() - t0) + tuple(eng.train_log_fields(acc, nsteps, peak=peak))))
         if epoch % 10 == 0:
             if rank == 0:
                 print('[INFO] Saving')
@@ -132,11 +151,11 @@ def train(args):
             # the every-10th-epoch evaluation (NVFPCC.py:308-392), sharded: each rank its contiguous blocks, one small
             # all-reduce of the 22 log sums (the reference runs it on its single device)
             t1 = time.time()
-            fields = tuple(test_log_fields(eng, net, data.N, args.lmbda, rank, world, nd.allreduce_sum_))
+            fields = tuple(test_log_fields(eng, net, data.N, args.lmbda, rank, world, nd.allreduce_sum_, peak=peak))
             say(TEST_LINE % ((epoch, time.time() - t1) + fields))
 
 
-def test_log_fields(eng, net, n_points, lmbda, rank=0, world=1, reduce=None):
+def test_log_fields(eng, net, n_points, lmbda, rank=0, world=1, reduce=None, peak=1023):
     """The 17 numbers of the reference's TEST line (NVFPCC.py:308-392): full-batch net(emb, 'eval', 2), the same
     losses / metrics as the TRAIN line on ALL blocks (one "mini-batch": cnt = 1), and b_all = (latent bits + network
     bits incl. the side information of Net.get_network_bits) / N.  Quirk kept: its Loss adds lambda * (b_latent + b_net)
@@ -149,18 +168,18 @@ def test_log_fields(eng, net, n_points, lmbda, rank=0, world=1, reduce=None):
     if reduce is not None and world > 1:
         reduce(sums)
     return test_fields_from_sums(sums.double().cpu().numpy(), eng.weight_bits(), float(eng.counts.sum()), float(n_points),
-                                 lmbda, net.get_network_bits())
+                                 lmbda, net.get_network_bits(), peak=peak)
 
 
-def test_fields_from_sums(sums, weight_bits, n_pts, n_points, lmbda, network_bits):
+def test_fields_from_sums(sums, weight_bits, n_pts, n_points, lmbda, network_bits, peak=1023):
     """Host arithmetic of the TEST line from the 22 additive sums of TrainEngine.eval_sums (focal terms [0:3], metric
-    counts [3:21], latent bits [21])."""
+    counts [3:21], latent bits [21]).  peak: 2^bits - 1 of the cloud, the peak of PSNR1."""
     ls, c, lat_bits = sums[0:3], sums[3:21], float(sums[21])
     b_latent, b_net = lat_bits / n_pts, float(weight_bits) / float(n_points)
     with np.errstate(divide="ignore", invalid="ignore"):
         r = [c[6 * t + k] / c[6 * t + k + 1] for t in range(3) for k in (0, 2)]
         mse1 = c[4] / c[5]
-        psnr1 = 20 * np.log10(1023 / np.sqrt(mse1 / 3))
+        psnr1 = 20 * np.log10(peak / np.sqrt(mse1 / 3))
     b_all = (lat_bits + network_bits) / float(n_points)
     return [ls[0] + ls[1] + ls[2] + lmbda * (b_latent + b_net), 0.0, 0.0, r[0], r[1], ls[1], ls[2], r[2], r[3], r[4],
             r[5], b_latent + b_net, b_latent, b_net, b_all, mse1, psnr1]
@@ -179,6 +198,7 @@ def encode(args):
     """Pack everything the decoder needs (NVFPCC.py:395-554)."""
     from nvfpcc_amd import ops, weight_codec, latent_codec
     from nvfpcc_amd.recon import reconstruct_points, write_ply_ascii
+    bits = _bits(args)
     dev, rank, world = _device(args)
     data, pre = _load_data(args, dev, shuffle=False)
     net = _build_net(args, dev)
@@ -225,7 +245,7 @@ def encode(args):
         print(sel['line'])
     print('[Latent code] Gross bpp: %.4f' % ((latent_bits + net_bits + side_bits) / data.N))
     print('[Recon] Pacc: %.4f Nacc: %.4f MSE1: %.4f PSNR1: %.4f' % (
-        m[0] / max(m[1], 1), m[2] / max(m[3], 1), *_psnr1(m[4], m[5])))
+        m[0] / max(m[1], 1), m[2] / max(m[3], 1), *_psnr1(m[4], m[5], (1 << bits) - 1)))
     write_ply_ascii('rc_enc.ply', pts)
     _print_pc_error(args, pts, dev)
 
@@ -281,6 +301,9 @@ def decode(args):
     else:
         n = int(args.N)
         origins = total_pack['origins'][:n]
+    if args.ref_ply is not None and n and int(np.max(origins)) >= 1024:
+        raise SystemExit("--ref_ply: this pack holds a cloud of more than 10 bits per axis; the D1 / D2 metrics "
+                         "(nvfpcc_amd.pc_metrics) stop at 10")
     print('Start to reconstruct')
     thh, block_counts, used = args.thh, None, []
     side = total_pack.get('thh_pack')
@@ -357,6 +380,9 @@ def build_parser():
     p.add_argument('--from_ply', action='store_true', default=argparse.SUPPRESS,
                    help='train / encode: the input is the cloud itself (ASCII PLY, 10-bit coordinates); it is '
                         'pre-processed on the device and no *_l5_*.npy file is read or written.')
+    p.add_argument('--bits', type=int, choices=[10, 11, 12], default=argparse.SUPPRESS,
+                   help='train / encode with --from_ply: bits per axis of the cloud (10 when absent).  The leaf cubes '
+                        'stay 32^3, so 11 and 12 make the octree one and two levels deeper; decode needs no flag.')
     p.add_argument('--pack_octree', action='store_true', default=argparse.SUPPRESS,
                    help='encode: carry the leaf cubes in the pack as octree occupancy bytes (octree_pack, counted in '
                         'Gross bpp) instead of raw origins; decode then needs no --N.')

@@ -822,6 +822,29 @@ int nvf_pp_neighbours(const int32_t* origins, const uint32_t* rank_tab, const in
                       int nblocks, void* stream);
 int nvf_pp_grids(const int32_t* d2, float* dist, float* gt, int64_t n, void* stream);
 
+/* The same four steps for clouds of 11 or 12 bits per axis (csrc/pp_deep.hip); bits = 10 is served by the entry points
+ * above and rejected here.  D = bits - 5 is the level of the 32^3 leaves, a cell code has 3 D bits, W = 8^D / 32 is the
+ * number of words of the level-D bitmap and cap(L) = min(8^L, npts) bounds the nodes of level L.  Same call order, same
+ * contracts, with these differences:
+ * nvf_pp_keys_deep: keys are int64 (cell code << 15 | local voxel, up to 36 bits; 0x7fffffffffffffff for a rejected
+ *   point); bitmap uint32 [8 W] is the level-(D + 1) bitmap (256 KiB at 11 bits, 2 MiB at 12) and stays in global memory.
+ * nvf_pp_tree_deep: origins has room for cap(D) rows, nb_off for cap(D) + 1; rank_tab uint32 [2 W]; octree_bytes holds
+ *   level L at byte sum of cap(l) over l < L, so sum of cap(L) over L <= D bytes in all; work uint32
+ *   [NVF_PP_DEEP_WORK_WORDS] is scratch.  A grid-wide prefix sum is three launches (sums per workgroup, one workgroup
+ *   scans them, emit); no workgroup waits for another.  meta: [0] N, [1] rejected points, [2..9] bytes of level 0..7
+ *   (D + 1 of them are written), [10] nb_off[N], [11] occupied voxels (written by nvf_pp_blocks_deep).
+ * nvf_pp_blocks_deep: blk_off has room for cap(D) + 1.
+ * nvf_pp_neighbours_deep: the steps are taken on the 2^D grid; an octant boundary is no boundary. */
+#define NVF_PP_DEEP_WORK_WORDS 11264
+int nvf_pp_keys_deep(const int32_t* pts, int npts, int bits, int64_t* keys, uint32_t* bitmap, int32_t* meta,
+                     void* stream);
+int nvf_pp_tree_deep(const uint32_t* bitmap, int bits, int npts, int32_t* origins, uint32_t* rank_tab,
+                     uint8_t* octree_bytes, int32_t* nb_off, uint32_t* work, int32_t* meta, void* stream);
+int nvf_pp_blocks_deep(const int64_t* sorted_keys, int npts, int bits, const uint32_t* rank_tab, int32_t* meta,
+                       int32_t* pts, int32_t* blk_off, void* stream);
+int nvf_pp_neighbours_deep(const int32_t* origins, int bits, const uint32_t* rank_tab, const int32_t* nb_off,
+                           int32_t* nb_idx, int nblocks, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

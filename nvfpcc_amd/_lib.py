@@ -140,6 +140,10 @@ PROTOTYPES = {
     "nvf_pp_blocks": (I, [P, I, P, P, P, P, P]),
     "nvf_pp_neighbours": (I, [P, P, P, P, I, P]),
     "nvf_pp_grids": (I, [P, P, P, L, P]),
+    "nvf_pp_keys_deep": (I, [P, I, I, P, P, P, P]),
+    "nvf_pp_tree_deep": (I, [P, I, I, P, P, P, P, P, P, P]),
+    "nvf_pp_blocks_deep": (I, [P, I, I, P, P, P, P, P]),
+    "nvf_pp_neighbours_deep": (I, [P, I, P, P, P, I, P]),
 }
 
 

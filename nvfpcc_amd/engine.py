@@ -887,15 +887,16 @@ class TrainEngine:
             raise ValueError("Problem with grad: %d non-finite gradient entries this epoch" % int(acc[6]))
         return acc
 
-    def train_log_fields(self, acc, nsteps):
+    def train_log_fields(self, acc, nsteps, peak=1023):
         """The 16 numbers of the reference's TRAIN line after 'seconds]' (NVFPCC.py:261-281), from read_epoch_stats:
         Loss, PosiPenal, PosiGain, Pacc, Nacc, S1 Loss, S2 Loss, S1Pacc, S1Nacc, S2Pacc, S2Nacc, bpp, b_latent, b_net,
-        MSE1, PSNR1 -- means over the epoch's mini-batches, MSE1 = sum sse / sum denom (0 / 0 = nan, as there)."""
+        MSE1, PSNR1 -- means over the epoch's mini-batches, MSE1 = sum sse / sum denom (0 / 0 = nan, as there).  peak:
+        2^bits - 1 of the cloud, the peak of PSNR1."""
         cnt = float(nsteps)
         ls, bl, bn = acc[0:3] / cnt, acc[3] / cnt, acc[4] / cnt
         with np.errstate(divide="ignore", invalid="ignore"):
             mse1 = np.float64(acc[14]) / np.float64(acc[15])
-            psnr1 = 20 * np.log10(1023 / np.sqrt(mse1 / 3))
+            psnr1 = 20 * np.log10(peak / np.sqrt(mse1 / 3))
         loss = ls.sum() + self.lmbda * (bl * self.w1 + bn * self.w2)
         return [loss, 0.0, 0.0, acc[8] / cnt, acc[9] / cnt, ls[1], ls[2], acc[10] / cnt, acc[11] / cnt,
                 acc[12] / cnt, acc[13] / cnt, bl + bn, bl, bn, mse1, psnr1]

@@ -1,4 +1,4 @@
-"""Pre-processing of a 10-bit voxelised point cloud into the three `*_l5_*.npy` files the trainer reads
+"""Pre-processing of a voxelised point cloud (10 bits per axis; 11 and 12 on the device route) into the three `*_l5_*.npy` files the trainer reads
 (SURVEY.md section 8, row f2):
 
   * level-5 octree partition: the 32^3 leaf cubes in the reference's depth-first child order
@@ -8,7 +8,7 @@
     nearest input point, gt_grid = (dist == 0), axes (x, y, z) (util_get_grids.py:19-46) -- the distances come
     from the gfx950 kernel nvf_nearest_dist2 instead of 30 M KD-tree queries in a Python loop.
 
-`preprocess_device` does both on the device (csrc/pp_device.hip) and leaves the float32 grids there for the trainer;
+`preprocess_device` does both on the device (csrc/pp_device.hip; csrc/pp_deep.hip for 11 and 12 bits per axis) and leaves the float32 grids there for the trainer;
 `write_octree_pack` / `read_octree_pack` carry the partition in pack.pk as octree bytes instead of raw origins.
 """
 import numpy as np
@@ -18,6 +18,14 @@ from ._lib import lib, check
 
 LEAF = 32
 ROOT = 1024
+BITS = (10, 11, 12)             # bits per axis; the leaves are the cells of level D = bits - 5
+
+
+def _depth(bits):
+    """D = bits - 5, the octree level of the 32^3 leaf blocks."""
+    if isinstance(bits, bool) or bits not in BITS:
+        raise ValueError(f"bits must be one of {BITS}, not {bits!r}")
+    return int(bits) - 5
 
 
 def read_ply_xyz(path):
@@ -64,6 +72,17 @@ def octree_level5(points):
                 c = (2 * nx + (i & 1), 2 * ny + ((i >> 1) & 1), 2 * nz + ((i >> 2) & 1))
                 bits.append("1" if c in occupied else "0")
     return origins, "".join(bits)
+
+
+def octree_partition(points, bits=10):
+    """octree_level5 for a cloud of `bits` bits per axis: (origins int64 [N,3] of the 32^3 leaves in traversal order,
+    the breadth-first bit string of levels 0..D, D = bits - 5).  octree_partition(p, 10) equals octree_level5(p)."""
+    depth = _depth(bits)
+    pts = np.asarray(points, np.int64).reshape(-1, 3)
+    levels = octree_level_bytes(pts, bits)
+    cells = np.unique(pts // LEAF, axis=0)
+    origins = cells[np.argsort(_child_path_key(cells, depth), kind="stable")] * LEAF
+    return origins, subtree_from_level_bytes(levels)
 
 
 def write_origins_txt(path, origins):
@@ -147,17 +166,18 @@ def _unmorton(codes, levels):
     return out
 
 
-def octree_level_bytes(points):
-    """The child-occupancy bytes of levels 0..5, breadth first, one `bytes` per level: what octree_level5's string
-    holds, eight characters to the byte."""
+def octree_level_bytes(points, bits=10):
+    """The child-occupancy bytes of levels 0..D (D = bits - 5: 0..5 at 10 bits), breadth first, one `bytes` per level:
+    what octree_level5's string holds, eight characters to the byte."""
+    depth = _depth(bits)
     pts = np.asarray(points, np.int64).reshape(-1, 3)
     if pts.shape[0] == 0:
         raise ValueError("empty cloud")
-    if pts.min() < 0 or pts.max() >= ROOT:
-        raise ValueError("coordinates must lie in [0, 1024)")
-    codes = np.unique(_morton(pts >> 4, 6))                      # occupied level-6 cells
+    if pts.min() < 0 or pts.max() >= 1 << bits:
+        raise ValueError(f"coordinates must lie in [0, {1 << bits})")
+    codes = np.unique(_morton(pts >> 4, depth + 1))              # occupied 16^3 cells, one level below the leaves
     levels = []
-    for _ in range(6):
+    for _ in range(depth + 1):
         parents, inverse = np.unique(codes >> 3, return_inverse=True)
         b = np.zeros(parents.shape[0], np.uint8)
         np.bitwise_or.at(b, inverse, (1 << (codes & 7)).astype(np.uint8))
@@ -172,23 +192,33 @@ def subtree_from_level_bytes(levels):
                    for b in levels)
 
 
-def write_octree_pack(levels):
-    """The `octree_pack` entry of pack.pk: one header byte (the number of levels that follow) + the bytes of levels
-    0..4.  Its length times 8 is the side information the encoder adds to Gross bpp."""
-    levels = [bytes(b) for b in levels[:OCTREE_PACK_LEVELS]]
-    if len(levels) != OCTREE_PACK_LEVELS:
-        raise ValueError(f"octree_pack needs the bytes of levels 0..{OCTREE_PACK_LEVELS - 1}")
-    return bytes([OCTREE_PACK_LEVELS]) + b"".join(levels)
+PACK_DEPTHS = (5, 6, 7)         # the header byte: 5 for 10 bits per axis, 6 for 11, 7 for 12
+
+
+def write_octree_pack(levels, depth=None):
+    """The `octree_pack` entry of pack.pk: one header byte (the number D of levels that follow: 5, 6 or 7) + the bytes
+    of levels 0..D-1.  `levels` is what octree_level_bytes returns (D + 1 entries, the last is not carried) or its
+    first D entries with `depth` = D; five entries without `depth` are levels 0..4.  Its length times 8 is the side
+    information the encoder adds to Gross bpp."""
+    if depth is None:
+        depth = max(len(levels) - 1, OCTREE_PACK_LEVELS)
+    if depth not in PACK_DEPTHS:
+        raise ValueError(f"octree_pack carries {PACK_DEPTHS} levels, not {depth}")
+    levels = [bytes(b) for b in levels[:depth]]
+    if len(levels) != depth:
+        raise ValueError(f"octree_pack needs the bytes of levels 0..{depth - 1}")
+    return bytes([depth]) + b"".join(levels)
 
 
 def read_octree_pack(data):
     """octree_pack -> origins int64 [N,3] of the leaf cubes in the reference's traversal order.  Every node byte is
     read exactly once; a stream that is short, long, or holds a node without children raises ValueError."""
     data = np.frombuffer(bytes(data), np.uint8)
-    if data.size < 1 or int(data[0]) != OCTREE_PACK_LEVELS:
+    if data.size < 1 or int(data[0]) not in PACK_DEPTHS:
         raise ValueError("octree_pack: unknown header byte")
+    depth = int(data[0])
     codes, at = np.zeros(1, np.int64), 1
-    for level in range(OCTREE_PACK_LEVELS):
+    for level in range(depth):
         n = codes.shape[0]
         if at + n > data.size:
             raise ValueError(f"octree_pack: truncated at level {level}")
@@ -200,12 +230,13 @@ def read_octree_pack(data):
         codes = (codes[:, None] * 8 + np.arange(8))[kids]                            # row-major: ascending code
     if at != data.size:
         raise ValueError("octree_pack: bytes left over after the last level")
-    return _unmorton(codes, OCTREE_PACK_LEVELS) * LEAF
+    return _unmorton(codes, depth) * LEAF
 
 
-def octree_pack_from_origins(origins):
+def octree_pack_from_origins(origins, bits=10):
     """The pack of a partition given by its leaf origins (the file-based encoder has nothing else)."""
-    return write_octree_pack(octree_level_bytes(np.asarray(origins, np.int64))[:OCTREE_PACK_LEVELS])
+    depth = _depth(bits)
+    return write_octree_pack(octree_level_bytes(np.asarray(origins, np.int64), bits)[:depth], depth)
 
 
 # ---------------------------------------------------------------- the whole pre-processing on the device
@@ -217,20 +248,22 @@ META_INTS = 16                  # NVF_PP_META_INTS
 class DevicePreprocess:
     """What preprocess_device leaves on the device.  origins int32 [N,3] (traversal order), blk_off int32 [N+1],
     points int32 [P,3] sorted by block, (nb_off, nb_idx) the candidate lists, gt / dist float32 [N,1,32,32,32],
-    n_points = occupied voxels.  octree_bytes (six `bytes`, level 0..5) and subtree are fetched when first asked."""
+    n_points = occupied voxels, bits = bits per axis.  octree_bytes (D + 1 = bits - 4 `bytes`, level 0..D) and subtree
+    are fetched when first asked."""
 
-    def __init__(self, origins, blk_off, points, nb_off, nb_idx, gt, dist, n_points, oct_dev, level_counts):
+    def __init__(self, origins, blk_off, points, nb_off, nb_idx, gt, dist, n_points, oct_dev, level_counts,
+                 level_starts=None, bits=10):
         self.origins, self.blk_off, self.points, self.nb_off, self.nb_idx = origins, blk_off, points, nb_off, nb_idx
-        self.gt, self.dist, self.n_points = gt, dist, int(n_points)
+        self.gt, self.dist, self.n_points, self.bits = gt, dist, int(n_points), int(bits)
         self._oct_dev, self._level_counts = oct_dev, [int(c) for c in level_counts]
+        self._level_starts = level_starts if level_starts is not None else [(8 ** lv - 1) // 7 for lv in range(6)]
         self._octree_bytes = self._subtree = None
 
     @property
     def octree_bytes(self):
         if self._octree_bytes is None:
             raw = self._oct_dev.cpu().numpy().tobytes()
-            starts = [(8 ** lv - 1) // 7 for lv in range(6)]
-            self._octree_bytes = tuple(raw[s:s + c] for s, c in zip(starts, self._level_counts))
+            self._octree_bytes = tuple(raw[s:s + c] for s, c in zip(self._level_starts, self._level_counts))
         return self._octree_bytes
 
     @property
@@ -256,10 +289,12 @@ def grids_from_d2(d2, in_place=False):
     return gt, dist
 
 
-def preprocess_device(points, device="cuda"):
-    """octree_level5 + build_grids on the device: integer points [P,3] (numpy or tensor, 10-bit coordinates, duplicates
-    allowed) -> DevicePreprocess.  The host reads one 64-byte record (N, the count of rejected points, the list
-    sizes); nothing that scales with P or with the voxels crosses the bus after the points went up."""
+def preprocess_device(points, device="cuda", bits=10):
+    """octree_partition + build_grids on the device: integer points [P,3] (numpy or tensor, coordinates of `bits` bits,
+    duplicates allowed) -> DevicePreprocess.  The host reads one 64-byte record (N, the count of rejected points, the
+    list sizes); nothing that scales with P or with the voxels crosses the bus after the points went up.  bits = 10
+    runs the kernels of csrc/pp_device.hip, 11 and 12 those of csrc/pp_deep.hip."""
+    depth = _depth(bits)
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("preprocess_device runs on the HIP device only; there is no CPU fallback")
@@ -273,8 +308,10 @@ def preprocess_device(points, device="cuda"):
         raise ValueError("too many points")
     t = t.to(dev)
     if t.dtype != torch.int32:
-        t = t.to(torch.int64).clamp(-1, ROOT).to(torch.int32)               # out of range stays out of range in 32 bits
+        t = t.to(torch.int64).clamp(-1, 1 << bits).to(torch.int32)          # out of range stays out of range in 32 bits
     t = t.contiguous()
+    if depth > 5:
+        return _preprocess_device_deep(t, dev, bits)
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream().cuda_stream
         i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
@@ -302,3 +339,47 @@ def preprocess_device(points, device="cuda"):
                                   nb_idx.data_ptr(), d2.data_ptr(), n, st), "nvf_nearest_dist2")
         gt, dist = grids_from_d2(d2, in_place=True)
     return DevicePreprocess(origins, blk_off, spts, nb_off, nb_idx, gt, dist, voxels, oct_dev, level_counts)
+
+
+DEEP_WORK_WORDS = 11264         # NVF_PP_DEEP_WORK_WORDS
+DEEP_META = {"levels": 2, "nb": 10, "voxels": 11}        # meta of nvf_pp_tree_deep: [2..9] bytes of level 0..7
+
+
+def _preprocess_device_deep(t, dev, bits):
+    """preprocess_device for 11 and 12 bits per axis: the same steps with int64 sort keys, the bitmap of level D + 1 in
+    global memory and every buffer sized from min(8^L, P) instead of 8^L."""
+    depth, npts = bits - 5, t.shape[0]
+    caps = [min(8 ** lv, npts) for lv in range(depth + 1)]
+    starts = [sum(caps[:lv]) for lv in range(depth + 1)]
+    cap, words = caps[depth], 8 ** depth // 32
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream().cuda_stream
+        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+        keys = torch.empty(npts, dtype=torch.int64, device=dev)
+        bitmap, meta, work = i32(8 * words), i32(META_INTS), i32(DEEP_WORK_WORDS)
+        origins, tab, nb_off, blk_off = i32(cap, 3), i32(2 * words), i32(cap + 1), i32(cap + 1)
+        oct_dev = torch.empty(sum(caps), dtype=torch.uint8, device=dev)
+        spts = i32(npts, 3)
+        L = lib()
+        check(L.nvf_pp_keys_deep(t.data_ptr(), npts, bits, keys.data_ptr(), bitmap.data_ptr(), meta.data_ptr(), st),
+              "nvf_pp_keys_deep")
+        skeys = torch.sort(keys).values                          # plumbing: equal keys are equal points
+        check(L.nvf_pp_tree_deep(bitmap.data_ptr(), bits, npts, origins.data_ptr(), tab.data_ptr(), oct_dev.data_ptr(),
+                                 nb_off.data_ptr(), work.data_ptr(), meta.data_ptr(), st), "nvf_pp_tree_deep")
+        check(L.nvf_pp_blocks_deep(skeys.data_ptr(), npts, bits, tab.data_ptr(), meta.data_ptr(), spts.data_ptr(),
+                                   blk_off.data_ptr(), st), "nvf_pp_blocks_deep")
+        m = meta.cpu().tolist()                                  # the one host sync of the call
+        n, bad, nb_total, voxels = m[0], m[1], m[DEEP_META["nb"]], m[DEEP_META["voxels"]]
+        level_counts = m[DEEP_META["levels"]:DEEP_META["levels"] + depth + 1]
+        if bad:
+            raise ValueError(f"coordinates must lie in [0, {1 << bits}): {bad} points do not")
+        origins, nb_off, blk_off = origins[:n], nb_off[:n + 1], blk_off[:n + 1]
+        nb_idx = i32(nb_total)
+        check(L.nvf_pp_neighbours_deep(origins.data_ptr(), bits, tab.data_ptr(), nb_off.data_ptr(), nb_idx.data_ptr(), n,
+                                       st), "nvf_pp_neighbours_deep")
+        d2 = i32(n, 1, LEAF, LEAF, LEAF)
+        check(L.nvf_nearest_dist2(spts.data_ptr(), blk_off.data_ptr(), origins.data_ptr(), nb_off.data_ptr(),
+                                  nb_idx.data_ptr(), d2.data_ptr(), n, st), "nvf_nearest_dist2")
+        gt, dist = grids_from_d2(d2, in_place=True)
+    return DevicePreprocess(origins, blk_off, spts, nb_off, nb_idx, gt, dist, voxels, oct_dev, level_counts,
+                            level_starts=starts, bits=bits)

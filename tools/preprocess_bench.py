@@ -7,9 +7,12 @@
 
 Wall clock around work that ends in a device synchronise.  (b): --warmup + --calls calls, median [min, max].
 (a) takes tens of seconds a call, so it runs --host-calls times, without warm-up; the device was warmed by then
-when --order device-first (the default).  The clouds are tools/rd_sweep.py's bumpy ellipsoid shells.
+when --order device-first (the default).  The clouds are tools/rd_sweep.py's bumpy ellipsoid shells.  --bits 11 | 12
+shifts them by (2^bits - 1024) / 2 per axis, to the middle of the deeper volume, where they cross its octant planes;
+route (a) is 10-bit only, so only route (b) is timed then.
 
     python tools/preprocess_bench.py                              # the table + one JSON line
+    python tools/preprocess_bench.py --bits 12                    # the deep partition (csrc/pp_deep.hip), route (b) only
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/preprocess_bench.py --device-only --calls 5
     python tools/preprocess_bench.py --kernel-stats OUT/.../*_kernel_stats.csv      # the per-kernel split of (b)
 """
@@ -56,11 +59,11 @@ def files_route(pts, dev, tmp):
     return out
 
 
-def device_route(pts, dev):
+def device_route(pts, dev, bits=10):
     import torch
     from nvfpcc_amd import preprocess as pp
     t0 = time.perf_counter()
-    pre = pp.preprocess_device(pts, dev)
+    pre = pp.preprocess_device(pts, dev, bits=bits)
     torch.cuda.synchronize()
     return time.perf_counter() - t0, pre
 
@@ -83,6 +86,8 @@ def main():
     ap.add_argument("--calls", type=int, default=20)
     ap.add_argument("--host-calls", type=int, default=3)
     ap.add_argument("--device-only", action="store_true", help="route (b) only (the run to put under rocprofv3)")
+    ap.add_argument("--bits", type=int, choices=[10, 11, 12], default=10,
+                    help="bits per axis: above 10 the cloud is shifted to the middle of the volume and only (b) runs")
     ap.add_argument("--kernel-stats", default=None, help="print the split of a rocprofv3 *_kernel_stats.csv and stop")
     args = ap.parse_args()
     if args.kernel_stats:
@@ -92,22 +97,23 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("preprocess_bench needs a HIP device: a time taken anywhere else says nothing")
     dev = torch.device("cuda:0")
-    result = {"tool": "preprocess_bench", "clouds": {}}
+    result = {"tool": "preprocess_bench", "bits": args.bits, "clouds": {}}
+    device_only = args.device_only or args.bits > 10
     for name in args.clouds.split(","):
         radius, n_dir = CLOUDS[name]
-        pts = make_cloud(1, radius, n_dir)
+        pts = make_cloud(1, radius, n_dir) + ((1 << args.bits) - 1024) // 2
         for _ in range(args.warmup):
-            device_route(pts, dev)
+            device_route(pts, dev, args.bits)
         times = []
         for _ in range(args.calls):
-            dt, pre = device_route(pts, dev)
+            dt, pre = device_route(pts, dev, args.bits)
             times.append(dt * 1e3)
         row = {"points": int(len(pts)), "blocks": int(pre.origins.shape[0]), "device_ms": times}
         print(f"[{name}] {len(pts)} points, {pre.origins.shape[0]} leaf blocks", flush=True)
         print(f"  (b) preprocess_device          {med(times)} ms", flush=True)
         del pre
         torch.cuda.empty_cache()
-        if not args.device_only:
+        if not device_only:
             runs = []
             for _ in range(args.host_calls):
                 with tempfile.TemporaryDirectory() as tmp:
