@@ -572,6 +572,9 @@ int nvf_focal_loss_multi(const float* const* ps, const float* const* gts, const 
                          void* stream);
 
 /* metrics (utils/loss.py:74-84, 113-121): out[0..5] (+)= tp, ap, tn, an at thh_acc; sse, denom at thh_sse */
+/* Exactness of the five counts: the per-workgroup partials are float32 and exact while a workgroup sees fewer than 2^24
+ * elements, i.e. up to n = 2^34 per term (1024 workgroups); the final pass adds them in float64 and rounds once, so a
+ * count is the true count rounded to float32 (equal to it below 2^24).  sse: float32 partials, float64 final sum. */
 /* with ctx (an open nvf_finals_begin) the final pass joins the deferred ones: out exists after nvf_finals_flush, and
  * `workspace` must then be a buffer no other deferred pass uses */
 int nvf_metrics(const float* p, const float* gt, const float* dist, float thh_acc, float thh_sse, float* out,

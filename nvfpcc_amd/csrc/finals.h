@@ -197,20 +197,24 @@ __device__ __forceinline__ int stem_gdn_final_body(const StemGdnFinal& f, int p0
   return bad;
 }
 
-// metric partials of term t (rows of 6) -> out[6 t + k], k = tid % 6, in row order (the arithmetic of finalize_partials)
+// metric partials of term t (rows of 6) -> out[6 t + k], k = tid % 6.  The partials are float32 and, for the five counts,
+// exact: a workgroup counts at most n / nwg + 256 elements, below 2^24 up to n = 2^34 at the 1024-workgroup cap.  Their sum
+// is not representable in float32 past 2^24, so it is taken in float64 (exact: every count < 2^53; four accumulators, the
+// order cannot matter) and rounded ONCE on the store: out = the true count rounded to float32.  sse goes the same way.
 __device__ __forceinline__ void metrics_final_body(const float* __restrict__ part, float* __restrict__ out,
                                                    const int32_t* nwg, int nterm, int accumulate, int tid) {
   if (tid >= 6 * nterm) return;
   const int t = tid / 6, k = tid - 6 * t;
-  float s = 0.f;
-  for (int g0 = 0; g0 < nwg[t]; g0 += 16) {        // 16 loads in flight, added in ascending row order
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int g0 = 0; g0 < nwg[t]; g0 += 16) {        // 16 loads in flight
     float v[16];
 #pragma unroll
     for (int i = 0; i < 16; ++i) v[i] = g0 + i < nwg[t] ? part[((size_t)t * kLossMaxWG + g0 + i) * 6 + k] : 0.f;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) s += v[i];
+    for (int i = 0; i < 16; ++i) s[i & 3] += (double)v[i];
   }
-  out[tid] = accumulate ? out[tid] + s : s;
+  const double tot = (s[0] + s[1]) + (s[2] + s[3]);
+  out[tid] = (float)(accumulate ? (double)out[tid] + tot : tot);
 }
 
 // Everything one finals launch needs (at most one job of each kind)
@@ -230,7 +234,7 @@ struct FinalsArgs {
   float r_ghost;
   StemGdnFinal g;
   const float* m_part;   // metrics (nvf_metrics / nvf_metrics3): per term t, m_nwg[t] rows of 6 partial sums at row
-  float* m_out;          // t * kLossMaxWG, summed in row order into m_out[6 t .. 6 t + 5]
+  float* m_out;          // t * kLossMaxWG, summed in float64 into m_out[6 t .. 6 t + 5]
   int32_t m_nwg[3], m_nterm, m_accumulate;
   int32_t f_nterm, has_f, has_s, has_r, has_g, has_m;
   const float* hb_part;  // the heads' bias gradients (nvf_heads3_loss_bwd_data_bias): head h = the sum of its logit
