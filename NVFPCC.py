@@ -301,9 +301,6 @@ def decode(args):
     else:
         n = int(args.N)
         origins = total_pack['origins'][:n]
-    if args.ref_ply is not None and n and int(np.max(origins)) >= 1024:
-        raise SystemExit("--ref_ply: this pack holds a cloud of more than 10 bits per axis; the D1 / D2 metrics "
-                         "(nvfpcc_amd.pc_metrics) stop at 10")
     print('Start to reconstruct')
     thh, block_counts, used = args.thh, None, []
     side = total_pack.get('thh_pack')
@@ -323,16 +320,29 @@ def decode(args):
     if block_counts is not None:
         print(ts.threshold_line('block-count', block_counts=block_counts, thresholds=torch.cat(used).cpu().numpy()))
     write_ply_ascii('rc_dec.ply', pts)
-    _print_pc_error(args, pts, dev)
+    _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10)
 
 
-def _print_pc_error(args, pts, dev):
-    """--ref_ply: symmetric D1 / D2 geometry PSNR of the written cloud against the original (nvfpcc_amd.pc_metrics)."""
+def _pack_bits(total_pack, origins):
+    """Bits per axis of the cloud a pack holds: octree_pack's header byte (the leaf level D) + 5, or for raw origins
+    the smallest of 10 / 11 / 12 whose volume holds every 32^3 leaf cube."""
+    if 'octree_pack' in total_pack:
+        return int(total_pack['octree_pack'][0]) + 5
+    top = int(np.max(origins)) + 31 if len(origins) else 0
+    for bits in (10, 11, 12):
+        if top < (1 << bits):
+            return bits
+    raise SystemExit(f"--ref_ply: the pack's leaf cubes reach coordinate {top}, beyond 12 bits per axis")
+
+
+def _print_pc_error(args, pts, dev, bits=10):
+    """--ref_ply: symmetric D1 / D2 geometry PSNR of the written cloud against the original (nvfpcc_amd.pc_metrics);
+    `bits` is the domain of both clouds, and the peak of the PSNR is 2^bits - 1."""
     if args.ref_ply is None:
         return
     from nvfpcc_amd.pc_metrics import geometry_psnr, read_ply_points
     ref, ref_normals = read_ply_points(args.ref_ply)
-    r = geometry_psnr(ref, pts, ref_normals=ref_normals, device=dev)
+    r = geometry_psnr(ref, pts, ref_normals=ref_normals, device=dev, bits=bits)
     print('[PCError] D1 PSNR: %.4f D2 PSNR: %.4f' % (r['d1_psnr'], r['d2_psnr']))
 
 

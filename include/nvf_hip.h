@@ -770,6 +770,45 @@ int nvf_pc_error_sums(const int32_t* query_xyz, int n_query, const int32_t* targ
                       const float* normals, int normals_of_target, int64_t* sums, double* d2_sum, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ---- point-cloud metrics, sparse index: the same searches for clouds of 10, 11 and 12 bits per axis (csrc/pc_sparse.hip)
+ * Coordinates lie in [0, 2^bits) (the caller checks the range).  Memory follows the points and the occupied cells, not
+ * the volume.  Cells are 8 voxels, super-cells 64, hyper-cells 512; with c = p >> 3, s = p >> 6, h = p >> 9 per axis and
+ * hb = bits - 9 the cell key nests the levels:
+ *   key = (h.x << 2 hb | h.y << hb | h.z) << 18 | ((s.x & 7) << 6 | (s.y & 7) << 3 | (s.z & 7)) << 9
+ *       | (c.x & 7) << 6 | (c.y & 7) << 3 | (c.z & 7)                                     (at most 27 bits)
+ * so the points of a node of any level are one contiguous range of the SORTED CLOUD (int32 [n, 4] rows (x, y, z, input
+ * index) ordered by key; the order inside a cell is free).  With M occupied cells and S occupied super-cells, both
+ * numbered in key order:
+ *   cell_start   int32 [M + 1]   exclusive prefix sum of the points per occupied cell.
+ *   super_mask   uint64 [S, 8]   512-bit occupancy of the super-cell's cells: word = c.x & 7, bit = (c.y & 7) << 3 | c.z & 7.
+ *   super_first  int32 [S]       number of the super-cell's first occupied cell; the cell of bit b of word w is number
+ *                                super_first + popcount(words below w) + popcount(word w below bit b).
+ *   super_table  int32 [NVF_PC_SPARSE_SUPERS(bits)]  at key >> 9: the super-cell's number, or -1 when it is empty.
+ *   hyper_table  int32 [NVF_PC_SPARSE_HYPERS(bits)]  at key >> 18: 1 when the hyper-cell holds a point, else 0.
+ * nvf_pc_sparse_build fills super_mask, super_first and both tables of `index` (whose sorted, cell_start, sizes and bits
+ *   the caller has set) from cell_key int32 [M], the keys of the occupied cells ascending, and cell_super int32 [M],
+ *   the number of each cell's super-cell.  Integer ORs and owner-written rows: the same bits on every call.
+ * nvf_pc_nearest_sparse / nvf_pc_knn_normals_sparse: nvf_pc_nearest / nvf_pc_knn_normals on that index, the same
+ *   definitions and the same answers (query_sorted is sorted by the same key).  d2 <= 3 * 4095^2 < 2^31.
+ * A NULL pointer (knn_idx excepted), bits outside 10..12, sizes that contradict each other, k outside 3..32 or n < k give
+ *   NVF_EINVAL before any device work.  nvf_pc_error_sums serves every bits unchanged. */
+#define NVF_PC_SPARSE_SUPERS(bits) (1 << (3 * ((bits) - 6)))
+#define NVF_PC_SPARSE_HYPERS(bits) (1 << (3 * ((bits) - 9)))
+typedef struct NvfPcSparseIndex {
+  int32_t* sorted;
+  int32_t* cell_start;
+  uint64_t* super_mask;
+  int32_t* super_first;
+  int32_t* super_table;
+  int32_t* hyper_table;
+  int32_t n, n_cells, n_supers, bits;
+} NvfPcSparseIndex;
+int nvf_pc_sparse_build(const NvfPcSparseIndex* index, const int32_t* cell_key, const int32_t* cell_super, void* stream);
+int nvf_pc_nearest_sparse(const int32_t* query_sorted, int n_query, const NvfPcSparseIndex* target, int32_t* nn_idx,
+                          int32_t* nn_d2, void* stream);
+int nvf_pc_knn_normals_sparse(const NvfPcSparseIndex* cloud, const int32_t* cloud_xyz, int k, float* normals,
+                              int32_t* knn_idx, void* stream);
+
 /* ---- occupancy selection (nvfpcc_amd/thh_select.py, csrc/occ_select.hip) -------------------------------------------
  * The sort key of a probability is its bit pattern (monotone for floats >= 0; -0.0 counts as +0.0).  A key above the
  * bits of 1.0f (NaN, a negative value, a value over 1) is an input error: such voxels go into no bin and are counted

@@ -131,6 +131,9 @@ PROTOTYPES = {
     "nvf_pc_nearest": (I, [P, I, P, P, I, P, P, P]),
     "nvf_pc_knn_normals": (I, [P, P, P, I, I, P, P, P]),
     "nvf_pc_error_sums": (I, [P, I, P, P, P, I, P, P, P, Z, P]),
+    "nvf_pc_sparse_build": (I, [P, P, P, P]),
+    "nvf_pc_nearest_sparse": (I, [P, I, P, P, P, P]),
+    "nvf_pc_knn_normals_sparse": (I, [P, P, I, P, P, P]),
     "nvf_occ_hist": (I, [P, I, I, I, I, P, P, P, P, P, P, P, P]),
     "nvf_occ_hist_edges": (I, [P, I, I, P, I, P, P, P, P, P, P, P]),
     "nvf_threshold_count_v": (I, [P, P, P, I, I, P]),
@@ -176,6 +179,12 @@ class NvfAdamFuse(C.Structure):
     _fields_ = [("g_base", P), ("p_base", P), ("m_base", P), ("v_base", P), ("n", L), ("coef_dev", P),
                 ("coef0_host", F), ("coef1_host", F), ("beta1", F), ("beta2", F), ("eps", F), ("reserved", F),
                 ("bad_count", P)]
+
+
+class NvfPcSparseIndex(C.Structure):
+    """include/nvf_hip.h: typedef struct NvfPcSparseIndex."""
+    _fields_ = [(n, P) for n in ("sorted", "cell_start", "super_mask", "super_first", "super_table", "hyper_table")] + \
+               [(n, C.c_int32) for n in ("n", "n_cells", "n_supers", "bits")]
 
 
 _lib = None

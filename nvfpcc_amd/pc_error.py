@@ -1,8 +1,9 @@
 """Geometry PSNR of a test cloud against a reference, printed the way MPEG's pc_error prints it.
 
-    python -m nvfpcc_amd.pc_error REF.ply TEST.ply [--peak 1023] [--knn 12] [--no-d2]
+    python -m nvfpcc_amd.pc_error REF.ply TEST.ply [--bits 10] [--index dense|sparse] [--peak 1023] [--knn 12] [--no-d2]
 
-REF.ply is the original (A), TEST.ply the decoded cloud (B); both ASCII PLY with integer coordinates in [0, 1024).
+REF.ply is the original (A), TEST.ply the decoded cloud (B); both ASCII PLY with integer coordinates in [0, 2^bits),
+bits = 10, 11 or 12.  --peak defaults to 2^bits - 1; --index to the dense cell grid at 10 bits and the sparse one above.
 The normals of A come from REF.ply's nx ny nz when it has them, otherwise from a k-NN PCA (nvfpcc_amd.pc_metrics).
 The exit status is 1 on bad input.
 """
@@ -29,19 +30,30 @@ def _lines(r, d2):
     return out
 
 
-def main(argv=None):
+def build_parser():
     p = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     p.add_argument("ref", help="reference cloud (A), ASCII PLY")
     p.add_argument("test", help="test (decoded) cloud (B), ASCII PLY")
-    p.add_argument("--peak", type=float, default=1023, help="peak value of the PSNR")
+    p.add_argument("--bits", type=int, choices=(10, 11, 12), default=10,
+                   help="bits per axis: coordinates lie in [0, 2^bits)")
+    p.add_argument("--index", choices=("dense", "sparse"), default=None,
+                   help="cell index of the search (default: dense at 10 bits, sparse above; dense is 10-bit only)")
+    p.add_argument("--peak", type=float, default=None, help="peak value of the PSNR (default: 2^bits - 1)")
     p.add_argument("--knn", type=int, default=12, help="neighbours of the PCA normal estimate (3..32)")
     p.add_argument("--no-d2", action="store_true", help="point-to-point only")
-    args = p.parse_args(argv)
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.peak is None:
+        args.peak = (1 << args.bits) - 1
     from nvfpcc_amd.pc_metrics import geometry_psnr, read_ply_points
     try:
         a, na = read_ply_points(args.ref)
         b, _ = read_ply_points(args.test)
-        r = geometry_psnr(a, b, peak=args.peak, ref_normals=na, knn=args.knn, d2=not args.no_d2)
+        r = geometry_psnr(a, b, peak=args.peak, ref_normals=na, knn=args.knn, d2=not args.no_d2, bits=args.bits,
+                          index=args.index)
     except (OSError, ValueError) as e:
         print(f"pc_error: {e}", file=sys.stderr)
         return 1

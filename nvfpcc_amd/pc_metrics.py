@@ -1,12 +1,12 @@
 """Geometry PSNR of a decoded point cloud against its reference: MPEG's D1 (point-to-point) and D2 (point-to-plane),
-as pc_error defines them, on the gfx950 kernels of csrc/pc_metrics.hip (C ABI: include/nvf_hip.h).
+as pc_error defines them, on the gfx950 kernels of csrc/pc_metrics.hip and csrc/pc_sparse.hip (C ABI: include/nvf_hip.h).
 
 Definitions.  A is the reference cloud (the original), B the test cloud (decoded).  Both hold integer coordinates in
-[0, 1024), the codec's domain; anything else (non-integer or out-of-range coordinates, an empty cloud) raises
-ValueError.  Points are taken as given: duplicates are not removed.
+[0, 2^bits), bits = 10 (the default), 11 or 12; anything else (non-integer or out-of-range coordinates, an empty
+cloud) raises ValueError.  Points are taken as given: duplicates are not removed.
 
   nn_Y(p)       the point of Y with the least squared distance to p; ties go to the lowest index in Y's INPUT order.
-                Squared distances are exact int32 (at most 3 * 1023^2 < 2^31).
+                Squared distances are exact int32 (at most 3 * 4095^2 < 2^31).
   D1(X->Y)      mean_i |x_i - nn_Y(x_i)|^2
   D2(X->Y)      mean_i ((nn_Y(x_i) - x_i) . n_X[i])^2     (pc_error's c2p: the error projected on the query's normal)
   normals of A  the PLY's nx ny nz when given, otherwise PCA: the eigenvector of the smallest eigenvalue of the
@@ -15,27 +15,45 @@ ValueError.  Points are taken as given: duplicates are not removed.
                 3 <= k <= 32.
   normals of B  n_B[i] = n_A[nn_A(b_i)] (pc_error averages over the points of A that have b_i as nearest neighbour;
                 this simplified transfer makes D2(B->A) exactly the error projected on the normal at the reference point).
-  symmetric     mse = max(A->B, B->A);  PSNR = 10 log10(3 peak^2 / mse), peak = 1023 by default (the convention of
-                NVFPCC's PSNR1); inf when mse == 0.  Per direction also the Hausdorff value max_i |x_i - nn_Y(x_i)|^2.
+  symmetric     mse = max(A->B, B->A);  PSNR = 10 log10(3 peak^2 / mse), peak = 2^bits - 1 by default (the convention
+                of NVFPCC's PSNR1); inf when mse == 0.  Per direction also the Hausdorff value max_i |x_i - nn_Y(x_i)|^2.
 
 D1 equals pc_error's for clouds without duplicate points.  D2 uses pc_error's formula, but the normals of B are
 transferred in the simplified way above, so D2 is not promised to match pc_error to the bit.
 
+Index.  `index="dense"` buckets a cloud into a dense grid of 8-voxel cells over the 1024^3 volume (10 bits only);
+`index="sparse"` keeps the occupied cells only, under 64- and 512-voxel parents (any bits; its memory follows the
+points, not the volume).  Both give the same answers, bit for bit.  index=None means dense at 10 bits and sparse above.
+
 The search, the normal estimation and the sums run on the GPU; there is no CPU fallback (as for every op, _lib.py).
 """
+import ctypes as C
 import math
 
 import numpy as np
 import torch
 
-from ._lib import lib, check
+from ._lib import lib, check, NvfPcSparseIndex
 
-ROOT = 1024
-CELLS = 128 ** 3           # NVF_PC_CELLS
+ROOT = 1024                # the default domain: bits = 10
+CELLS = 128 ** 3           # NVF_PC_CELLS, the dense index
+BITS = (10, 11, 12)        # bits per axis the metrics reach
 
 
-def _points(a, what):
+def _check_index(bits, index):
+    """-> True for the sparse index; ValueError on a bits / index pair there is no index for."""
+    if bits not in BITS:
+        raise ValueError(f"bits must be one of {BITS}, got {bits}")
+    if index not in (None, "dense", "sparse"):
+        raise ValueError(f"index must be None, 'dense' or 'sparse', got {index!r}")
+    if index == "dense" and bits != 10:
+        raise ValueError(f"index='dense' covers 10 bits per axis only, not {bits}: use index='sparse'")
+    return index == "sparse" or (index is None and bits != 10)
+
+
+def _points(a, what, bits=10):
     """-> int64 [n, 3] numpy, or ValueError."""
+    root = 1 << bits
     a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
     if a.ndim != 2 or a.shape[1] != 3:
         raise ValueError(f"{what}: expected an [n, 3] array of coordinates, got shape {a.shape}")
@@ -46,8 +64,8 @@ def _points(a, what):
     if not np.issubdtype(a.dtype, np.integer):
         if not np.issubdtype(a.dtype, np.floating) or not np.all(np.isfinite(a)) or np.any(a != np.round(a)):
             raise ValueError(f"{what}: coordinates must be integers")
-    if a.min() < 0 or a.max() >= ROOT:
-        raise ValueError(f"{what}: coordinates must lie in [0, {ROOT})")
+    if a.min() < 0 or a.max() >= root:
+        raise ValueError(f"{what}: coordinates must lie in [0, {root})")
     return a.astype(np.int64)
 
 
@@ -69,6 +87,48 @@ class _Cloud:
         self.start[1:] = torch.cumsum(torch.bincount(key.long(), minlength=CELLS), 0)
 
 
+def _key9(v):
+    return ((v[:, 0] & 7) << 6) | ((v[:, 1] & 7) << 3) | (v[:, 2] & 7)
+
+
+class _SparseCloud:
+    """A cloud on the device under the sparse index of include/nvf_hip.h (NvfPcSparseIndex): xyz and the sorted cloud
+    as in _Cloud but in the nested key order, start int32 [M + 1] over the M occupied cells, and for the S occupied
+    super-cells mask int64 [S, 8] (the bits of uint64 words) and first int32 [S]; super_table and hyper_table are dense
+    over the super- and hyper-cells of the 2^bits volume.  The sort and the two run-length scans are torch's, the
+    records and tables are filled by nvf_pc_sparse_build."""
+
+    def __init__(self, points, device, bits):
+        pts = torch.from_numpy(points).to(device=device, dtype=torch.int32)
+        self.n, self.bits = pts.shape[0], bits
+        self.xyz = pts.contiguous()
+        hb = bits - 9
+        h = pts >> 9
+        key = ((((h[:, 0] << (2 * hb)) | (h[:, 1] << hb) | h[:, 2]) << 18) | (_key9(pts >> 6) << 9) | _key9(pts >> 3))
+        skey, order = torch.sort(key, stable=True)
+        ids = torch.arange(self.n, device=device, dtype=torch.int32)
+        self.sorted = torch.cat([pts, ids[:, None]], 1)[order].contiguous()
+        cell_key, counts = torch.unique_consecutive(skey, return_counts=True)
+        supers, cell_super = torch.unique_consecutive(cell_key >> 9, return_inverse=True)
+        m, s = cell_key.numel(), supers.numel()
+        self.start = torch.zeros(m + 1, dtype=torch.int32, device=device)
+        self.start[1:] = torch.cumsum(counts, 0)
+        self.mask = torch.empty((s, 8), dtype=torch.int64, device=device)
+        self.first = torch.empty(s, dtype=torch.int32, device=device)
+        self.super_table = torch.empty(1 << (3 * (bits - 6)), dtype=torch.int32, device=device)
+        self.hyper_table = torch.empty(1 << (3 * hb), dtype=torch.int32, device=device)
+        self.index = NvfPcSparseIndex(self.sorted.data_ptr(), self.start.data_ptr(), self.mask.data_ptr(),
+                                      self.first.data_ptr(), self.super_table.data_ptr(), self.hyper_table.data_ptr(),
+                                      self.n, m, s, bits)
+        check(lib().nvf_pc_sparse_build(C.byref(self.index), cell_key.to(torch.int32).contiguous().data_ptr(),
+                                        cell_super.to(torch.int32).contiguous().data_ptr(), _stream()),
+              "nvf_pc_sparse_build")
+
+
+def _cloud(points, device, bits, sparse):
+    return _SparseCloud(points, device, bits) if sparse else _Cloud(points, device)
+
+
 def _device(device):
     dev = torch.device(device)
     if dev.type != "cuda" or not torch.cuda.is_available():
@@ -84,6 +144,10 @@ def _nearest(q, t):
     """(input index int32 [q.n], d2 int32 [q.n]) of nn_t for every point of q, on the device."""
     idx = torch.empty(q.n, dtype=torch.int32, device=q.xyz.device)
     d2 = torch.empty_like(idx)
+    if isinstance(t, _SparseCloud):
+        check(lib().nvf_pc_nearest_sparse(q.sorted.data_ptr(), q.n, C.byref(t.index), idx.data_ptr(), d2.data_ptr(),
+                                          _stream()), "nvf_pc_nearest_sparse")
+        return idx, d2
     check(lib().nvf_pc_nearest(q.sorted.data_ptr(), q.n, t.sorted.data_ptr(), t.start.data_ptr(), t.n,
                                idx.data_ptr(), d2.data_ptr(), _stream()), "nvf_pc_nearest")
     return idx, d2
@@ -99,6 +163,11 @@ def _check_knn(k, n):
 def _normals(c, k, want_knn=False):
     nrm = torch.empty((c.n, 3), dtype=torch.float32, device=c.xyz.device)
     knn = torch.empty((c.n, k), dtype=torch.int32, device=c.xyz.device) if want_knn else None
+    if isinstance(c, _SparseCloud):
+        check(lib().nvf_pc_knn_normals_sparse(C.byref(c.index), c.xyz.data_ptr(), int(k), nrm.data_ptr(),
+                                              None if knn is None else knn.data_ptr(), _stream()),
+              "nvf_pc_knn_normals_sparse")
+        return nrm, knn
     check(lib().nvf_pc_knn_normals(c.sorted.data_ptr(), c.start.data_ptr(), c.xyz.data_ptr(), c.n, int(k),
                                    nrm.data_ptr(), None if knn is None else knn.data_ptr(), _stream()),
           "nvf_pc_knn_normals")
@@ -123,30 +192,36 @@ def psnr(mse, peak=1023.0):
     return math.inf if mse == 0 else 10.0 * math.log10(3.0 * peak * peak / mse)
 
 
-def nearest(query, target, device="cuda"):
+def nearest(query, target, device="cuda", bits=10, index=None):
     """(input index of nn_target, squared distance) for every query point: int64 numpy arrays [n_query]."""
-    query, target = _points(query, "query"), _points(target, "target")
+    sparse = _check_index(bits, index)
+    query, target = _points(query, "query", bits), _points(target, "target", bits)
     dev = _device(device)
-    idx, d2 = _nearest(_Cloud(query, dev), _Cloud(target, dev))
+    idx, d2 = _nearest(_cloud(query, dev, bits, sparse), _cloud(target, dev, bits, sparse))
     return idx.cpu().numpy().astype(np.int64), d2.cpu().numpy().astype(np.int64)
 
 
-def estimate_normals(points, k=12, device="cuda", return_knn=False):
+def estimate_normals(points, k=12, device="cuda", return_knn=False, bits=10, index=None):
     """PCA unit normals float32 [n, 3] of the cloud (and, with return_knn, its k-NN sets int64 [n, k])."""
-    points = _points(points, "points")
+    sparse = _check_index(bits, index)
+    points = _points(points, "points", bits)
     _check_knn(k, points.shape[0])
     dev = _device(device)
-    nrm, knn = _normals(_Cloud(points, dev), int(k), return_knn)
+    nrm, knn = _normals(_cloud(points, dev, bits, sparse), int(k), return_knn)
     return (nrm.cpu().numpy(), knn.cpu().numpy().astype(np.int64)) if return_knn else nrm.cpu().numpy()
 
 
-def geometry_psnr(ref, test, peak=1023, ref_normals=None, knn=12, d2=True, device="cuda"):
+def geometry_psnr(ref, test, peak=None, ref_normals=None, knn=12, d2=True, device="cuda", bits=10, index=None):
     """D1 / D2 geometry PSNR of `test` (B) against `ref` (A); see the module docstring for the definitions.
+    Coordinates lie in [0, 2^bits); peak=None means 2^bits - 1.
 
     Returns {"d1_mse", "d1_psnr", "d2_mse", "d2_psnr", "hausdorff_d2", "n_ref", "n_test"} for the symmetric values,
     plus the same keys (without the counts) under "ref_to_test" (A->B, pc_error's mse1) and "test_to_ref" (B->A,
     mse2).  With d2=False the D2 entries are None and no normals are computed."""
-    ref, test = _points(ref, "ref"), _points(test, "test")
+    sparse = _check_index(bits, index)
+    ref, test = _points(ref, "ref", bits), _points(test, "test", bits)
+    if peak is None:
+        peak = (1 << bits) - 1
     if not float(peak) > 0 or not math.isfinite(float(peak)):
         raise ValueError(f"peak must be positive, got {peak}")
     n = None
@@ -157,7 +232,7 @@ def geometry_psnr(ref, test, peak=1023, ref_normals=None, knn=12, d2=True, devic
     elif d2:
         _check_knn(knn, ref.shape[0])
     dev = _device(device)
-    A, B = _Cloud(ref, dev), _Cloud(test, dev)
+    A, B = _cloud(ref, dev, bits, sparse), _cloud(test, dev, bits, sparse)
     nA = None
     if d2:
         nA = torch.from_numpy(np.ascontiguousarray(n)).to(dev) if n is not None else _normals(A, int(knn))[0]
