@@ -15,8 +15,10 @@ engine (nvfpcc_amd/engine.py) instead of a DataLoader + autograd loop.
     python NVFPCC.py train cloud.ply --from_ply ...                            # no get_octree / util_get_grids run, no .npy
     python NVFPCC.py encode cloud.ply --from_ply --pack_octree ...             # leaves travel as octree bytes; decode needs no --N
     python NVFPCC.py train cloud_vox11.ply --from_ply --bits 11 ...            # 11 or 12 bits per axis (--from_ply only)
+    python NVFPCC.py encode ... --pack_lod --lod_heads ckpts/0500.ckpt         # the coarse heads travel in the pack (lod_pack)
+    python NVFPCC.py decode pack.pk --lod 1 ...                                # half resolution: the trunk stops at the 16^3 head
 
-Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --bits, --pack_octree, --thh_mode (count | block-count | d1:
+Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --thh_mode (count | block-count | d1:
 nvfpcc_amd/thh_select.py picks the occupancy threshold at encode time and a `thh_pack` key carries it); multi-GPU training when launched
 through torch.distributed.run (one process per GPU, leaf blocks sharded, one RCCL all-reduce per step).
 Headless: no GUI window, no IPython shell.
@@ -224,6 +226,10 @@ def encode(args):
         sel = _select_threshold(args.thh_mode, net, info['quantized_latent'].detach(), data, np_origins, dev, batch)
         thh = sel['t']
         total_pack['thh_pack'] = sel['pack']
+    lod = None
+    if getattr(args, 'pack_lod', False):    # the two coarse heads and their thresholds travel too: decode --lod 1 | 2
+        lod = _encode_lod(args, net, info['quantized_latent'].detach(), data, np_origins, dev, batch)
+        total_pack['lod_pack'] = lod['pack']
     with open(args.pack_fn, 'wb') as f:
         pickle.dump(total_pack, f)
     print('Start to reconstruct')
@@ -241,6 +247,7 @@ def encode(args):
         m = ops.metrics(out, gt, dist, thh, thh).cpu().numpy()
     latent_bits = len(latent_pack['latent_byte_stream']) * 8
     side_bits = (0 if sel is None else 8 * len(sel['pack'])) + 8 * len(total_pack.get('octree_pack', b''))
+    side_bits += 8 * len(total_pack.get('lod_pack', b''))
     if sel is not None:
         print(sel['line'])
     print('[Latent code] Gross bpp: %.4f' % ((latent_bits + net_bits + side_bits) / data.N))
@@ -248,6 +255,45 @@ def encode(args):
         m[0] / max(m[1], 1), m[2] / max(m[3], 1), *_psnr1(m[4], m[5], (1 << bits) - 1)))
     write_ply_ascii('rc_enc.ply', pts)
     _print_pc_error(args, pts, dev)
+    if lod is not None:
+        for level, (line, lod_pts) in enumerate(zip(lod['lines'], lod['points']), 1):
+            print(line)
+            write_ply_ascii('rc_enc_lod%d.ply' % level, lod_pts)
+
+
+def _encode_lod(args, net, latents, data, origins, dev, batch):
+    """encode --pack_lod: the coarse heads (conv1_cls = level 1, conv0_cls = level 2) rounded to float16 in `net`, the
+    threshold of each level chosen by count against the max-pooled ground truth, and the level's cloud through
+    ops.head_points.  -> {'pack': lod_pack bytes, 'lines': the two [LoD l] lines, 'points': the two clouds}."""
+    from nvfpcc_amd import lod_pack as lp, ops, thh_select as ts
+    from nvfpcc_amd.recon import reconstruct_points_lod
+    src = getattr(args, 'lod_heads', None) or args.load_weights
+    try:
+        heads = lp.head_tensors(torch.load(src, map_location='cpu'))
+    except KeyError as e:
+        raise SystemExit(f"encode --pack_lod: {src} holds no {e.args[0]} (manipulate_weights.py drops the coarse heads); "
+                         f"name the checkpoint that training wrote with --lod_heads")
+    c1, c2 = lp.head_channels(args.chanstr)
+    if heads[lp.HEAD_KEYS[0]].shape != (1, c1, 3, 3, 3) or heads[lp.HEAD_KEYS[2]].shape != (1, c2, 3, 3, 3):
+        raise SystemExit(f"encode --pack_lod: the coarse heads of {src} do not fit --chanstr {args.chanstr}")
+    net.load_state_dict(heads, strict=False)
+    rounded = lp.round_heads_(net)          # before anything is evaluated at a coarse level: the decoder's numbers
+    g, _ = data.to_device(dev)
+    out = {'t': [], 'lines': [], 'points': []}
+    for level in (1, 2):
+        g = ops.maxpool2(g.contiguous())
+        k = int((g != 0).sum().item())      # occupied coarse voxels of the input
+        with torch.no_grad():
+            p = torch.cat([net.reconstruct_lod(latents[i:i + batch].contiguous(), level, 2, return_p=True)[1]
+                           for i in range(0, latents.shape[0], batch)], 0)
+        t = float(ts.threshold_for_count(p, k).item())
+        m = ops.metrics(p, g, None, t, t).cpu().numpy()
+        pts, _ = reconstruct_points_lod(net, latents, origins, level, t, batch=batch)
+        out['t'].append(t)
+        out['lines'].append(lp.lod_line(level, t, pts.shape[0], m[0] / max(m[1], 1), m[2] / max(m[3], 1)))
+        out['points'].append(pts)
+    out['pack'] = lp.write_lod_pack(out['t'][0], out['t'][1], *[rounded[k] for k in lp.HEAD_KEYS])
+    return out
 
 
 def _select_threshold(mode, net, latents, data, origins, dev, batch):
@@ -284,6 +330,15 @@ def decode(args):
     net = _build_net(args, torch.device('cpu'))
     with open(args.input, 'rb') as f:
         total_pack = pickle.load(f)
+    lod, lod_side = getattr(args, 'lod', 0), None
+    if lod:
+        from nvfpcc_amd import lod_pack as lp
+        if 'lod_pack' not in total_pack:
+            raise SystemExit(f"decode --lod {lod}: {args.input} carries no lod_pack (it was encoded without --pack_lod)")
+        try:
+            lod_side = lp.read_lod_pack(total_pack['lod_pack'], args.chanstr)
+        except ValueError as e:
+            raise SystemExit(f"decode --lod {lod}: {e}")
     wp = total_pack['net_weight_pack']
     dec_pool = weight_codec.entropy_decode(wp['bit_stream'], wp['inv_codebook'], wp['element_length'], wp['shape_list'])
     nd_ = {}
@@ -291,6 +346,8 @@ def decode(args):
         nd_[k] = torch.from_numpy(v).float() / args.qp
     for k, v in zip(wp['keys_code_as_is'], wp['as_is_pool']):
         nd_[k] = torch.from_numpy(np.asarray(v)).float()
+    if lod_side is not None:
+        nd_.update(lod_side['state'])
     net.load_state_dict(nd_, strict=False)
     net = net.to(dev)
     latents = latent_codec.arithmetic_dec(total_pack['latent_pack']).to(dev)
@@ -302,6 +359,15 @@ def decode(args):
         n = int(args.N)
         origins = total_pack['origins'][:n]
     print('Start to reconstruct')
+    if lod_side is not None:                # a coarser level of detail: the trunk stops at the level's head
+        from nvfpcc_amd.recon import reconstruct_points_lod
+        t = lod_side['t'][lod - 1]
+        pts, counts = reconstruct_points_lod(net, latents[:n].contiguous(), origins, lod, t,
+                                             batch=max(int(args.batchsize), 1))
+        print(lp.lod_line(lod, t, pts.shape[0]))
+        write_ply_ascii('rc_dec.ply', pts)
+        _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10, lod=lod)
+        return
     thh, block_counts, used = args.thh, None, []
     side = total_pack.get('thh_pack')
     if side is None and args.thh_mode not in (None, 'fixed'):
@@ -335,13 +401,23 @@ def _pack_bits(total_pack, origins):
     raise SystemExit(f"--ref_ply: the pack's leaf cubes reach coordinate {top}, beyond 12 bits per axis")
 
 
-def _print_pc_error(args, pts, dev, bits=10):
+def _print_pc_error(args, pts, dev, bits=10, lod=0):
     """--ref_ply: symmetric D1 / D2 geometry PSNR of the written cloud against the original (nvfpcc_amd.pc_metrics);
-    `bits` is the domain of both clouds, and the peak of the PSNR is 2^bits - 1."""
+    `bits` is the domain of both clouds, and the peak of the PSNR is 2^bits - 1.  lod > 0: `pts` lie on the lattice of
+    bits - lod bits per axis; the original is reduced to it (>> lod, duplicates removed: its normals do not survive,
+    D2 uses estimated ones) and bits - lod is the domain and the peak."""
     if args.ref_ply is None:
         return
     from nvfpcc_amd.pc_metrics import geometry_psnr, read_ply_points
     ref, ref_normals = read_ply_points(args.ref_ply)
+    if lod:
+        from nvfpcc_amd.recon import reduce_to_lattice
+        ref, ref_normals, bits = reduce_to_lattice(ref, lod), None, bits - lod
+        print('[PCError] LoD %d: %d reference points on the %d-bit lattice, peak %d' % (lod, ref.shape[0], bits, (1 << bits) - 1))
+        # the search index covers 10 to 12 bits per axis; a smaller domain fits the 10-bit one, the peak is the lattice's
+        r = geometry_psnr(ref, pts, peak=(1 << bits) - 1, ref_normals=None, device=dev, bits=max(bits, 10))
+        print('[PCError] D1 PSNR: %.4f D2 PSNR: %.4f' % (r['d1_psnr'], r['d2_psnr']))
+        return
     r = geometry_psnr(ref, pts, ref_normals=ref_normals, device=dev, bits=bits)
     print('[PCError] D1 PSNR: %.4f D2 PSNR: %.4f' % (r['d1_psnr'], r['d2_psnr']))
 
@@ -396,6 +472,17 @@ def build_parser():
     p.add_argument('--pack_octree', action='store_true', default=argparse.SUPPRESS,
                    help='encode: carry the leaf cubes in the pack as octree occupancy bytes (octree_pack, counted in '
                         'Gross bpp) instead of raw origins; decode then needs no --N.')
+    p.add_argument('--pack_lod', action='store_true', default=argparse.SUPPRESS,
+                   help='encode: carry the two coarse classifier heads and their thresholds in the pack (lod_pack, '
+                        'counted in Gross bpp), so that decode --lod can stop at a coarser level of detail; also writes '
+                        'rc_enc_lod1.ply / rc_enc_lod2.ply.')
+    p.add_argument('--lod_heads', default=argparse.SUPPRESS,
+                   help='encode --pack_lod: checkpoint that holds the coarse heads conv1_cls / conv0_cls (the one '
+                        'training wrote; manipulate_weights.py drops them).  Absent: --load_weights must hold them.')
+    p.add_argument('--lod', type=int, choices=[1, 2], default=argparse.SUPPRESS,
+                   help='decode: level of detail.  1 = 16^3 per block (half resolution), 2 = 8^3 (quarter); the trunk '
+                        'stops at that level and rc_dec.ply lies on the lattice of bits - lod bits per axis.  Needs a '
+                        'pack encoded with --pack_lod.')
     p.add_argument('--ref_ply', default=None,
                    help='Original cloud (ASCII PLY): encode / decode also print its D1 / D2 geometry PSNR.')
     return p

@@ -832,6 +832,24 @@ int nvf_threshold_count_v(const float* p, const float* thh, int32_t* counts, int
 int nvf_threshold_compact_v(const float* p, const float* thh, const int32_t* offsets, const int32_t* origins,
                             int32_t* coords, int batch, int dim, void* stream);
 
+/* ---- level-of-detail decode (nvfpcc_amd/recon.py: reconstruct_points_lod, csrc/lod_points.hip) ----------------------
+ * A coarse cloud comes from one of the two coarse classifier heads: level 1 = conv1_cls on the 16^3 grid, level 2 =
+ * conv0_cls on the 8^3 grid.
+ * nvf_head_occ_bits: x [batch, c, d^3] (the activation the head reads), w_fwd the head's forward-packed 3^3 weights
+ *   (nvf_pack_conv_weight), bias [1] or NULL; the threshold is thh_v[b] when thh_v (float [batch] on the device) is
+ *   given, else thh.  words uint64 [batch, d^3 / 64]: bit k of word w of a block is set when its voxel 64 w + k (raster
+ *   order z, y, x) has p > t, with p the very float nvf_conv3d_gather (act = NVF_ACT_SIGMOID) stores for that voxel:
+ *   the same fmaf chain and the same sigmoid, never written to memory.  counts int32 [batch] = set bits per block
+ *   (cleared by the call, popcounts added in integers).  (c, d) is (8, 16), (16, 16), (16, 8) or (32, 8); anything
+ *   else is NVF_EINVAL before any device work.
+ * nvf_points_from_bits: words as above, d = 16 or 8; offsets int32 [batch] the exclusive prefix sum of counts; origins
+ *   int32 [batch, 3] (NULL: zeros); points int32 [n, 3] receives (origin >> shift) + (z, y, x) per set bit in (block,
+ *   z, y, x) order, the order of nvf_threshold_compact.  shift = 0..2.  A slot outside [0, n) is not written. */
+int nvf_head_occ_bits(const float* x, const float* w_fwd, const float* bias, float thh, const float* thh_v,
+                      uint64_t* words, int32_t* counts, int batch, int c, int d, void* stream);
+int nvf_points_from_bits(const uint64_t* words, const int32_t* offsets, const int32_t* origins, int32_t* points, int n,
+                         int batch, int d, int shift, void* stream);
+
 /* ---- pre-processing on the device (nvfpcc_amd/preprocess.py: preprocess_device, csrc/pp_device.hip) ----------------
  * From int32 [P,3] points with 10-bit coordinates to everything nvf_nearest_dist2 and the trainer take, without a host
  * pass.  A CELL CODE is the 15-bit Morton code of a level-5 cell (x >> 5, y >> 5, z >> 5), x in the lowest bit of each

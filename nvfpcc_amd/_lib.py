@@ -138,6 +138,8 @@ PROTOTYPES = {
     "nvf_occ_hist_edges": (I, [P, I, I, P, I, P, P, P, P, P, P, P]),
     "nvf_threshold_count_v": (I, [P, P, P, I, I, P]),
     "nvf_threshold_compact_v": (I, [P, P, P, P, P, I, I, P]),
+    "nvf_head_occ_bits": (I, [P, P, P, F, P, P, P, I, I, I, P]),
+    "nvf_points_from_bits": (I, [P, P, P, P, I, I, I, I, P]),
     "nvf_pp_keys": (I, [P, I, P, P, P, P]),
     "nvf_pp_tree": (I, [P, P, P, P, P, P, P]),
     "nvf_pp_blocks": (I, [P, I, P, P, P, P, P]),

@@ -27,6 +27,17 @@ class Net(nn.Module):
         out, _, _ = self.reconstructor(latent, q)
         return out
 
+    def reconstruct_lod(self, latent, lod, q=2, return_p=False):
+        """What the level-`lod` head reads (CompDecoder.forward_lod): the trunk stops there."""
+        return self.reconstructor.forward_lod(latent, q, lod, return_p)
+
+    def lod_head_params(self, lod):
+        """(forward-packed 3^3 weights, bias [1]) of the level's head, as ops.head_points takes them."""
+        head = self.reconstructor.lod_head(lod)
+        with torch.no_grad():
+            w, b = head._effective(0)
+            return ops.pack_conv_weight(w.contiguous(), want_bwd=False)[0], b.contiguous()
+
     def get_network_bits(self):
         return self.entropy_coder.get_bits() + self.reconstructor.get_bits()
 

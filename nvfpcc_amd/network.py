@@ -252,6 +252,28 @@ class CompDecoder(nn.Module):
         net_bits = torch.stack([self.likelihood_model(p) for p in self.get_q_params()])
         return out, [cls0, cls1, out], net_bits
 
+    @torch.no_grad()
+    def forward_lod(self, x, q, lod, return_p=False):
+        """The trunk up to the activation a coarse head reads, and no further: lod 1 stops after conv1 ([B, c2, 16^3],
+        read by conv1_cls), lod 2 after conv0 ([B, c1, 8^3], read by conv0_cls).  Same modules, same kernels and the
+        same bits as forward(x, q) computes on its way; an evaluation path (q = 0 or 2: no weight noise, no gradient).
+        return_p: also the head's probabilities [B, 1, D^3], equal to forward(x, q)[1][2 - lod]."""
+        if lod not in (1, 2):
+            raise ValueError(f"lod must be 1 or 2, got {lod!r}")
+        if q not in (0, 2):
+            raise ValueError("forward_lod is an evaluation path: q must be 0 or 2")
+        R = NF.ACT_RELU
+        t = self.activation(self.up0(x, q))
+        t = self.conv0(t, q, R)
+        if lod == 1:
+            t = self.conv1(self.up1(t, q, R), q, R)
+        if not return_p:
+            return t
+        return t, self.lod_head(lod)(t, NF.ACT_SIGMOID)
+
+    def lod_head(self, lod):
+        return self.conv1_cls if lod == 1 else self.conv0_cls
+
     def get_q_params(self):
         return [getattr(self, n).kernel for n in self._order[:7]]
 

@@ -1286,6 +1286,71 @@ def threshold_points(p, thh, origins=None):
     return coords[:total], counts
 
 
+# ---------------------------------------------------------------- level-of-detail decode (csrc/lod_points.hip)
+HEAD_OCC_SHAPES = ((8, 16), (16, 16), (16, 8), (32, 8))      # (channels, grid) nvf_head_occ_bits is instantiated for
+
+
+def head_occ_bits(x, w_fwd, bias, thh):
+    """x [B,C,D,D,D] (what a coarse head reads), the head's forward-packed weights and bias -> (words int64 [B, D^3/64]
+    holding the uint64 occupancy words: bit k of word w = voxel 64 w + k in raster order has p > thh; counts int32 [B]).
+    thh: a float, or a float32 tensor [B] on the device.  p is never stored."""
+    _f32(x, w_fwd, bias)
+    B, c, d = x.shape[0], x.shape[1], x.shape[-1]
+    per_block = isinstance(thh, torch.Tensor)
+    if per_block:
+        _f32(thh)
+        if thh.shape != (B,):
+            raise RuntimeError(f"per-block thresholds must have shape ({B},), got {tuple(thh.shape)}")
+    if (c, d) not in HEAD_OCC_SHAPES or x.shape[2:] != (d, d, d) or w_fwd.numel() != 27 * c:
+        raise RuntimeError(f"nvf_head_occ_bits has no kernel for {c} channels on a {tuple(x.shape[2:])} grid")
+    words = torch.empty((B, d ** 3 // 64), dtype=torch.int64, device=x.device)
+    counts = torch.empty(B, dtype=torch.int32, device=x.device)
+    check(lib().nvf_head_occ_bits(_ptr(x), _ptr(w_fwd), _ptr(bias), 0.0 if per_block else float(thh),
+                                  _ptr(thh) if per_block else None, _ptr(words), _ptr(counts), B, c, d, _stream()),
+          "nvf_head_occ_bits")
+    return words, counts
+
+
+def points_from_bits(words, counts, origins, d, shift):
+    """Occupancy words [B, d^3/64] + counts int32 [B] -> int32 [n,3] points (origin >> shift) + (z,y,x) in (b,z,y,x)
+    raster order.  origins int32 [B,3] or None."""
+    _chk(words, counts, origins)
+    B = words.shape[0]
+    if words.dtype != torch.int64 or words.shape != (B, d ** 3 // 64) or counts.dtype != torch.int32 or counts.shape != (B,):
+        raise RuntimeError("points_from_bits: words must be int64 [B, d^3/64] and counts int32 [B]")
+    offsets = (torch.cumsum(counts, 0, dtype=torch.int32) - counts).contiguous()
+    total = int(counts.sum().item())
+    points = torch.empty((max(total, 1), 3), dtype=torch.int32, device=words.device)
+    if origins is not None and (origins.dtype != torch.int32 or origins.shape != (B, 3)):
+        raise RuntimeError("points_from_bits: origins must be int32 [B, 3]")
+    check(lib().nvf_points_from_bits(_ptr(words), _ptr(offsets), _ptr(origins), _ptr(points), total, B, int(d),
+                                     int(shift), _stream()), "nvf_points_from_bits")
+    return points[:total]
+
+
+def head_points(x, w_fwd, bias, thh, origins, lod):
+    """The points of a coarse level straight from the activation its head reads: x [B,C,D,D,D], the head's
+    forward-packed weights and bias, thh a float or a float32 tensor [B], origins int [B,3] of the 32^3 blocks (or
+    None), lod = 1 (D = 16) or 2 (D = 8).  -> (int32 [n,3] points (origin >> lod) + (z,y,x) in (b,z,y,x) raster order,
+    int32 counts [B]): what threshold_points(p, thh, origins >> lod) gives for the head's p, bit for bit.
+
+    The decoders' own shapes (HEAD_OCC_SHAPES) take the fused kernels (nvf_head_occ_bits + nvf_points_from_bits, p
+    never stored); any other channel count runs the head through nvf_conv3d_gather and threshold_points."""
+    _f32(x, w_fwd, bias)
+    if lod not in (1, 2):
+        raise RuntimeError(f"lod must be 1 or 2, got {lod!r}")
+    B, c, d = x.shape[0], x.shape[1], x.shape[-1]
+    if d != 32 >> lod or x.shape[2:] != (d, d, d):
+        raise RuntimeError(f"level {lod} reads a {32 >> lod}^3 grid, got {tuple(x.shape[2:])}")
+    if origins is not None:
+        origins = origins.to(device=x.device, dtype=torch.int32).contiguous()
+    if (c, d) in HEAD_OCC_SHAPES:
+        words, counts = head_occ_bits(x, w_fwd, bias, thh)
+        return points_from_bits(words, counts, origins, d, lod), counts
+    p = conv3d_gather(x, w_fwd, bias, 1, 3, 1, 1, (d, d, d), ACT_SIGMOID)
+    return threshold_points(p, thh, None if origins is None else origins >> lod)
+
+
 def _occ_riders(p, d2, gt, nbins):
     B = p.shape[0]
     _chk(d2, gt)

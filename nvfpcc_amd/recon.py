@@ -45,6 +45,41 @@ def reconstruct_points(net, latents, origins, thh, batch=64, q=2, block_counts=N
     return torch.cat(pts, 0).long().numpy(), torch.cat(counts, 0).numpy()
 
 
+@torch.no_grad()
+def reconstruct_points_lod(net, latents, origins, lod, thh, batch=64, q=2):
+    """reconstruct_points at a coarser level of detail: lod 1 = the 16^3 head (conv1_cls), lod 2 = the 8^3 head
+    (conv0_cls).  The trunk stops at the activation the head reads (Net.reconstruct_lod) and ops.head_points turns it
+    into points on the lattice of `bits - lod` bits per axis: (origins[b] >> lod) + (z, y, x) of the coarse grid, in
+    (block, z, y, x) order.  thh: a float, or a float32 tensor [N] (one per block).
+    -> (int64 [n,3] points, per-block counts)."""
+    dev = latents.device
+    origins = torch.as_tensor(np.asarray(origins)).to(torch.int32)
+    if isinstance(thh, torch.Tensor):
+        thh = thh.to(device=dev, dtype=torch.float32)
+    w_fwd, bias = net.lod_head_params(lod)
+    pts, counts = [], []
+    for lo in range(0, latents.shape[0], batch):
+        hi = min(lo + batch, latents.shape[0])
+        x = net.reconstruct_lod(latents[lo:hi].contiguous(), lod, q)
+        t = thh[lo:hi].contiguous() if isinstance(thh, torch.Tensor) else thh
+        p, c = ops.head_points(x, w_fwd, bias, t, origins[lo:hi].to(dev), lod)
+        pts.append(p.cpu())
+        counts.append(c.cpu())
+    return torch.cat(pts, 0).long().numpy(), torch.cat(counts, 0).numpy()
+
+
+def reduce_to_lattice(points, lod):
+    """A cloud on the lattice of a coarser level: every coordinate >> lod, duplicates removed (rows sorted, as
+    numpy.unique gives them).  Normals and other columns do not survive the reduction: pass the xyz columns."""
+    pts = np.asarray(points)
+    if pts.ndim != 2 or pts.shape[1] != 3:
+        raise ValueError("reduce_to_lattice takes [n, 3] coordinates")
+    pts = np.round(pts).astype(np.int64)
+    if pts.size and pts.min() < 0:
+        raise ValueError("coordinates must not be negative")
+    return np.unique(pts >> int(lod), axis=0)
+
+
 def write_ply_ascii(path, points):
     """ASCII PLY with double x/y/z, the layout open3d writes for write_ascii=True (NVFPCC.py:554, 650)."""
     pts = np.round(np.asarray(points, np.float64))
