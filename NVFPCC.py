@@ -17,8 +17,10 @@ engine (nvfpcc_amd/engine.py) instead of a DataLoader + autograd loop.
     python NVFPCC.py train cloud_vox11.ply --from_ply --bits 11 ...            # 11 or 12 bits per axis (--from_ply only)
     python NVFPCC.py encode ... --pack_lod --lod_heads ckpts/0500.ckpt         # the coarse heads travel in the pack (lod_pack)
     python NVFPCC.py decode pack.pk --lod 1 ...                                # half resolution: the trunk stops at the 16^3 head
+    python NVFPCC.py encode ... --lossless                                     # the true occupancy travels too (lossless_pack)
+    python NVFPCC.py decode pack.pk --lossless ...                             # rc_dec.ply holds exactly the input's voxels
 
-Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --thh_mode (count | block-count | d1:
+Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --thh_mode (count | block-count | d1:
 nvfpcc_amd/thh_select.py picks the occupancy threshold at encode time and a `thh_pack` key carries it); multi-GPU training when launched
 through torch.distributed.run (one process per GPU, leaf blocks sharded, one RCCL all-reduce per step).
 Headless: no GUI window, no IPython shell.
@@ -230,6 +232,10 @@ def encode(args):
     if getattr(args, 'pack_lod', False):    # the two coarse heads and their thresholds travel too: decode --lod 1 | 2
         lod = _encode_lod(args, net, info['quantized_latent'].detach(), data, np_origins, dev, batch)
         total_pack['lod_pack'] = lod['pack']
+    lossless = None
+    if getattr(args, 'lossless', False):    # the true occupancy, coded under the field the pack's own bytes decode to
+        lossless = _encode_lossless(args, total_pack, data, dev, batch)
+        total_pack['lossless_pack'] = lossless['pack']
     with open(args.pack_fn, 'wb') as f:
         pickle.dump(total_pack, f)
     print('Start to reconstruct')
@@ -247,7 +253,7 @@ def encode(args):
         m = ops.metrics(out, gt, dist, thh, thh).cpu().numpy()
     latent_bits = len(latent_pack['latent_byte_stream']) * 8
     side_bits = (0 if sel is None else 8 * len(sel['pack'])) + 8 * len(total_pack.get('octree_pack', b''))
-    side_bits += 8 * len(total_pack.get('lod_pack', b''))
+    side_bits += 8 * len(total_pack.get('lod_pack', b'')) + 8 * len(total_pack.get('lossless_pack', b''))
     if sel is not None:
         print(sel['line'])
     print('[Latent code] Gross bpp: %.4f' % ((latent_bits + net_bits + side_bits) / data.N))
@@ -259,6 +265,30 @@ def encode(args):
         for level, (line, lod_pts) in enumerate(zip(lod['lines'], lod['points']), 1):
             print(line)
             write_ply_ascii('rc_enc_lod%d.ply' % level, lod_pts)
+    if lossless is not None:
+        print(lossless['line'])
+
+
+def _encode_lossless(args, total_pack, data, dev, batch):
+    """encode --lossless: the decoder exactly as decode() rebuilds it from the pack's bytes (_decoder_from_pack), the
+    occupancy of every leaf block coded under its probabilities (nvfpcc_amd.lossless_pack), and the stream decoded again
+    on the device: a pack whose words differ from the input's occupancy is not written.
+    -> {'pack': lossless_pack bytes, 'line': the [Lossless] line}."""
+    import contextlib
+    import io
+    from nvfpcc_amd import lossless_pack as lp
+    with contextlib.redirect_stdout(io.StringIO()):     # the decoder's own progress lines belong to decode
+        net, latents = _decoder_from_pack(args, total_pack, dev)
+    latents = latents[:data.N_leaf].contiguous()
+    gt, _ = data.to_device(dev)
+    try:
+        pack, info = lp.encode_occupancy(net, latents, gt, batch=batch, group=lp.GROUP)
+        words, counts = lp.decode_occupancy(net, latents, pack, batch=batch)
+    except ValueError as e:
+        raise SystemExit(f"encode --lossless: {e}")
+    if not torch.equal(words, info['gt_words']) or int(counts.sum().item()) != int(data.N):
+        raise SystemExit("encode --lossless: the stream does not decode to the input's occupancy; no pack written")
+    return {'pack': pack, 'line': lp.lossless_line(len(pack), data.N, info['ideal_bits'], lp.GROUP)}
 
 
 def _encode_lod(args, net, latents, data, origins, dev, batch):
@@ -326,10 +356,12 @@ def decode(args):
     """Decode from a pack (NVFPCC.py:557-652)."""
     from nvfpcc_amd import weight_codec, latent_codec
     from nvfpcc_amd.recon import reconstruct_points, write_ply_ascii
+    lossless_refusals(args, None)
     dev, rank, world = _device(args)
     net = _build_net(args, torch.device('cpu'))
     with open(args.input, 'rb') as f:
         total_pack = pickle.load(f)
+    lossless_refusals(args, total_pack)
     lod, lod_side = getattr(args, 'lod', 0), None
     if lod:
         from nvfpcc_amd import lod_pack as lp
@@ -339,18 +371,7 @@ def decode(args):
             lod_side = lp.read_lod_pack(total_pack['lod_pack'], args.chanstr)
         except ValueError as e:
             raise SystemExit(f"decode --lod {lod}: {e}")
-    wp = total_pack['net_weight_pack']
-    dec_pool = weight_codec.entropy_decode(wp['bit_stream'], wp['inv_codebook'], wp['element_length'], wp['shape_list'])
-    nd_ = {}
-    for k, v in zip(wp['keys_quantize'], dec_pool):
-        nd_[k] = torch.from_numpy(v).float() / args.qp
-    for k, v in zip(wp['keys_code_as_is'], wp['as_is_pool']):
-        nd_[k] = torch.from_numpy(np.asarray(v)).float()
-    if lod_side is not None:
-        nd_.update(lod_side['state'])
-    net.load_state_dict(nd_, strict=False)
-    net = net.to(dev)
-    latents = latent_codec.arithmetic_dec(total_pack['latent_pack']).to(dev)
+    net, latents = _decoder_from_pack(args, total_pack, dev, net, lod_side)
     if 'octree_pack' in total_pack:         # the leaves and their count come from the pack, not from --N
         from nvfpcc_amd.preprocess import read_octree_pack
         origins = read_octree_pack(total_pack['octree_pack']).astype(np.int16)
@@ -359,6 +380,18 @@ def decode(args):
         n = int(args.N)
         origins = total_pack['origins'][:n]
     print('Start to reconstruct')
+    if getattr(args, 'lossless', False):    # the input's own voxels: the occupancy words decoded under the field
+        from nvfpcc_amd import lossless_pack as lp
+        try:
+            words, counts = lp.decode_occupancy(net, latents[:n].contiguous(), total_pack['lossless_pack'],
+                                                batch=max(int(args.batchsize), 1))
+        except ValueError as e:
+            raise SystemExit(f"decode --lossless: {e}")
+        pts = lp.points_from_words(words, counts, origins)
+        print('[Lossless] points: %d' % pts.shape[0])
+        write_ply_ascii('rc_dec.ply', pts)
+        _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10)
+        return
     if lod_side is not None:                # a coarser level of detail: the trunk stops at the level's head
         from nvfpcc_amd.recon import reconstruct_points_lod
         t = lod_side['t'][lod - 1]
@@ -387,6 +420,39 @@ def decode(args):
         print(ts.threshold_line('block-count', block_counts=block_counts, thresholds=torch.cat(used).cpu().numpy()))
     write_ply_ascii('rc_dec.ply', pts)
     _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10)
+
+
+def _decoder_from_pack(args, total_pack, dev, net=None, lod_side=None):
+    """The decoder and the latents a pack's bytes hold: the de-quantised kernels and the as-is parameters of
+    net_weight_pack (and the coarse heads of a read lod_pack) loaded into `net` (a fresh one when absent), and the
+    latents of latent_pack.  -> (net on dev, latents on dev)."""
+    from nvfpcc_amd import weight_codec, latent_codec
+    if net is None:
+        net = _build_net(args, torch.device('cpu'))
+    wp = total_pack['net_weight_pack']
+    dec_pool = weight_codec.entropy_decode(wp['bit_stream'], wp['inv_codebook'], wp['element_length'], wp['shape_list'])
+    nd_ = {}
+    for k, v in zip(wp['keys_quantize'], dec_pool):
+        nd_[k] = torch.from_numpy(v).float() / args.qp
+    for k, v in zip(wp['keys_code_as_is'], wp['as_is_pool']):
+        nd_[k] = torch.from_numpy(np.asarray(v)).float()
+    if lod_side is not None:
+        nd_.update(lod_side['state'])
+    net.load_state_dict(nd_, strict=False)
+    net = net.to(dev)
+    latents = latent_codec.arithmetic_dec(total_pack['latent_pack']).to(dev)
+    return net, latents
+
+
+def lossless_refusals(args, total_pack):
+    """decode --lossless: what cannot be served exits here with its reason.  total_pack None: the flags alone."""
+    if not getattr(args, 'lossless', False):
+        return
+    if getattr(args, 'lod', 0):
+        raise SystemExit("decode: --lossless and --lod exclude each other: lossless_pack codes the 32^3 occupancy, a "
+                         "coarser level of detail is lossy by construction")
+    if total_pack is not None and 'lossless_pack' not in total_pack:
+        raise SystemExit(f"decode --lossless: {args.input} carries no lossless_pack (it was encoded without --lossless)")
 
 
 def _pack_bits(total_pack, origins):
@@ -483,6 +549,10 @@ def build_parser():
                    help='decode: level of detail.  1 = 16^3 per block (half resolution), 2 = 8^3 (quarter); the trunk '
                         'stops at that level and rc_dec.ply lies on the lattice of bits - lod bits per axis.  Needs a '
                         'pack encoded with --pack_lod.')
+    p.add_argument('--lossless', action='store_true', default=argparse.SUPPRESS,
+                   help='encode: also code the true occupancy of every leaf block under the decoder\'s probabilities '
+                        '(lossless_pack, counted in Gross bpp).  decode: write exactly the input\'s voxels to rc_dec.ply '
+                        'from a pack encoded with it; excludes --lod.')
     p.add_argument('--ref_ply', default=None,
                    help='Original cloud (ASCII PLY): encode / decode also print its D1 / D2 geometry PSNR.')
     return p

@@ -850,6 +850,45 @@ int nvf_head_occ_bits(const float* x, const float* w_fwd, const float* bias, flo
 int nvf_points_from_bits(const uint64_t* words, const int32_t* offsets, const int32_t* origins, int32_t* points, int n,
                          int batch, int d, int shift, void* stream);
 
+/* ---- lossless geometry (nvfpcc_amd/lossless_pack.py, csrc/occ_rans.hip) ---------------------------------------------
+ * The true occupancy of the 32^3 leaf blocks, entropy-coded under the probabilities p of the eval forward.  p and gt
+ * are float [batch, 32768] in raster order (z, y, x); gt non-zero = occupied.
+ * Context of a voxel, from the float32 bits of p alone: side = p > 0.5f; q = side ? 1.0f - p : p; key = bits(q) >> 21;
+ *   idx = clamp((bits(0.5f) >> 21) - key, 0, 127); ctx = 2 idx + side, 256 contexts.  Every bit pattern has a context.
+ * nvf_occ_ctx_hist: cnt[ctx] += voxels, occ[ctx] += occupied voxels (uint64 [256] each), bad[0] += voxels whose p is an
+ *   input error as for nvf_occ_hist (NaN, negative, over 1; -0.0 counts as +0.0): they are in no context and the caller
+ *   raises.  The three accumulate over calls (the caller clears them once); all sums are integers.  voxels <= 2^24.
+ * The coder is binary rANS with 64-bit states in [2^31, 2^63), 32-bit words and 16-bit frequencies: f1 int32 [256] on the
+ *   device is the frequency of "occupied" per context out of 65536 (an entry outside [1, 65535] is pulled inside);
+ *   symbol 1 = (start 0, freq f1), symbol 0 = (start f1, freq 65536 - f1).  A GROUP is `group` consecutive blocks (the
+ *   last one of a call may be shorter), 1 <= group <= NVF_OCC_RANS_MAX_GROUP, coded by one 64-lane wave with 64 states:
+ *   symbol i = b_local * 32768 + raster voxel belongs to lane i % 64 at step i / 64.
+ * nvf_occ_rans_encode: states uint64 [groups, 64] = the final states (the decoder's initial ones); words uint32
+ *   [groups, group * 32768] is the worst-case region of each group, filled from the END of the region of its own blocks:
+ *   group g's words are words[g][nb * 32768 - nwords[g] .. nb * 32768) with nb its number of blocks, in the order the
+ *   decoder reads them; nwords uint32 [groups].  gt_words (may be NULL) uint64 [batch, 512]: the occupancy words of gt,
+ *   bit k of word w = voxel 64 w + k, the format of nvf_head_occ_bits.
+ * nvf_occ_rans_decode: words uint32 [total_words], group g's at words[word_off[g] .. word_off[g] + nwords[g]) (word_off
+ *   int64 [groups], nwords uint32 [groups]).  occ_words uint64 [batch, 512] and counts int32 [batch] (set bits per block)
+ *   are written for every block.  status int32 [groups] is always written: 0, or the OR of NVF_OCC_RANS_PAST_END (a word
+ *   was wanted beyond the group's words, or its range leaves [0, total_words): such reads yield 0 and touch no memory),
+ *   NVF_OCC_RANS_BAD_STATE (a final state is not 2^31) and NVF_OCC_RANS_WORDS_LEFT (words were left over).  No content
+ *   of states, words, word_off or nwords makes the kernel read outside words[0 .. total_words).
+ * nvf_points_from_bits32: nvf_points_from_bits for d = 32 (512 words per block), shift 0. */
+#define NVF_OCC_RANS_MAX_GROUP 1024
+#define NVF_OCC_RANS_PAST_END 1
+#define NVF_OCC_RANS_BAD_STATE 2
+#define NVF_OCC_RANS_WORDS_LEFT 4
+int nvf_occ_ctx_hist(const float* p, const float* gt, int batch, int voxels, uint64_t* cnt, uint64_t* occ, uint64_t* bad,
+                     void* stream);
+int nvf_occ_rans_encode(const float* p, const float* gt, const int32_t* f1, int batch, int group, uint64_t* states,
+                        uint32_t* words, uint32_t* nwords, uint64_t* gt_words, void* stream);
+int nvf_occ_rans_decode(const float* p, const int32_t* f1, const uint64_t* states, const uint32_t* words,
+                        const int64_t* word_off, const uint32_t* nwords, int64_t total_words, int batch, int group,
+                        uint64_t* occ_words, int32_t* counts, int32_t* status, void* stream);
+int nvf_points_from_bits32(const uint64_t* words, const int32_t* offsets, const int32_t* origins, int32_t* points, int n,
+                           int batch, void* stream);
+
 /* ---- pre-processing on the device (nvfpcc_amd/preprocess.py: preprocess_device, csrc/pp_device.hip) ----------------
  * From int32 [P,3] points with 10-bit coordinates to everything nvf_nearest_dist2 and the trainer take, without a host
  * pass.  A CELL CODE is the 15-bit Morton code of a level-5 cell (x >> 5, y >> 5, z >> 5), x in the lowest bit of each

@@ -140,6 +140,10 @@ PROTOTYPES = {
     "nvf_threshold_compact_v": (I, [P, P, P, P, P, I, I, P]),
     "nvf_head_occ_bits": (I, [P, P, P, F, P, P, P, I, I, I, P]),
     "nvf_points_from_bits": (I, [P, P, P, P, I, I, I, I, P]),
+    "nvf_occ_ctx_hist": (I, [P, P, I, I, P, P, P, P]),
+    "nvf_occ_rans_encode": (I, [P, P, P, I, I, P, P, P, P, P]),
+    "nvf_occ_rans_decode": (I, [P, P, P, P, P, P, L, I, I, P, P, P, P]),
+    "nvf_points_from_bits32": (I, [P, P, P, P, I, I, P]),
     "nvf_pp_keys": (I, [P, I, P, P, P, P]),
     "nvf_pp_tree": (I, [P, P, P, P, P, P, P]),
     "nvf_pp_blocks": (I, [P, I, P, P, P, P, P]),

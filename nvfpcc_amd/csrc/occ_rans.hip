@@ -1,0 +1,313 @@
+// Lossless geometry: the true occupancy of every leaf block, entropy-coded under the decoder's own field
+// (nvfpcc_amd/lossless_pack.py).  The eval forward gives a probability p for every voxel on both sides of the pack; a
+// voxel's CONTEXT is a function of the float32 bits of p alone (occ_ctx below), a calibration table sends the measured
+// occupancy rate of each of the 256 contexts as a 16-bit frequency f1, and a binary rANS coder spends about
+// -log2(f / 65536) bits per voxel.
+//
+//   nvf_occ_ctx_hist        per context the voxels and the occupied voxels, exact integers, accumulated over calls
+//   nvf_occ_rans_encode     one 64-lane wave per GROUP of up to G consecutive blocks; symbol i = b_local * 32768 + raster
+//                           voxel belongs to lane i % 64 at step i / 64, so a step reads 64 consecutive voxels.  64
+//                           interleaved 64-bit states (start 2^31, 32-bit words, 16-bit frequencies).  The steps are
+//                           walked BACKWARDS and the words of a step are written downwards from the end of the group's
+//                           region, highest lane first: read forwards they come in the decoder's order.
+//   nvf_occ_rans_decode     the same wave walks forwards; the lanes whose state fell below 2^31 take consecutive words in
+//                           ascending lane order (a ballot and a prefix popcount).  The ballot of the decoded symbols of
+//                           step t IS occupancy word t % 512 of block t / 512, the word format of nvf_head_occ_bits.
+//                           Every word index is checked against the group's word count: a damaged stream sets the group's
+//                           status and reads zeros, it cannot make the kernel read outside its words.
+//   nvf_points_from_bits32  nvf_points_from_bits for the 32^3 grid: 512 words per block, 64 at a time.
+//
+// Only the state recurrence is serial: contexts and frequencies depend on p alone, so each wave fetches OCC_AHEAD steps
+// of p (and of the ground truth) at once and looks their frequencies up in LDS before it enters the chain.
+#include "nvf_common.h"
+
+#define OCC_CTX 256
+#define OCC_VOX 32768                                  // voxels of a 32^3 block
+#define OCC_WPB 512                                    // occupancy words of a block
+#define OCC_AHEAD 8                                    // steps fetched together; divides OCC_WPB
+#define OCC_HIST_THREADS 1024
+#define OCC_PEEL 4
+#define OCC_KEY_ONE 0x3F800000u
+#define OCC_RANS_L (1ull << 31)
+
+namespace {
+
+// the context of a probability, from its bits alone: which side of 0.5, and the exponent + 2 mantissa bits of the
+// distance to the nearer end.  Any bit pattern (NaN, negative, > 1) lands inside [0, 256).
+__device__ __forceinline__ int occ_ctx(float p) {
+  const int side = p > 0.5f ? 1 : 0;
+  const float q = side ? 1.0f - p : p;
+  const int key = (int)(__float_as_uint(q) >> 21);
+  int idx = (int)(0x3F000000u >> 21) - key;
+  idx = idx < 0 ? 0 : (idx > 127 ? 127 : idx);
+  return 2 * idx + side;
+}
+
+__device__ __forceinline__ bool occ_bad(float p) {
+  uint32_t key = __float_as_uint(p);
+  if (key == 0x80000000u) key = 0u;
+  return key > OCC_KEY_ONE;
+}
+
+// x / f and x % f for x < 2^63 and 1 <= f < 2^16, in three 32-bit divisions (long division in base 2^16 below the top)
+__device__ __forceinline__ void occ_divmod(unsigned long long x, uint32_t f, unsigned long long& quot, uint32_t& rem) {
+  const uint32_t hi = (uint32_t)(x >> 32), lo = (uint32_t)x;
+  const uint32_t q1 = hi / f, r1 = hi - q1 * f;
+  const uint32_t n2 = (r1 << 16) | (lo >> 16);         // r1 < f < 2^16
+  const uint32_t q2 = n2 / f, r2 = n2 - q2 * f;        // q2 < 2^16
+  const uint32_t n3 = (r2 << 16) | (lo & 0xFFFFu);
+  const uint32_t q3 = n3 / f;
+  rem = n3 - q3 * f;
+  quot = ((unsigned long long)q1 << 32) | ((unsigned long long)q2 << 16) | q3;
+}
+
+// same-address LDS adds serialise and trained decoders saturate, so a wave peels equal contexts before it adds, as
+// occ_select.hip does for its bins
+__global__ __launch_bounds__(OCC_HIST_THREADS) void occ_ctx_hist_kernel(const float* __restrict__ p,
+                                                                        const float* __restrict__ gt, int voxels,
+                                                                        unsigned long long* __restrict__ cnt,
+                                                                        unsigned long long* __restrict__ occ,
+                                                                        unsigned long long* __restrict__ bad) {
+  __shared__ uint32_t h_cnt[OCC_CTX];
+  __shared__ uint32_t h_occ[OCC_CTX];
+  __shared__ uint32_t h_bad;
+  const int tid = threadIdx.x, lane = tid & 63;
+  if (tid < OCC_CTX) { h_cnt[tid] = 0; h_occ[tid] = 0; }
+  if (tid == 0) h_bad = 0;
+  __syncthreads();
+  const size_t row = (size_t)blockIdx.x * voxels;
+  uint32_t nbad = 0;
+  // every lane of a wave runs the same number of rounds: the ballots below need the whole wave
+  for (int base = 0; base < voxels; base += OCC_HIST_THREADS) {
+    const int i = base + tid;
+    bool live = i < voxels;
+    const float v = live ? p[row + i] : 0.f;
+    const bool hit = live && gt[row + i] != 0.f;
+    if (live && occ_bad(v)) { ++nbad; live = false; }
+    const int c = occ_ctx(v);
+#pragma unroll 1
+    for (int round = 0; round < OCC_PEEL; ++round) {
+      const unsigned long long alive = __ballot(live);
+      if (alive == 0ull) break;
+      const int first = __ffsll((long long)alive) - 1;
+      const int lead = __shfl(c, first, 64);
+      const bool mine = live && c == lead;
+      const int n = __popcll(__ballot(mine));
+      if (n == 1) break;                               // nothing to aggregate: leave it to the plain adds
+      const int nocc = __popcll(__ballot(mine && hit));
+      if (lane == first) {
+        atomicAdd(&h_cnt[lead], (uint32_t)n);
+        if (nocc) atomicAdd(&h_occ[lead], (uint32_t)nocc);
+      }
+      if (mine) live = false;
+    }
+    if (live) {
+      atomicAdd(&h_cnt[c], 1u);
+      if (hit) atomicAdd(&h_occ[c], 1u);
+    }
+  }
+  if (nbad) atomicAdd(&h_bad, nbad);
+  __syncthreads();
+  // integers: any order of these adds gives the same totals
+  if (tid < OCC_CTX) {
+    if (h_cnt[tid]) atomicAdd(cnt + tid, (unsigned long long)h_cnt[tid]);
+    if (h_occ[tid]) atomicAdd(occ + tid, (unsigned long long)h_occ[tid]);
+  }
+  if (tid == 0 && h_bad) atomicAdd(bad, (unsigned long long)h_bad);
+}
+
+// the table in LDS, an entry outside [1, 65535] pulled inside: no frequency is ever 0
+__device__ __forceinline__ void occ_load_table(const int32_t* __restrict__ f1, uint32_t* tab, int lane) {
+#pragma unroll
+  for (int i = lane; i < OCC_CTX; i += 64) {
+    const int v = f1[i];
+    tab[i] = (uint32_t)(v < 1 ? 1 : (v > 65535 ? 65535 : v));
+  }
+  __syncthreads();
+}
+
+// one wave per group
+__global__ __launch_bounds__(64) void occ_rans_encode_kernel(const float* __restrict__ p, const float* __restrict__ gt,
+                                                             const int32_t* __restrict__ f1, int batch, int G,
+                                                             unsigned long long* __restrict__ states,
+                                                             uint32_t* __restrict__ words, uint32_t* __restrict__ nwords,
+                                                             unsigned long long* __restrict__ gt_words) {
+  __shared__ uint32_t tab[OCC_CTX];
+  const int lane = threadIdx.x, g = blockIdx.x;
+  occ_load_table(f1, tab, lane);
+  const int b0 = g * G, nb = min(G, batch - b0);
+  const int steps = nb * OCC_WPB;
+  const int region = nb * OCC_VOX;                     // a symbol emits one word at the most
+  const float* pg = p + (size_t)b0 * OCC_VOX;
+  const float* gg = gt + (size_t)b0 * OCC_VOX;
+  uint32_t* wg = words + (size_t)g * G * OCC_VOX;
+  unsigned long long x = OCC_RANS_L;
+  int ptr = region;                                    // the words written so far are wg[ptr .. region)
+  for (int t0 = steps - OCC_AHEAD; t0 >= 0; t0 -= OCC_AHEAD) {
+    float pv[OCC_AHEAD], gv[OCC_AHEAD];
+#pragma unroll
+    for (int k = 0; k < OCC_AHEAD; ++k) {
+      pv[k] = pg[(size_t)(t0 + k) * 64 + lane];
+      gv[k] = gg[(size_t)(t0 + k) * 64 + lane];
+    }
+    uint32_t fr[OCC_AHEAD], st[OCC_AHEAD];
+#pragma unroll
+    for (int k = 0; k < OCC_AHEAD; ++k) {
+      const uint32_t one = tab[occ_ctx(pv[k])];
+      const bool s = gv[k] != 0.f;
+      fr[k] = s ? one : 65536u - one;
+      st[k] = s ? 0u : one;
+      const unsigned long long word = __ballot(s);
+      if (gt_words && lane == 0) gt_words[(size_t)b0 * OCC_WPB + t0 + k] = word;
+    }
+#pragma unroll
+    for (int k = OCC_AHEAD - 1; k >= 0; --k) {
+      const bool emit = x >= ((unsigned long long)fr[k] << 47);
+      const unsigned long long m = __ballot(emit);
+      if (emit) {
+        const int at = ptr - 1 - __popcll((m >> lane) >> 1);   // the lanes above write first
+        if (at >= 0) wg[at] = (uint32_t)x;
+        x >>= 32;
+      }
+      ptr -= __popcll(m);
+      unsigned long long quot;
+      uint32_t rem;
+      occ_divmod(x, fr[k], quot, rem);
+      x = (quot << 16) + rem + st[k];
+    }
+  }
+  states[(size_t)g * 64 + lane] = x;
+  if (lane == 0) nwords[g] = (uint32_t)(region - ptr);
+}
+
+__global__ __launch_bounds__(64) void occ_rans_decode_kernel(const float* __restrict__ p, const int32_t* __restrict__ f1,
+                                                             const unsigned long long* __restrict__ states,
+                                                             const uint32_t* __restrict__ words,
+                                                             const long long* __restrict__ word_off,
+                                                             const uint32_t* __restrict__ nwords, long long total_words,
+                                                             int batch, int G, unsigned long long* __restrict__ occ_words,
+                                                             int32_t* __restrict__ counts, int32_t* __restrict__ status) {
+  __shared__ uint32_t tab[OCC_CTX];
+  const int lane = threadIdx.x, g = blockIdx.x;
+  occ_load_table(f1, tab, lane);
+  const int b0 = g * G, nb = min(G, batch - b0);
+  const float* pg = p + (size_t)b0 * OCC_VOX;
+  // this group's words are words[off .. off + n), cut to the buffer: nothing outside is ever read
+  long long off = word_off[g];
+  long long n = (long long)nwords[g];
+  bool damaged = false;
+  if (off < 0 || off > total_words) { off = 0; n = 0; damaged = true; }
+  if (n > total_words - off) { n = total_words - off; damaged = true; }
+  const uint32_t* wg = words + off;
+  unsigned long long x = states[(size_t)g * 64 + lane];
+  long long pos = 0;
+  for (int bl = 0; bl < nb; ++bl) {
+    int cnt = 0;
+    for (int t0 = 0; t0 < OCC_WPB; t0 += OCC_AHEAD) {
+      uint32_t one[OCC_AHEAD];
+#pragma unroll
+      for (int k = 0; k < OCC_AHEAD; ++k) one[k] = tab[occ_ctx(pg[((size_t)bl * OCC_WPB + t0 + k) * 64 + lane])];
+#pragma unroll
+      for (int k = 0; k < OCC_AHEAD; ++k) {
+        const uint32_t slot = (uint32_t)x & 0xFFFFu;
+        const bool s = slot < one[k];
+        const uint32_t f = s ? one[k] : 65536u - one[k];
+        const uint32_t start = s ? 0u : one[k];
+        x = (unsigned long long)f * (x >> 16) + slot - start;
+        const bool need = x < OCC_RANS_L;
+        const unsigned long long m = __ballot(need);
+        if (need) {
+          const long long at = pos + __popcll(m & ((1ull << lane) - 1ull));
+          uint32_t w = 0u;
+          if (at < n) w = wg[at]; else damaged = true;          // past the end: a zero, and the status says so
+          x = (x << 32) | w;
+        }
+        pos += __popcll(m);
+        const unsigned long long word = __ballot(s);
+        cnt += __popcll(word);
+        if (lane == 0) occ_words[((size_t)b0 + bl) * OCC_WPB + t0 + k] = word;
+      }
+    }
+    if (lane == 0) counts[b0 + bl] = cnt;
+  }
+  int st = 0;
+  if (__ballot(damaged) != 0ull) st |= NVF_OCC_RANS_PAST_END;
+  if (__ballot(x != OCC_RANS_L) != 0ull) st |= NVF_OCC_RANS_BAD_STATE;
+  if (pos < (long long)nwords[g]) st |= NVF_OCC_RANS_WORDS_LEFT;
+  if (lane == 0) status[g] = st;
+}
+
+// one wave per block, four blocks per workgroup; the block's 512 words 64 at a time, one per lane
+__global__ __launch_bounds__(256) void points_from_bits32_kernel(const unsigned long long* __restrict__ words,
+                                                                 const int32_t* __restrict__ offsets,
+                                                                 const int32_t* __restrict__ origins,
+                                                                 int32_t* __restrict__ points, int batch, int n) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= batch) return;
+  const int oz = origins ? origins[3 * b] : 0, oy = origins ? origins[3 * b + 1] : 0, ox = origins ? origins[3 * b + 2] : 0;
+  int run = offsets[b];
+  for (int w0 = 0; w0 < OCC_WPB; w0 += 64) {
+    const unsigned long long mine = words[(size_t)b * OCC_WPB + w0 + lane];
+    if (__ballot(mine != 0ull) == 0ull) continue;     // wave-uniform
+    for (int wi = 0; wi < 64; ++wi) {
+      const unsigned long long word = __shfl(mine, wi, 64);
+      if (word == 0ull) continue;                      // wave-uniform
+      const int slot = run + __popcll(word & ((1ull << lane) - 1ull));
+      if (((word >> lane) & 1ull) && slot >= 0 && slot < n) {
+        const int v = 64 * (w0 + wi) + lane;
+        int32_t* o = points + (size_t)slot * 3;
+        o[0] = oz + (v >> 10);
+        o[1] = oy + ((v >> 5) & 31);
+        o[2] = ox + (v & 31);
+      }
+      run += __popcll(word);
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int nvf_occ_ctx_hist(const float* p, const float* gt, int batch, int voxels, uint64_t* cnt, uint64_t* occ,
+                                uint64_t* bad, void* stream) {
+  if (!p || !gt || !cnt || !occ || !bad || batch <= 0 || voxels <= 0 || voxels > (1 << 24)) return NVF_EINVAL;
+  occ_ctx_hist_kernel<<<batch, OCC_HIST_THREADS, 0, nvf_stream(stream)>>>(
+      p, gt, voxels, (unsigned long long*)cnt, (unsigned long long*)occ, (unsigned long long*)bad);
+  NVF_LAUNCH_CHECK();
+  return NVF_OK;
+}
+
+extern "C" int nvf_occ_rans_encode(const float* p, const float* gt, const int32_t* f1, int batch, int group,
+                                   uint64_t* states, uint32_t* words, uint32_t* nwords, uint64_t* gt_words,
+                                   void* stream) {
+  if (!p || !gt || !f1 || !states || !words || !nwords || batch <= 0 || group < 1 || group > NVF_OCC_RANS_MAX_GROUP)
+    return NVF_EINVAL;
+  const int groups = (batch + group - 1) / group;
+  occ_rans_encode_kernel<<<groups, 64, 0, nvf_stream(stream)>>>(p, gt, f1, batch, group, (unsigned long long*)states,
+                                                                words, nwords, (unsigned long long*)gt_words);
+  NVF_LAUNCH_CHECK();
+  return NVF_OK;
+}
+
+extern "C" int nvf_occ_rans_decode(const float* p, const int32_t* f1, const uint64_t* states, const uint32_t* words,
+                                   const int64_t* word_off, const uint32_t* nwords, int64_t total_words, int batch,
+                                   int group, uint64_t* occ_words, int32_t* counts, int32_t* status, void* stream) {
+  if (!p || !f1 || !states || !words || !word_off || !nwords || !occ_words || !counts || !status || total_words < 0 ||
+      batch <= 0 || group < 1 || group > NVF_OCC_RANS_MAX_GROUP)
+    return NVF_EINVAL;
+  const int groups = (batch + group - 1) / group;
+  occ_rans_decode_kernel<<<groups, 64, 0, nvf_stream(stream)>>>(
+      p, f1, (const unsigned long long*)states, words, (const long long*)word_off, nwords, (long long)total_words, batch,
+      group, (unsigned long long*)occ_words, counts, status);
+  NVF_LAUNCH_CHECK();
+  return NVF_OK;
+}
+
+extern "C" int nvf_points_from_bits32(const uint64_t* words, const int32_t* offsets, const int32_t* origins,
+                                      int32_t* points, int n, int batch, void* stream) {
+  if (!words || !offsets || !points || n < 0 || batch <= 0) return NVF_EINVAL;
+  points_from_bits32_kernel<<<(batch + 3) / 4, 256, 0, nvf_stream(stream)>>>((const unsigned long long*)words, offsets,
+                                                                             origins, points, batch, n);
+  NVF_LAUNCH_CHECK();
+  return NVF_OK;
+}

@@ -1394,3 +1394,110 @@ def occ_hist(p, shift=None, nbits=None, prefix=None, d2=None, gt=None, edges=Non
     check(lib().nvf_occ_hist(_ptr(p), B, voxels, int(shift), int(nbits), _ptr(prefix), _ptr(d2), _ptr(gt), _ptr(count),
                              _ptr(sum_d2), _ptr(count_gt), _ptr(bad), _stream()), "nvf_occ_hist")
     return count, sum_d2, count_gt, bad
+
+
+# ---------------------------------------------------------------- lossless geometry (csrc/occ_rans.hip)
+OCC_CONTEXTS = 256
+OCC_RANS_MAX_GROUP = 1024
+OCC_RANS_PAST_END, OCC_RANS_BAD_STATE, OCC_RANS_WORDS_LEFT = 1, 2, 4
+
+
+def _occ_blocks(p, gt=None):
+    _f32(p, gt)
+    B = p.shape[0]
+    if B < 1 or p.numel() != B * 32768 or (gt is not None and gt.shape != p.shape):
+        raise RuntimeError("the occupancy coder takes p (and gt) as float32 [B, 1, 32, 32, 32]")
+    return B
+
+
+def _occ_table(f1, dev):
+    _chk(f1)
+    if f1.dtype != torch.int32 or f1.shape != (OCC_CONTEXTS,) or f1.device != dev:
+        raise RuntimeError(f"f1 must be int32 [{OCC_CONTEXTS}] on the device of p")
+
+
+def occ_ctx_hist(p, gt, cnt=None, occ=None, bad=None):
+    """Voxels and occupied voxels per context of p (include/nvf_hip.h: 256 contexts from the bits of p), added to cnt and
+    occ (int64 [256] holding the uint64 sums) and the voxels whose p is NaN or outside [0, 1] to bad (int64 [1]): pass
+    the three back in to stream a cloud batch by batch; absent, they start at zero.  -> (cnt, occ, bad)."""
+    B = _occ_blocks(p, gt)
+    if cnt is None:
+        cnt, occ, bad = (torch.zeros(n, dtype=torch.int64, device=p.device) for n in (OCC_CONTEXTS, OCC_CONTEXTS, 1))
+    _chk(cnt, occ, bad)
+    for t, n in ((cnt, OCC_CONTEXTS), (occ, OCC_CONTEXTS), (bad, 1)):
+        if t.dtype != torch.int64 or t.shape != (n,):
+            raise RuntimeError("occ_ctx_hist: cnt and occ are int64 [256], bad is int64 [1]")
+    check(lib().nvf_occ_ctx_hist(_ptr(p), _ptr(gt), B, 32768, _ptr(cnt), _ptr(occ), _ptr(bad), _stream()),
+          "nvf_occ_ctx_hist")
+    return cnt, occ, bad
+
+
+def occ_rans_encode(p, gt, f1, group):
+    """The occupancy gt of B blocks coded under p and the table f1 (int32 [256]) in groups of `group` blocks ->
+    (states int64 [groups, 64] holding the uint64 final states, words: a list with one int32 tensor (uint32 words, in
+    the decoder's reading order) per group, gt_words int64 [B, 512] the occupancy words of gt)."""
+    B = _occ_blocks(p, gt)
+    _occ_table(f1, p.device)
+    G = int(group)
+    if not 1 <= G <= OCC_RANS_MAX_GROUP:
+        raise RuntimeError(f"group must be in [1, {OCC_RANS_MAX_GROUP}], got {group!r}")
+    ng = (B + G - 1) // G
+    states = torch.empty((ng, 64), dtype=torch.int64, device=p.device)
+    region = torch.empty((ng, G * 32768), dtype=torch.int32, device=p.device)
+    nwords = torch.empty(ng, dtype=torch.int32, device=p.device)
+    gt_words = torch.empty((B, 512), dtype=torch.int64, device=p.device)
+    check(lib().nvf_occ_rans_encode(_ptr(p), _ptr(gt), _ptr(f1), B, G, _ptr(states), _ptr(region), _ptr(nwords),
+                                    _ptr(gt_words), _stream()), "nvf_occ_rans_encode")
+    words = []
+    for g, n in enumerate(nwords.tolist()):
+        end = min(G, B - g * G) * 32768
+        words.append(region[g, end - n:end].clone())
+    return states, words, gt_words
+
+
+def occ_rans_decode(p, f1, states, words, nwords, group):
+    """The inverse of occ_rans_encode: states int64 [groups, 64], words int32 [total] the groups' words back to back,
+    nwords int32 [groups] -> (occ_words int64 [B, 512], counts int32 [B], status int32 [groups]: 0 for a sound group,
+    else the OR of OCC_RANS_PAST_END / _BAD_STATE / _WORDS_LEFT).  A damaged stream cannot make the kernel read outside
+    `words`; what it decodes then is garbage and the status says so."""
+    B = _occ_blocks(p)
+    _occ_table(f1, p.device)
+    G = int(group)
+    if not 1 <= G <= OCC_RANS_MAX_GROUP:
+        raise RuntimeError(f"group must be in [1, {OCC_RANS_MAX_GROUP}], got {group!r}")
+    ng = (B + G - 1) // G
+    _chk(states, words, nwords)
+    if states.dtype != torch.int64 or states.shape != (ng, 64) or words.dtype != torch.int32 or words.dim() != 1 or \
+            nwords.dtype != torch.int32 or nwords.shape != (ng,):
+        raise RuntimeError(f"occ_rans_decode: {B} blocks in groups of {G} take states int64 [{ng}, 64], words int32 [n] "
+                           f"and nwords int32 [{ng}]")
+    n64 = nwords.to(torch.int64) & 0xFFFFFFFF
+    word_off = (torch.cumsum(n64, 0) - n64).contiguous()
+    if words.numel() == 0:                      # a pointer to pass; total_words = 0 keeps the kernel away from it
+        words = torch.zeros(1, dtype=torch.int32, device=p.device)
+        total = 0
+    else:
+        total = words.numel()
+    occ_words = torch.empty((B, 512), dtype=torch.int64, device=p.device)
+    counts = torch.empty(B, dtype=torch.int32, device=p.device)
+    status = torch.empty(ng, dtype=torch.int32, device=p.device)
+    check(lib().nvf_occ_rans_decode(_ptr(p), _ptr(f1), _ptr(states), _ptr(words), _ptr(word_off), _ptr(nwords), total, B,
+                                    G, _ptr(occ_words), _ptr(counts), _ptr(status), _stream()), "nvf_occ_rans_decode")
+    return occ_words, counts, status
+
+
+def points_from_bits32(words, counts, origins):
+    """points_from_bits for the 32^3 grid: occupancy words int64 [B, 512] + counts int32 [B] -> int32 [n, 3] points
+    origin + (z, y, x) in (b, z, y, x) raster order.  origins int32 [B, 3] or None."""
+    _chk(words, counts, origins)
+    B = words.shape[0]
+    if words.dtype != torch.int64 or words.shape != (B, 512) or counts.dtype != torch.int32 or counts.shape != (B,):
+        raise RuntimeError("points_from_bits32: words must be int64 [B, 512] and counts int32 [B]")
+    if origins is not None and (origins.dtype != torch.int32 or origins.shape != (B, 3)):
+        raise RuntimeError("points_from_bits32: origins must be int32 [B, 3]")
+    offsets = (torch.cumsum(counts, 0, dtype=torch.int32) - counts).contiguous()
+    total = int(counts.sum().item())
+    points = torch.empty((max(total, 1), 3), dtype=torch.int32, device=words.device)
+    check(lib().nvf_points_from_bits32(_ptr(words), _ptr(offsets), _ptr(origins), _ptr(points), total, B, _stream()),
+          "nvf_points_from_bits32")
+    return points[:total]

@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""Times the lossless occupancy coder on N resident blocks, next to the eval forward it follows.
+
+    python tools/lossless_bench.py --blocks 917 --batch 64 --chanstr 8,16,8,8 --ch 3 --reps 10 --warmup 2
+
+What is timed is a whole call, latents and ground truth on the device in, bytes (encode) or occupancy words on the
+device (decode) out:
+
+    forward          Net.reconstruct over all blocks in calls of --batch: what both coder routes contain (the encoder twice)
+    encode G         lossless_pack.encode_occupancy: forward + nvf_occ_ctx_hist, the table, forward + nvf_occ_rans_encode,
+                     the copy of states and words to the host and the pack's bytes
+    decode G         lossless_pack.decode_occupancy: the pack's bytes to the device, forward + nvf_occ_rans_decode, status
+    coder G          nvf_occ_rans_encode / nvf_occ_rans_decode alone on one span of resident probabilities (what one
+                     launch of the whole calls takes: lossless_pack.SPAN_GROUPS groups, one wave each), bracketed by
+                     device events; the encoder's includes trimming each group's region to its words
+
+for G = 16, 32 and 64 blocks per group.  Every whole call ends in a synchronise (its result is on the host or its
+status was read); the routes alternate inside every repetition, the first --warmup repetitions are dropped and the
+median, minimum and maximum of the rest are reported in milliseconds.  Each pack is decoded and compared with the
+ground truth's occupancy words first.  Weights and latents are seeded random numbers and the ground truth is a seeded
+draw from the decoder's own probabilities, so the coder has a calibrated field to work with; its time depends on the
+values only through the number of words it moves.  Prints one JSON line.  There is no CPU path."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--blocks", type=int, default=917)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--chanstr", default="8,16,8,8")
+    ap.add_argument("--ch", type=int, default=3)
+    ap.add_argument("--groups", default="16,32,64")
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("lossless_bench.py needs a HIP device: nothing here can be timed on a CPU")
+    from nvfpcc_amd import lossless_pack as lp, network, ops
+    from nvfpcc_amd.model import Net
+    from nvfpcc_amd.seeds import synthetic_seed
+    dev = torch.device("cuda")
+    network.reset_seed(synthetic_seed())
+    net = Net(None, "Gaussian", a.ch, a.chanstr, verbose=False)
+    g = torch.Generator().manual_seed(3)
+    with torch.no_grad():
+        for n, p in net.named_parameters():
+            if n.endswith("kernel") or n.endswith(".b"):
+                p.add_(0.03 * torch.randn(p.shape, generator=g))
+    net = net.to(dev)
+    lat = torch.round(2.0 * torch.randn(a.blocks, a.ch, 2, 2, 2, generator=g)).to(dev)
+    groups = [int(v) for v in a.groups.split(",")]
+    gd = torch.Generator(device=dev).manual_seed(4)
+    gts = []
+    with torch.no_grad():
+        for lo in range(0, a.blocks, a.batch):
+            p = net.reconstruct(lat[lo:lo + a.batch].contiguous(), 2)
+            # sharpened so that the cloud is sparse, as a leaf block is
+            gts.append((torch.rand(p.shape, device=dev, generator=gd) < p ** 8).float())
+    gt = torch.cat(gts, 0)
+    n_points = int(gt.sum().item())
+
+    def forward():
+        with torch.no_grad():
+            for lo in range(0, a.blocks, a.batch):
+                net.reconstruct(lat[lo:lo + a.batch].contiguous(), 2)
+        torch.cuda.synchronize()
+
+    packs, info = {}, {}
+    for G in groups:
+        packs[G], side = lp.encode_occupancy(net, lat, gt, batch=a.batch, group=G)
+        words, counts = lp.decode_occupancy(net, lat, packs[G], batch=a.batch)
+        if not torch.equal(words, side["gt_words"]) or int(counts.sum().item()) != n_points:
+            raise SystemExit(f"group {G}: the pack does not decode to the ground truth")
+        info[G] = {"bytes": len(packs[G]), "bpp": round(8 * len(packs[G]) / n_points, 4),
+                   "ideal_bpp": round(side["ideal_bits"] / n_points, 4)}
+    routes = {"forward": forward}
+    for G in groups:
+        routes[f"encode_G{G}"] = lambda G=G: lp.encode_occupancy(net, lat, gt, batch=a.batch, group=G)
+        routes[f"decode_G{G}"] = lambda G=G: lp.decode_occupancy(net, lat, packs[G], batch=a.batch)
+    times = {k: [] for k in routes}
+    for rep in range(a.warmup + a.reps):
+        for name, fn in routes.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if rep >= a.warmup:
+                times[name].append(1e3 * (time.perf_counter() - t0))
+
+    # the coder kernels alone, on one span of resident probabilities
+    span = {}
+    with torch.no_grad():
+        for G in groups:
+            nb = min(lp._span(a.batch, G, lp.SPAN_GROUPS), a.blocks)
+            p = net.reconstruct(lat[:nb].contiguous(), 2)
+            cnt, occ, _ = ops.occ_ctx_hist(p, gt[:nb].contiguous())
+            f1 = torch.tensor(lp.table_from_counts(cnt.tolist(), occ.tolist()), dtype=torch.int32, device=dev)
+            states, words, _ = ops.occ_rans_encode(p, gt[:nb].contiguous(), f1, G)
+            nwords = torch.tensor([w.numel() for w in words], dtype=torch.int32, device=dev)
+            span[G] = (nb, p, gt[:nb].contiguous(), f1, states, torch.cat(words), nwords)
+            times[f"coder_encode_G{G}"], times[f"coder_decode_G{G}"] = [], []
+        for rep in range(a.warmup + a.reps):
+            for G in groups:
+                nb, p, gg, f1, states, flat, nwords = span[G]
+                for name, fn in ((f"coder_encode_G{G}", lambda: ops.occ_rans_encode(p, gg, f1, G)),
+                                 (f"coder_decode_G{G}", lambda: ops.occ_rans_decode(p, f1, states, flat, nwords, G))):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if rep >= a.warmup:
+                        times[name].append(e0.elapsed_time(e1))
+    out = {"tool": "lossless_bench", "device": torch.cuda.get_device_name(0), "blocks": a.blocks, "batch": a.batch,
+           "chanstr": a.chanstr, "reps": a.reps, "warmup": a.warmup, "points": n_points,
+           "span_blocks": {str(G): span[G][0] for G in groups}, "packs": {str(G): v for G, v in info.items()},
+           "ms": {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+                  for k, v in times.items()}}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
