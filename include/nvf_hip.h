@@ -890,59 +890,43 @@ int nvf_points_from_bits32(const uint64_t* words, const int32_t* offsets, const 
                            int batch, void* stream);
 
 /* ---- pre-processing on the device (nvfpcc_amd/preprocess.py: preprocess_device, csrc/pp_device.hip) ----------------
- * From int32 [P,3] points with 10-bit coordinates to everything nvf_nearest_dist2 and the trainer take, without a host
- * pass.  A CELL CODE is the 15-bit Morton code of a level-5 cell (x >> 5, y >> 5, z >> 5), x in the lowest bit of each
- * level: the reference's traversal order of the leaves is ascending cell code.  Every result is an OR or an integer
- * count, so repeated calls give the same bits.  Call order: keys, (sort the keys ascending), tree, blocks, neighbours.
- * nvf_pp_keys: clears bitmap6 and meta, then per point keys[i] = cell code << 15 | (x & 31) << 10 | (y & 31) << 5 |
- *   (z & 31), the point's bit in bitmap6 (uint32 [8192], 16-byte aligned: bit = cell code << 3 | child index of the
- *   16^3 cell, so byte c holds the eight children of cell c), and meta[1] += 1 for a point with a coordinate outside
- *   [0, 1024) (its key is 0x7fffffff; the caller raises on a non-zero count).
- * nvf_pp_tree: origins int32 [N,3] (room for 32768 rows) in traversal order; rank_tab uint32 [2048] = the level-5
+ * From int32 [P,3] points with coordinates of `bits` bits (10, 11 or 12; anything else is NVF_EINVAL) to everything
+ * nvf_nearest_dist2 and the trainer take, without a host pass.  D = bits - 5 is the level of the 32^3 leaves.  A CELL
+ * CODE is the 3 D-bit Morton code of a level-D cell (x >> 5, y >> 5, z >> 5), x in the lowest bit of each level: the
+ * reference's traversal order of the leaves is ascending cell code.  W = 8^D / 32 is the number of words of the level-D
+ * bitmap and cap(L) = min(8^L, npts) bounds the nodes of level L.  Every result is an OR or an integer count, so
+ * repeated calls give the same bits.  Call order: keys, (sort the keys ascending), tree, blocks, neighbours, each with
+ * the same bits and npts.
+ * nvf_pp_keys: clears bitmap and meta, then per point keys[i] = cell code << 15 | (x & 31) << 10 | (y & 31) << 5 |
+ *   (z & 31) -- keys is int32 [P] at 10 bits (30-bit keys) and int64 [P] at 11 and 12 (up to 36 bits) --, the point's
+ *   bit in bitmap (uint32 [8 W], the level-(D + 1) bitmap: bit = cell code << 3 | child index of the 16^3 cell, so byte
+ *   c holds the eight children of cell c), and meta[1] += 1 for a point with a coordinate outside [0, 2^bits) (its key
+ *   is the type's largest value, 0x7fffffff or 0x7fffffffffffffff; the caller raises on a non-zero count).
+ * nvf_pp_tree: origins int32 [N,3] (room for cap(D) rows) in traversal order; rank_tab uint32 [2 W] = the level-D
  *   bitmap and the number of set bits before each of its words (block id of a cell = a prefix popcount);
- *   octree_bytes uint8 [NVF_PP_OCT_BYTES]: the child-occupancy bytes of level L (bit i = child i), breadth first,
- *   start at byte (8^L - 1) / 7; nb_off int32 [N+1] (room for 32769) the row offsets of the candidate lists.
- *   meta int32 [NVF_PP_META_INTS]: [0] N, [1] rejected points, [2..7] bytes of level 0..5, [8] nb_off[N], [9] occupied
- *   voxels (distinct points; written by nvf_pp_blocks).
- * nvf_pp_blocks: sorted_keys -> pts int32 [P,3] sorted by block and blk_off int32 [N+1] (room for 32769); N is read
- *   from meta on the device.
- * nvf_pp_neighbours: nb_idx int32 [nb_off[N]]: per block the occupied blocks within +-2 block steps, the block itself
- *   first, then by squared block distance ((dx, dy, dz) lexicographic among equals).
+ *   octree_bytes uint8 [sum of cap(L), L <= D]: the child-occupancy bytes of level L (bit i = child i), breadth first,
+ *   start at byte sum of cap(l) over l < L; nb_off int32 [N+1] (room for cap(D) + 1) the row offsets of the candidate
+ *   lists; work uint32 [NVF_PP_WORK_WORDS] is scratch.  A grid-wide prefix sum is three launches (sums per workgroup,
+ *   one workgroup scans them, emit); no workgroup waits for another.
+ *   meta int32 [NVF_PP_META_INTS]: [0] N, [1] rejected points, [2..9] bytes of level 0..7 (D + 1 of them are written),
+ *   [10] nb_off[N], [11] occupied voxels (distinct points; written by nvf_pp_blocks).
+ * nvf_pp_blocks: sorted_keys (the type nvf_pp_keys wrote) -> pts int32 [P,3] sorted by block and blk_off int32 [N+1]
+ *   (room for cap(D) + 1); N is read from meta on the device.
+ * nvf_pp_neighbours: nb_idx int32 [nb_off[N]]: per block the occupied blocks within +-2 block steps of the 2^D grid (an
+ *   octant boundary is no boundary), the block itself first, then by squared block distance ((dx, dy, dz)
+ *   lexicographic among equals).
  * nvf_pp_grids: dist[i] = sqrtf(d2[i]) correctly rounded, gt[i] = (d2[i] == 0) as 1.0f / 0.0f, i < n; d2 in [0, 2^24);
  *   pointers 16-byte aligned; dist may be the buffer of d2 itself. */
 #define NVF_PP_META_INTS 16
-#define NVF_PP_OCT_BYTES 37449
-int nvf_pp_keys(const int32_t* pts, int npts, int32_t* keys, uint32_t* bitmap6, int32_t* meta, void* stream);
-int nvf_pp_tree(const uint32_t* bitmap6, int32_t* origins, uint32_t* rank_tab, uint8_t* octree_bytes, int32_t* nb_off,
-                int32_t* meta, void* stream);
-int nvf_pp_blocks(const int32_t* sorted_keys, int npts, const uint32_t* rank_tab, int32_t* meta, int32_t* pts,
+#define NVF_PP_WORK_WORDS 11264
+int nvf_pp_keys(const int32_t* pts, int npts, int bits, void* keys, uint32_t* bitmap, int32_t* meta, void* stream);
+int nvf_pp_tree(const uint32_t* bitmap, int bits, int npts, int32_t* origins, uint32_t* rank_tab, uint8_t* octree_bytes,
+                int32_t* nb_off, uint32_t* work, int32_t* meta, void* stream);
+int nvf_pp_blocks(const void* sorted_keys, int npts, int bits, const uint32_t* rank_tab, int32_t* meta, int32_t* pts,
                   int32_t* blk_off, void* stream);
-int nvf_pp_neighbours(const int32_t* origins, const uint32_t* rank_tab, const int32_t* nb_off, int32_t* nb_idx,
+int nvf_pp_neighbours(const int32_t* origins, int bits, const uint32_t* rank_tab, const int32_t* nb_off, int32_t* nb_idx,
                       int nblocks, void* stream);
 int nvf_pp_grids(const int32_t* d2, float* dist, float* gt, int64_t n, void* stream);
-
-/* The same four steps for clouds of 11 or 12 bits per axis (csrc/pp_deep.hip); bits = 10 is served by the entry points
- * above and rejected here.  D = bits - 5 is the level of the 32^3 leaves, a cell code has 3 D bits, W = 8^D / 32 is the
- * number of words of the level-D bitmap and cap(L) = min(8^L, npts) bounds the nodes of level L.  Same call order, same
- * contracts, with these differences:
- * nvf_pp_keys_deep: keys are int64 (cell code << 15 | local voxel, up to 36 bits; 0x7fffffffffffffff for a rejected
- *   point); bitmap uint32 [8 W] is the level-(D + 1) bitmap (256 KiB at 11 bits, 2 MiB at 12) and stays in global memory.
- * nvf_pp_tree_deep: origins has room for cap(D) rows, nb_off for cap(D) + 1; rank_tab uint32 [2 W]; octree_bytes holds
- *   level L at byte sum of cap(l) over l < L, so sum of cap(L) over L <= D bytes in all; work uint32
- *   [NVF_PP_DEEP_WORK_WORDS] is scratch.  A grid-wide prefix sum is three launches (sums per workgroup, one workgroup
- *   scans them, emit); no workgroup waits for another.  meta: [0] N, [1] rejected points, [2..9] bytes of level 0..7
- *   (D + 1 of them are written), [10] nb_off[N], [11] occupied voxels (written by nvf_pp_blocks_deep).
- * nvf_pp_blocks_deep: blk_off has room for cap(D) + 1.
- * nvf_pp_neighbours_deep: the steps are taken on the 2^D grid; an octant boundary is no boundary. */
-#define NVF_PP_DEEP_WORK_WORDS 11264
-int nvf_pp_keys_deep(const int32_t* pts, int npts, int bits, int64_t* keys, uint32_t* bitmap, int32_t* meta,
-                     void* stream);
-int nvf_pp_tree_deep(const uint32_t* bitmap, int bits, int npts, int32_t* origins, uint32_t* rank_tab,
-                     uint8_t* octree_bytes, int32_t* nb_off, uint32_t* work, int32_t* meta, void* stream);
-int nvf_pp_blocks_deep(const int64_t* sorted_keys, int npts, int bits, const uint32_t* rank_tab, int32_t* meta,
-                       int32_t* pts, int32_t* blk_off, void* stream);
-int nvf_pp_neighbours_deep(const int32_t* origins, int bits, const uint32_t* rank_tab, const int32_t* nb_off,
-                           int32_t* nb_idx, int nblocks, void* stream);
 
 #ifdef __cplusplus
 }

@@ -144,15 +144,11 @@ PROTOTYPES = {
     "nvf_occ_rans_encode": (I, [P, P, P, I, I, P, P, P, P, P]),
     "nvf_occ_rans_decode": (I, [P, P, P, P, P, P, L, I, I, P, P, P, P]),
     "nvf_points_from_bits32": (I, [P, P, P, P, I, I, P]),
-    "nvf_pp_keys": (I, [P, I, P, P, P, P]),
-    "nvf_pp_tree": (I, [P, P, P, P, P, P, P]),
-    "nvf_pp_blocks": (I, [P, I, P, P, P, P, P]),
-    "nvf_pp_neighbours": (I, [P, P, P, P, I, P]),
+    "nvf_pp_keys": (I, [P, I, I, P, P, P, P]),
+    "nvf_pp_tree": (I, [P, I, I, P, P, P, P, P, P, P]),
+    "nvf_pp_blocks": (I, [P, I, I, P, P, P, P, P]),
+    "nvf_pp_neighbours": (I, [P, I, P, P, P, I, P]),
     "nvf_pp_grids": (I, [P, P, P, L, P]),
-    "nvf_pp_keys_deep": (I, [P, I, I, P, P, P, P]),
-    "nvf_pp_tree_deep": (I, [P, I, I, P, P, P, P, P, P, P]),
-    "nvf_pp_blocks_deep": (I, [P, I, I, P, P, P, P, P]),
-    "nvf_pp_neighbours_deep": (I, [P, I, P, P, P, I, P]),
 }
 
 

@@ -8,7 +8,7 @@
     nearest input point, gt_grid = (dist == 0), axes (x, y, z) (util_get_grids.py:19-46) -- the distances come
     from the gfx950 kernel nvf_nearest_dist2 instead of 30 M KD-tree queries in a Python loop.
 
-`preprocess_device` does both on the device (csrc/pp_device.hip; csrc/pp_deep.hip for 11 and 12 bits per axis) and leaves the float32 grids there for the trainer;
+`preprocess_device` does both on the device (csrc/pp_device.hip, 10 to 12 bits per axis) and leaves the float32 grids there for the trainer;
 `write_octree_pack` / `read_octree_pack` carry the partition in pack.pk as octree bytes instead of raw origins.
 """
 import numpy as np
@@ -240,23 +240,22 @@ def octree_pack_from_origins(origins, bits=10):
 
 
 # ---------------------------------------------------------------- the whole pre-processing on the device
-MAX_LEAVES = (ROOT // LEAF) ** 3
-OCT_BYTES = 37449               # NVF_PP_OCT_BYTES: level L starts at byte (8^L - 1) / 7
-META_INTS = 16                  # NVF_PP_META_INTS
+META_INTS = 16                  # NVF_PP_META_INTS: [0] N, [1] rejected points, [2..9] bytes of level 0..7, [10] nb_off[N], [11] voxels
+WORK_WORDS = 11264              # NVF_PP_WORK_WORDS
 
 
 class DevicePreprocess:
     """What preprocess_device leaves on the device.  origins int32 [N,3] (traversal order), blk_off int32 [N+1],
     points int32 [P,3] sorted by block, (nb_off, nb_idx) the candidate lists, gt / dist float32 [N,1,32,32,32],
-    n_points = occupied voxels, bits = bits per axis.  octree_bytes (D + 1 = bits - 4 `bytes`, level 0..D) and subtree
-    are fetched when first asked."""
+    n_points = occupied voxels, bits = bits per axis.  octree_bytes (D + 1 = bits - 4 `bytes`, level 0..D; level L
+    starts at byte level_starts[L] of oct_dev) and subtree are fetched when first asked."""
 
     def __init__(self, origins, blk_off, points, nb_off, nb_idx, gt, dist, n_points, oct_dev, level_counts,
-                 level_starts=None, bits=10):
+                 level_starts, bits=10):
         self.origins, self.blk_off, self.points, self.nb_off, self.nb_idx = origins, blk_off, points, nb_off, nb_idx
         self.gt, self.dist, self.n_points, self.bits = gt, dist, int(n_points), int(bits)
         self._oct_dev, self._level_counts = oct_dev, [int(c) for c in level_counts]
-        self._level_starts = level_starts if level_starts is not None else [(8 ** lv - 1) // 7 for lv in range(6)]
+        self._level_starts = [int(s) for s in level_starts]
         self._octree_bytes = self._subtree = None
 
     @property
@@ -292,8 +291,9 @@ def grids_from_d2(d2, in_place=False):
 def preprocess_device(points, device="cuda", bits=10):
     """octree_partition + build_grids on the device: integer points [P,3] (numpy or tensor, coordinates of `bits` bits,
     duplicates allowed) -> DevicePreprocess.  The host reads one 64-byte record (N, the count of rejected points, the
-    list sizes); nothing that scales with P or with the voxels crosses the bus after the points went up.  bits = 10
-    runs the kernels of csrc/pp_device.hip, 11 and 12 those of csrc/pp_deep.hip."""
+    list sizes); nothing that scales with P or with the voxels crosses the bus after the points went up.  The kernels
+    are those of csrc/pp_device.hip at the leaf level D = bits - 5: sort keys are int32 at 10 bits and int64 above, and
+    every buffer is sized from min(8^L, P), the most nodes level L can have."""
     depth = _depth(bits)
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -310,76 +310,36 @@ def preprocess_device(points, device="cuda", bits=10):
     if t.dtype != torch.int32:
         t = t.to(torch.int64).clamp(-1, 1 << bits).to(torch.int32)          # out of range stays out of range in 32 bits
     t = t.contiguous()
-    if depth > 5:
-        return _preprocess_device_deep(t, dev, bits)
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream().cuda_stream
-        i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
-        keys, bitmap6, meta = i32(npts), i32(8192), i32(META_INTS)
-        origins, tab, nb_off, blk_off = i32(MAX_LEAVES, 3), i32(2048), i32(MAX_LEAVES + 1), i32(MAX_LEAVES + 1)
-        oct_dev = torch.empty(OCT_BYTES, dtype=torch.uint8, device=dev)
-        spts = i32(npts, 3)
-        L = lib()
-        check(L.nvf_pp_keys(t.data_ptr(), npts, keys.data_ptr(), bitmap6.data_ptr(), meta.data_ptr(), st), "nvf_pp_keys")
-        skeys = torch.sort(keys).values                          # plumbing: equal keys are equal points
-        check(L.nvf_pp_tree(bitmap6.data_ptr(), origins.data_ptr(), tab.data_ptr(), oct_dev.data_ptr(),
-                            nb_off.data_ptr(), meta.data_ptr(), st), "nvf_pp_tree")
-        check(L.nvf_pp_blocks(skeys.data_ptr(), npts, tab.data_ptr(), meta.data_ptr(), spts.data_ptr(),
-                              blk_off.data_ptr(), st), "nvf_pp_blocks")
-        m = meta.cpu().tolist()                                  # the one host sync of the call
-        n, bad, level_counts, nb_total, voxels = m[0], m[1], m[2:8], m[8], m[9]
-        if bad:
-            raise ValueError(f"coordinates must lie in [0, 1024): {bad} points do not")
-        origins, nb_off, blk_off = origins[:n], nb_off[:n + 1], blk_off[:n + 1]
-        nb_idx = i32(nb_total)
-        check(L.nvf_pp_neighbours(origins.data_ptr(), tab.data_ptr(), nb_off.data_ptr(), nb_idx.data_ptr(), n, st),
-              "nvf_pp_neighbours")
-        d2 = i32(n, 1, LEAF, LEAF, LEAF)
-        check(L.nvf_nearest_dist2(spts.data_ptr(), blk_off.data_ptr(), origins.data_ptr(), nb_off.data_ptr(),
-                                  nb_idx.data_ptr(), d2.data_ptr(), n, st), "nvf_nearest_dist2")
-        gt, dist = grids_from_d2(d2, in_place=True)
-    return DevicePreprocess(origins, blk_off, spts, nb_off, nb_idx, gt, dist, voxels, oct_dev, level_counts)
-
-
-DEEP_WORK_WORDS = 11264         # NVF_PP_DEEP_WORK_WORDS
-DEEP_META = {"levels": 2, "nb": 10, "voxels": 11}        # meta of nvf_pp_tree_deep: [2..9] bytes of level 0..7
-
-
-def _preprocess_device_deep(t, dev, bits):
-    """preprocess_device for 11 and 12 bits per axis: the same steps with int64 sort keys, the bitmap of level D + 1 in
-    global memory and every buffer sized from min(8^L, P) instead of 8^L."""
-    depth, npts = bits - 5, t.shape[0]
     caps = [min(8 ** lv, npts) for lv in range(depth + 1)]
     starts = [sum(caps[:lv]) for lv in range(depth + 1)]
     cap, words = caps[depth], 8 ** depth // 32
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream().cuda_stream
         i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
-        keys = torch.empty(npts, dtype=torch.int64, device=dev)
-        bitmap, meta, work = i32(8 * words), i32(META_INTS), i32(DEEP_WORK_WORDS)
+        keys = torch.empty(npts, dtype=torch.int32 if bits == 10 else torch.int64, device=dev)
+        bitmap, meta, work = i32(8 * words), i32(META_INTS), i32(WORK_WORDS)
         origins, tab, nb_off, blk_off = i32(cap, 3), i32(2 * words), i32(cap + 1), i32(cap + 1)
         oct_dev = torch.empty(sum(caps), dtype=torch.uint8, device=dev)
         spts = i32(npts, 3)
         L = lib()
-        check(L.nvf_pp_keys_deep(t.data_ptr(), npts, bits, keys.data_ptr(), bitmap.data_ptr(), meta.data_ptr(), st),
-              "nvf_pp_keys_deep")
+        check(L.nvf_pp_keys(t.data_ptr(), npts, bits, keys.data_ptr(), bitmap.data_ptr(), meta.data_ptr(), st),
+              "nvf_pp_keys")
         skeys = torch.sort(keys).values                          # plumbing: equal keys are equal points
-        check(L.nvf_pp_tree_deep(bitmap.data_ptr(), bits, npts, origins.data_ptr(), tab.data_ptr(), oct_dev.data_ptr(),
-                                 nb_off.data_ptr(), work.data_ptr(), meta.data_ptr(), st), "nvf_pp_tree_deep")
-        check(L.nvf_pp_blocks_deep(skeys.data_ptr(), npts, bits, tab.data_ptr(), meta.data_ptr(), spts.data_ptr(),
-                                   blk_off.data_ptr(), st), "nvf_pp_blocks_deep")
+        check(L.nvf_pp_tree(bitmap.data_ptr(), bits, npts, origins.data_ptr(), tab.data_ptr(), oct_dev.data_ptr(),
+                            nb_off.data_ptr(), work.data_ptr(), meta.data_ptr(), st), "nvf_pp_tree")
+        check(L.nvf_pp_blocks(skeys.data_ptr(), npts, bits, tab.data_ptr(), meta.data_ptr(), spts.data_ptr(),
+                              blk_off.data_ptr(), st), "nvf_pp_blocks")
         m = meta.cpu().tolist()                                  # the one host sync of the call
-        n, bad, nb_total, voxels = m[0], m[1], m[DEEP_META["nb"]], m[DEEP_META["voxels"]]
-        level_counts = m[DEEP_META["levels"]:DEEP_META["levels"] + depth + 1]
+        n, bad, level_counts, nb_total, voxels = m[0], m[1], m[2:depth + 3], m[10], m[11]
         if bad:
             raise ValueError(f"coordinates must lie in [0, {1 << bits}): {bad} points do not")
         origins, nb_off, blk_off = origins[:n], nb_off[:n + 1], blk_off[:n + 1]
         nb_idx = i32(nb_total)
-        check(L.nvf_pp_neighbours_deep(origins.data_ptr(), bits, tab.data_ptr(), nb_off.data_ptr(), nb_idx.data_ptr(), n,
-                                       st), "nvf_pp_neighbours_deep")
+        check(L.nvf_pp_neighbours(origins.data_ptr(), bits, tab.data_ptr(), nb_off.data_ptr(), nb_idx.data_ptr(), n, st),
+              "nvf_pp_neighbours")
         d2 = i32(n, 1, LEAF, LEAF, LEAF)
         check(L.nvf_nearest_dist2(spts.data_ptr(), blk_off.data_ptr(), origins.data_ptr(), nb_off.data_ptr(),
                                   nb_idx.data_ptr(), d2.data_ptr(), n, st), "nvf_nearest_dist2")
         gt, dist = grids_from_d2(d2, in_place=True)
-    return DevicePreprocess(origins, blk_off, spts, nb_off, nb_idx, gt, dist, voxels, oct_dev, level_counts,
-                            level_starts=starts, bits=bits)
+    return DevicePreprocess(origins, blk_off, spts, nb_off, nb_idx, gt, dist, voxels, oct_dev, level_counts, starts,
+                            bits=bits)

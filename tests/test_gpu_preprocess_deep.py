@@ -1,5 +1,5 @@
 """Pre-processing of clouds with 11 and 12 bits per axis on the device (preprocess.preprocess_device(bits=...),
-csrc/pp_deep.hip) against three yardsticks: the CPU restatement (preprocess.octree_partition / octree_level_bytes /
+csrc/pp_device.hip at D = 6 and 7) against three yardsticks: the CPU restatement (preprocess.octree_partition / octree_level_bytes /
 _neighbour_lists), the KD-tree grid oracle, and the 10-bit device path -- which is pinned to the reference's executable
 -- under translation by whole octants.  Then the command line at 11 bits.  Every comparison is exact."""
 import os

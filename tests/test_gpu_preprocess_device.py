@@ -124,6 +124,100 @@ def test_bad_input_raises_value_error():
         pp.preprocess_device(np.zeros((4, 3), np.float32), "cuda")
 
 
+def exact_against_the_cpu_restatement(pts, bits, pre):
+    """Every integer output of `pre` against octree_partition / octree_level_bytes / _neighbour_lists and a host sort;
+    returns the origins."""
+    pts = np.asarray(pts, np.int64)
+    origins, subtree = pp.octree_partition(pts, bits)
+    assert pre.bits == bits and pre.origins.dtype == torch.int32 and np.array_equal(pre.origins.cpu().numpy(), origins)
+    assert pre.octree_bytes == tuple(pp.octree_level_bytes(pts, bits)) and pre.subtree == subtree
+    assert pre.octree_pack() == pp.octree_pack_from_origins(origins, bits)
+    assert np.array_equal(pp.read_octree_pack(pre.octree_pack()), origins)
+    nb_off, nb_idx = pp._neighbour_lists(origins)
+    assert np.array_equal(pre.nb_off.cpu().numpy(), nb_off) and np.array_equal(pre.nb_idx.cpu().numpy(), nb_idx)
+    key = pp._child_path_key(pts // 32, bits - 5) * 32768 + (pts % 32) @ np.array([1024, 32, 1])
+    order = np.argsort(key, kind="stable")
+    assert np.array_equal(pre.points.cpu().numpy(), pts[order])
+    first = np.flatnonzero(np.diff(key[order] // 32768, prepend=-1))
+    assert np.array_equal(pre.blk_off.cpu().numpy(), np.concatenate([first, [len(pts)]]))
+    assert pre.n_points == len(np.unique(pts, axis=0)) == int(pre.gt.sum().item())
+    return origins
+
+
+@pytest.mark.parametrize("bits", (10, 11, 12))
+def test_one_point_at_the_last_voxel_of_the_volume(bits):
+    """Every level holds one node (min(8^L, 1) = 1 byte of room) and every scan meets its only non-empty word at the
+    very end of its bitmap."""
+    need_gpu()
+    from oracle import preprocess_oracle as PO
+    top = (1 << bits) - 1
+    pts = np.array([[top, top, top]], np.int64)
+    pre = pp.preprocess_device(pts, "cuda", bits=bits)
+    origins = exact_against_the_cpu_restatement(pts, bits, pre)
+    assert origins.tolist() == [[top - 31] * 3] and pre.octree_bytes == (b"\x80",) * (bits - 4)
+    assert pre.nb_off.tolist() == [0, 1] and pre.nb_idx.tolist() == [0] and pre.blk_off.tolist() == [0, 1]
+    gt_o, dist_o = PO.grids(pts, origins)
+    assert pre.gt.shape == (1, 1, 32, 32, 32)
+    assert torch.equal(pre.gt.cpu(), torch.from_numpy(gt_o).float())
+    assert torch.equal(pre.dist.cpu(), torch.from_numpy(dist_o).float())
+
+
+def test_seven_points_in_seven_leaves():
+    """Fewer points than a node has children: every level below the root has room for 7 nodes, not 8^L, and the
+    levels of the octree bytes start where those rooms add up to."""
+    need_gpu()
+    from oracle import preprocess_oracle as PO
+    pts = np.array([[0, 0, 0], [1023, 1023, 1023], [40, 0, 0], [0, 40, 0], [511, 512, 500], [512, 511, 500],
+                    [700, 33, 991]], np.int64)
+    pre = pp.preprocess_device(pts, "cuda")
+    origins = exact_against_the_cpu_restatement(pts, 10, pre)
+    assert len(origins) == 7 and [len(b) for b in pre.octree_bytes] == [1, 5, 5, 5, 5, 7]
+    assert pre.octree_pack() == pp.octree_pack_from_origins(origins)
+    host = host_route(pts)
+    assert pre.subtree == host[1] and torch.equal(pre.gt.cpu(), host[2]) and torch.equal(pre.dist.cpu(), host[3])
+    gt_o, dist_o = PO.grids(pts, origins)
+    assert torch.equal(pre.gt.cpu(), torch.from_numpy(gt_o).float())
+    assert torch.equal(pre.dist.cpu(), torch.from_numpy(dist_o).float())
+
+
+@pytest.mark.parametrize("where", ("corner", "centre"))
+@pytest.mark.parametrize("bits", (10, 12))
+def test_a_solid_cube_of_125_leaves(bits, where):
+    """5 x 5 x 5 leaves, one point each, at the origin corner of the volume and straddling its centre planes: the
+    middle block's list holds all 125 blocks in _neighbour_lists' order, the blocks at the rim are clipped."""
+    need_gpu()
+    side = 1 << (bits - 5)
+    first = 0 if where == "corner" else side // 2 - 2
+    cells = np.stack(np.meshgrid(*[first + np.arange(5)] * 3, indexing="ij"), -1).reshape(-1, 3)
+    pts = cells * 32 + np.random.default_rng(bits).integers(0, 32, size=cells.shape)
+    pre = pp.preprocess_device(pts, "cuda", bits=bits)
+    origins = exact_against_the_cpu_restatement(pts, bits, pre)
+    assert len(origins) == 125
+    nb_off, nb_idx = pre.nb_off.cpu().numpy(), pre.nb_idx.cpu().numpy()
+    cell_of = {tuple(c): i for i, c in enumerate((origins // 32).tolist())}
+    steps = sorted(((dx, dy, dz) for dx in range(-2, 3) for dy in range(-2, 3) for dz in range(-2, 3)),
+                   key=lambda s: s[0] * s[0] + s[1] * s[1] + s[2] * s[2])
+    mid = cell_of[(first + 2,) * 3]
+    assert nb_idx[nb_off[mid]:nb_off[mid + 1]].tolist() == [cell_of[tuple(first + 2 + d for d in s)] for s in steps]
+    low = cell_of[(first,) * 3]
+    assert nb_off[low + 1] - nb_off[low] == 27 and nb_idx[nb_off[low]] == low
+    gt, dist = pp.build_grids(pts, origins)                    # the same distance kernel under the host's lists
+    assert pre.gt.shape == (125, 1, 32, 32, 32)
+    assert torch.equal(pre.gt.cpu(), torch.from_numpy(gt).float())
+    assert torch.equal(pre.dist.cpu(), torch.from_numpy(dist).float())
+
+
+def test_out_of_range_at_ten_bits_raises_and_the_next_call_works():
+    need_gpu()
+    good = scattered_cloud()
+    for bad_row in ([5, 1024, 5], [-1, 0, 0]):
+        with pytest.raises(ValueError, match=r"coordinates must lie in \[0, 1024\)"):
+            pp.preprocess_device(np.concatenate([good, [bad_row]]), "cuda", bits=10)
+    with pytest.raises(ValueError, match=r"coordinates must lie in \[0, 1024\)"):          # int32 on the device: no host clamp
+        pp.preprocess_device(torch.tensor([[1, 2, 3], [1024, 0, 0]], dtype=torch.int32, device="cuda"), "cuda", bits=10)
+    exact_against_the_cpu_restatement(good, 10, pp.preprocess_device(good, "cuda", bits=10))
+
+
 def test_sqrt_epilogue_is_exact_for_every_squared_distance():
     """dist = sqrtf(d2) on the device equals float32(sqrt(float64(d2))) for every integer below 2^22, the bound
     thh_select.d2_from_dist documents; gt = (d2 == 0)."""

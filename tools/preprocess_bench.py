@@ -12,7 +12,7 @@ shifts them by (2^bits - 1024) / 2 per axis, to the middle of the deeper volume,
 route (a) is 10-bit only, so only route (b) is timed then.
 
     python tools/preprocess_bench.py                              # the table + one JSON line
-    python tools/preprocess_bench.py --bits 12                    # the deep partition (csrc/pp_deep.hip), route (b) only
+    python tools/preprocess_bench.py --bits 12                    # two more octree levels (D = 7), route (b) only
     rocprofv3 --kernel-trace --stats -d OUT -- python tools/preprocess_bench.py --device-only --calls 5
     python tools/preprocess_bench.py --kernel-stats OUT/.../*_kernel_stats.csv      # the per-kernel split of (b)
 """
