@@ -155,12 +155,19 @@ int nvf_conv3d_k4_mfma_bias(const float* x, const float* wp, const float* bias, 
  * output, so the forward (bit-exact batch invariance) never uses it.
  * dy [batch, 8, din^3]; dx, mask [batch, 8, (din + 3)^3]: dx = mask > 0 ? conv_full(dy, w) : 0 (the ReLU of the layer
  * below).  wp = nvf_pack_mfma_all kind 40 (c0 = c1 = 8) of the layer's gather-form backward weights w_bwd,
- * nvf_pack_wino_k4_floats() floats.  ppc = pairs of output planes per work unit (0: default).  bias_part (optional):
- * *bias_nparts slabs of 8 floats, the channel sums of dx per work unit (the bias gradient of the layer below, a
- * jtotal = 8 job of nvf_wgrad_reduce_multi).  NVF_EINVAL = no instantiation (din 32: conv2, 16: conv1).
- * Two kernels compute this, with the same bits: conv_wino1.hip (one accumulator set per wave, two waves per SIMD: the
- * default, ppc = 0, or bit 16 of ppc set with the low byte = pairs per work unit) and conv_wino.hip (two sets, every plane
- * walked once: an explicit even ppc in the low byte). */
+ * nvf_pack_wino_k4_floats() floats.  bias_part (optional): *bias_nparts slabs of 8 floats, the channel sums of dx per work
+ * unit (the bias gradient of the layer below, a jtotal = 8 job of nvf_wgrad_reduce_multi).  NVF_EINVAL = no instantiation
+ * (din 32: conv2, 16: conv1).
+ * ppc, for these and the three entry points below, names the kernel and its work units.  Every shape has up to two kernels
+ * that give the same bits: "one" (conv_wino1.hip / conv16_wino1.hip: one accumulator set or output plane per wave, two waves
+ * per SIMD) and "two" (conv_wino.hip / conv16_wino.hip: two sets or planes, every input plane walked once per pair).
+ *   bits 0-7   count: pairs of output planes per work unit (output planes in conv16_wino1.hip); 0 = the kernel's default.
+ *              conv_wino.hip takes even counts only (NVF_EINVAL otherwise).
+ *   bits 8-15  debug switches of -DNVF_WINO_DBG=1 tuning builds of conv_wino.hip; ignored by the "one" kernels.  The
+ *              16-channel "two" kernel has none: it reads every bit below bit 16 as its count.
+ *   bit 16     the "one" kernel.  NVF_EINVAL where the shape has none: 16 channels with din 16 or 19, or with bias_part.
+ *   ppc = 0 (count 0 without bit 16) is each shape's default kernel: "one" for 8 channels except the forward with din 19,
+ *   and for 16 channels with din 32 backward without bias_part; "two" elsewhere.  The 16-channel entries reject ppc < 0. */
 size_t nvf_pack_wino_k4_floats(void);
 int nvf_conv3d_k4_wino_bwd(const float* dy, const float* wp, float* dx, const float* mask, int batch, int din, int ppc,
                            float* bias_part, int* bias_nparts, void* stream);
@@ -175,10 +182,8 @@ int nvf_conv3d_k4_wino_fwd(const float* x, const float* wp, const float* bias, f
  * two output planes in flight, the five input planes of a pair walked once per pair.  Training steps only, as above.
  * wp = nvf_pack_mfma_all kind 41 (c0 = c1 = 16) of w_bwd (backward-data) / w_fwd (forward), nvf_pack_wino16_k4_floats()
  * floats.  bwd: dy [batch, 16, din^3] (din 32 / 16), dx, mask [batch, 16, (din + 3)^3]; fwd: x [batch, 16, din^3]
- * (din 35 / 19), y [batch, 16, (din - 3)^3].  ppc = pairs of output planes per work unit (0: default).  bias_part (optional,
- * bwd): *bias_nparts slabs of 16 floats, the channel sums of dx per work unit (a jtotal = 16 job of nvf_wgrad_reduce_multi*).
- * conv2's backward-data without bias_part runs, by default (ppc 0; or bit 16 of ppc with the low byte = output planes per
- * work unit), in conv16_wino1.hip: one output plane in flight per wave, two waves per SIMD -- the same bits. */
+ * (din 35 / 19), y [batch, 16, (din - 3)^3].  ppc: as above.  bias_part (optional, bwd): *bias_nparts slabs of 16 floats,
+ * the channel sums of dx per work unit (a jtotal = 16 job of nvf_wgrad_reduce_multi*). */
 size_t nvf_pack_wino16_k4_floats(void);
 int nvf_conv3d_k4_wino16_bwd(const float* dy, const float* wp, float* dx, const float* mask, int batch, int din, int ppc,
                              float* bias_part, int* bias_nparts, void* stream);

@@ -248,36 +248,49 @@ def pack_wino_k4(w_bwd):
     return wp
 
 
+def _wino_entry(c, name):
+    """The entry point nvf_conv3d_k4_wino_<name> (c = 8 channels) or nvf_conv3d_k4_wino16_<name> (c = 16), and its name."""
+    sym = "nvf_conv3d_k4_wino%s_%s" % ("" if c == 8 else "16", name)
+    return getattr(lib(), sym), sym[4:]
+
+
+def _conv3d_k4_wino_bwd(c, dy, wp, mask, out, bias_part, ppc):
+    import ctypes
+    fn, name = _wino_entry(c, "bwd")
+    _f32(dy, wp, mask)
+    B, di = dy.shape[0], dy.shape[2]
+    shape = (B, c, di + 3, di + 3, di + 3)
+    if dy.shape[1] != c or tuple(mask.shape) != shape:
+        raise RuntimeError("%s: dy [B,%d,n^3], mask [B,%d,(n+3)^3]" % (name, c, c))
+    dx = out if out is not None else torch.empty(shape, device=dy.device)
+    nparts = ctypes.c_int(0)
+    check(fn(_ptr(dy), _ptr(wp), _ptr(dx), _ptr(mask), B, di, int(ppc), None if bias_part is None else int(bias_part),
+             ctypes.byref(nparts) if bias_part is not None else None, _stream()), "nvf_" + name)
+    return dx if bias_part is None else (dx, nparts.value)
+
+
+def _conv3d_k4_wino_fwd(c, x, wp, bias, out, ppc):
+    fn, name = _wino_entry(c, "fwd")
+    _f32(x, wp, bias)
+    B, di = x.shape[0], x.shape[2]
+    if x.shape[1] != c:
+        raise RuntimeError("%s: x [B,%d,n^3]" % (name, c))
+    y = out if out is not None else torch.empty((B, c, di - 3, di - 3, di - 3), device=x.device)
+    check(fn(_ptr(x), _ptr(wp), _ptr(bias), _ptr(y), B, di, int(ppc), _stream()), "nvf_" + name)
+    return y
+
+
 def conv3d_k4_wino_bwd(dy, wp, mask, out=None, bias_part=None, ppc=0):
     """Backward-data of a valid 4^3 convolution (8 -> 8 channels) through the ReLU mask of the layer below, in the
     Winograd (y, x) form: dx = mask > 0 ? conv_full(dy, w) : 0.  ``bias_part``: device address of the slabs that receive
     the channel sums of dx per work unit; returns (dx, number of 8-float slabs) then."""
-    import ctypes
-    _f32(dy, wp, mask)
-    B, c, di = dy.shape[0], dy.shape[1], dy.shape[2]
-    shape = (B, 8, di + 3, di + 3, di + 3)
-    if c != 8 or tuple(mask.shape) != shape:
-        raise RuntimeError("conv3d_k4_wino_bwd: dy [B,8,n^3], mask [B,8,(n+3)^3]")
-    dx = out if out is not None else torch.empty(shape, device=dy.device)
-    nparts = ctypes.c_int(0)
-    check(lib().nvf_conv3d_k4_wino_bwd(_ptr(dy), _ptr(wp), _ptr(dx), _ptr(mask), B, di, int(ppc),
-                                       None if bias_part is None else int(bias_part),
-                                       ctypes.byref(nparts) if bias_part is not None else None, _stream()),
-          "nvf_conv3d_k4_wino_bwd")
-    return dx if bias_part is None else (dx, nparts.value)
+    return _conv3d_k4_wino_bwd(8, dy, wp, mask, out, bias_part, ppc)
 
 
 def conv3d_k4_wino_fwd(x, wp, bias, out=None, ppc=0):
     """relu(conv3d(x, w) + bias) of a valid 4^3 convolution (8 -> 8 channels) in the Winograd (y, x) form -- training steps
     only (rounding-level differences from the direct fixed-order kernel).  wp = pack_wino_k4(w_fwd)."""
-    _f32(x, wp, bias)
-    B, c, di = x.shape[0], x.shape[1], x.shape[2]
-    if c != 8:
-        raise RuntimeError("conv3d_k4_wino_fwd: x [B,8,n^3]")
-    y = out if out is not None else torch.empty((B, 8, di - 3, di - 3, di - 3), device=x.device)
-    check(lib().nvf_conv3d_k4_wino_fwd(_ptr(x), _ptr(wp), _ptr(bias), _ptr(y), B, di, int(ppc), _stream()),
-          "nvf_conv3d_k4_wino_fwd")
-    return y
+    return _conv3d_k4_wino_fwd(8, x, wp, bias, out, ppc)
 
 
 def pack_wino16_k4(w):
@@ -290,31 +303,12 @@ def pack_wino16_k4(w):
 def conv3d_k4_wino16_bwd(dy, wp, mask, out=None, ppc=0, bias_part=None):
     """conv3d_k4_wino_bwd for 16 -> 16 channels (the wide decoder): dx = mask > 0 ? conv_full(dy, w) : 0.  ``bias_part``:
     device address of the slabs that receive the 16 channel sums of dx per work unit; returns (dx, number of slabs) then."""
-    import ctypes
-    _f32(dy, wp, mask)
-    B, c, di = dy.shape[0], dy.shape[1], dy.shape[2]
-    shape = (B, 16, di + 3, di + 3, di + 3)
-    if c != 16 or tuple(mask.shape) != shape:
-        raise RuntimeError("conv3d_k4_wino16_bwd: dy [B,16,n^3], mask [B,16,(n+3)^3]")
-    dx = out if out is not None else torch.empty(shape, device=dy.device)
-    nparts = ctypes.c_int(0)
-    check(lib().nvf_conv3d_k4_wino16_bwd(_ptr(dy), _ptr(wp), _ptr(dx), _ptr(mask), B, di, int(ppc),
-                                         None if bias_part is None else int(bias_part),
-                                         ctypes.byref(nparts) if bias_part is not None else None, _stream()),
-          "nvf_conv3d_k4_wino16_bwd")
-    return dx if bias_part is None else (dx, nparts.value)
+    return _conv3d_k4_wino_bwd(16, dy, wp, mask, out, bias_part, ppc)
 
 
 def conv3d_k4_wino16_fwd(x, wp, bias, out=None, ppc=0):
     """conv3d_k4_wino_fwd for 16 -> 16 channels: relu(conv3d(x, w) + bias), training steps only."""
-    _f32(x, wp, bias)
-    B, c, di = x.shape[0], x.shape[1], x.shape[2]
-    if c != 16:
-        raise RuntimeError("conv3d_k4_wino16_fwd: x [B,16,n^3]")
-    y = out if out is not None else torch.empty((B, 16, di - 3, di - 3, di - 3), device=x.device)
-    check(lib().nvf_conv3d_k4_wino16_fwd(_ptr(x), _ptr(wp), _ptr(bias), _ptr(y), B, di, int(ppc), _stream()),
-          "nvf_conv3d_k4_wino16_fwd")
-    return y
+    return _conv3d_k4_wino_fwd(16, x, wp, bias, out, ppc)
 
 
 def wgrad16_k4_wino_partial(dy, x, slabs, max_slabs=256, zsplit=0):

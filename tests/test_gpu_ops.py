@@ -1211,6 +1211,30 @@ def test_conv2_winograd_kernels_give_the_same_bits(ops):
             assert torch.equal(ops.conv3d_k4_wino_bwd(dev(gy1), wpb, dev(x1), ppc=ppc), dx1), (B, ppc)
 
 
+def test_winograd_entry_points_reject_what_they_cannot_run(ops):
+    """The four Winograd entry points answer NVF_EINVAL -- before any launch -- for a (din, ppc, bias_part) without a kernel:
+    an odd count for the two-set 8-channel kernel, an extent without an instantiation, bit 16 of ppc (the one-plane kernel)
+    for a 16-channel shape that has none (din 16 / 19, or bias sums wanted), and a negative ppc in the 16-channel entries.
+    Every buffer is as large as the largest instantiation needs, whatever the extent named."""
+    from nvfpcc_amd._lib import lib
+    L, EINVAL = lib(), -1
+    big = torch.zeros(16 * 35 ** 3, device="cuda")
+    x, y, mask, wp = (torch.zeros_like(big) for _ in range(4))
+    slabs, nparts = torch.zeros(8192 * 16, device="cuda"), torch.zeros(1, dtype=torch.int32).numpy()
+    p = lambda t: t.data_ptr()
+    s = torch.cuda.current_stream().cuda_stream
+    assert L.nvf_conv3d_k4_wino_bwd(p(x), p(wp), p(y), p(mask), 1, 32, 3, None, None, s) == EINVAL
+    assert L.nvf_conv3d_k4_wino_bwd(p(x), p(wp), p(y), p(mask), 1, 16, 3, None, None, s) == EINVAL
+    assert L.nvf_conv3d_k4_wino_bwd(p(x), p(wp), p(y), p(mask), 1, 17, 0, None, None, s) == EINVAL
+    assert L.nvf_conv3d_k4_wino_fwd(p(x), p(wp), p(mask), p(y), 1, 34, 0, s) == EINVAL
+    assert L.nvf_conv3d_k4_wino16_bwd(p(x), p(wp), p(y), p(mask), 1, 16, 65537, None, None, s) == EINVAL
+    assert L.nvf_conv3d_k4_wino16_bwd(p(x), p(wp), p(y), p(mask), 1, 32, 65537, p(slabs), nparts.ctypes.data, s) == EINVAL
+    assert L.nvf_conv3d_k4_wino16_bwd(p(x), p(wp), p(y), p(mask), 1, 32, -1, None, None, s) == EINVAL
+    assert L.nvf_conv3d_k4_wino16_fwd(p(x), p(wp), p(mask), p(y), 1, 19, 65537, s) == EINVAL
+    torch.cuda.synchronize()
+    assert int(nparts[0]) == 0 and float(y.abs().max()) == 0.0          # nothing ran
+
+
 def _wino_bwd_case(ops, n, B, ppc):
     g = gen(4400 + B + n)
     x = torch.randn(B, 8, n, n, n, generator=g)
