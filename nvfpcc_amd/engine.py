@@ -454,6 +454,7 @@ class TrainEngine:
             # conv1 at large batch: 8 rows x 4 planes on eight waves (variant 5: 34.2 vs 39.4 us at batch 64, 107 vs 120
             # (variant 2) at 256, 402 vs 443 at 917; at batch 16 the default tile: 12.7 vs 17.6).  Every variant runs
             # the same per-output fmaf chain, so the bits -- and encode-at-any-batch == decode-at-batch-1 -- do not change
+            # (eval_forward at 66 blocks against batch 1: tests/test_gpu_decode_bits.py)
             var = 5 if (x.shape[-1] == 19 and x.shape[0] >= 64) else None
             return ops.conv3d_k4_mfma(x, L.wp_f, L.b_eff, 0, 0, act, variant=var)
         osz = tuple(s + 2 * L.pad - L.k + 1 for s in x.shape[2:])
@@ -568,7 +569,8 @@ class TrainEngine:
                                        mask=mask)
         if L.wp_s is not None:
             # up1 at large batch: two planes per wave (variant 2: 55 vs 63 us at batch 256; 173 vs 184 at 917)
-            # up2 at batch <= 64: 8 rows x 2 planes on eight waves (variant 6: 25.3 -> 22.8 us at batch 16; bit-identical);
+            # up2 at batch <= 64: 8 rows x 2 planes on eight waves (variant 6: 25.3 -> 22.8 us at batch 16; bit-identical;
+            # nvf_conv3d_gather's own choice by batch for these layers is held by tests/test_gpu_decode_bits.py);
             # above: 4 rows x 4 planes on eight waves (variant 5: 1027 vs 1149 us at batch 917)
             # up1 in training steps of the default engine: the two channel groups of g on different waves, 256 workgroups of
             # 2 rows x 2 planes (variant 7: another summation order, so not in the strict-trajectory engine)
