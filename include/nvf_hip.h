@@ -57,7 +57,7 @@ int nvf_step_ctx_init(NvfStepCtx* ctx);
  * arithmetic that follows the reference's training trajectory to 1e-7 (torch's conv backward, NVFPCC.py:164-172);
  * 0 (default): the reduced-multiplication forms, statistically equivalent training. */
 int nvf_step_ctx_set_direct(NvfStepCtx* ctx, int on);
-/* Forms of the merged weight-gradient launches (nvf_wgrad_mfma3_partial / nvf_wgrad_trunk5_*) when the context does not
+/* Forms of the merged weight-gradient launches (nvf_wgrad_trunk_partial) when the context does not
  * ask for the direct ones: conv2_zsplit in 0..8 (0 = default 1): z work items of conv2's Winograd gradient; conv1_wino
  * != 0: conv1's gradient in the Winograd form as well.  Each choice is another summation order (agreement to fp32
  * rounding): it belongs to the caller's context, the library reads no environment variable for it.  NVF_EINVAL outside
@@ -203,7 +203,7 @@ int nvf_wgrad16_k4_wino_partial(const float* dy, const float* x, float* slabs, i
  * (and db [8] = channel sums of dy when db is not NULL).  One launch of per-workgroup slabs + the fixed-order reduction
  * (deterministic; fp32 error 4e-6 of max |dw| against 1e-6 for the direct form).  workspace: 512 * (4096 + 8) floats.
  * zsplit: the z steps of a (block, tile group) are split over this many work items (1..8).  In the training step the same
- * body runs as job 0 of nvf_wgrad_trunk5_* (NVF_WGRAD_WINO=0 selects the direct form there). */
+ * body runs as job 0 of nvf_wgrad_trunk_partial (NVF_WGRAD_WINO=0 selects the direct form there). */
 int nvf_wgrad_k4_wino(const float* dy, const float* x, float* dw, float* db, void* workspace, size_t workspace_bytes,
                       int batch, int zsplit, void* stream);
 
@@ -345,7 +345,7 @@ int nvf_stem_bwd_partial(const float* g1, const float* x0, const float* a0, cons
                          float** dw_conv0_slabs, NvfStepCtx* ctx, void* stream);
 
 /* The same work with NO launch of its own (narrow decoder, c0 = 8, c1 = 16, batch <= 32): queued in `ctx`, it runs as the
- * first workgroups of the next five-job weight-gradient launch given that context (nvf_wgrad_trunk5_*), which must also
+ * first workgroups of the next five-job weight-gradient launch given that context (nvf_wgrad_trunk_partial), which must also
  * carry a queued latent tail (nvf_latent_tail_queue: the tail is the only consumer of dx0 inside that launch; its
  * dx_addend argument is ignored there).  The stem's backward depends on g1 alone, exactly like conv0's weight gradient
  * in that launch (autograd backward of network.py:4759-4760, gdn_3d.py:137-159).  Needs an open finals queue
@@ -384,13 +384,6 @@ int nvf_wgrad_partial(const float* p, const float* q, float* dw, void* workspace
 int nvf_wgrad_reduce_multi(const float* const* slabs, float* const* dws, const int* nslabs, const int* jtotals,
                            int n, void* stream);
 
-/* the three matrix-core weight gradients of the narrow trunk in one launch (partial sums only): job 0 = conv2
- * (p = dY [B,8,32^3], q = X [B,8,35^3]), job 1 = up2 (p = X [B,8,16^3], q = dY [B,8,35^3]), job 2 = conv1
- * (p = dY [B,8,16^3], q = X [B,8,19^3]); slabs[j] holds 512 slabs of 4096 / 8000 / 4096 floats, nslabs[j] = number
- * written.  Same kernels and results as three nvf_wgrad_partial calls; two workgroups share a CU. */
-int nvf_wgrad_mfma3_partial(const float* const* ps, const float* const* qs, float* const* slabs, int batch,
-                            int* nslabs, NvfStepCtx* ctx, void* stream);
-
 /* up1's and conv0's weight gradients of the narrow trunk in one launch (partial sums): job 0 = up1 (p = X [B,16,8^3],
  * q = dY [B,8,19^3]), job 1 = conv0 (p = X [B,8,4^3], q = dY [B,16,8^3]).  slabs[j] must hold 512 slabs of 16000
  * floats; nslabs[j] <= 512 at every batch (above 512 work items a workgroup walks several).  Both jobs are VALU tile
@@ -398,43 +391,53 @@ int nvf_wgrad_mfma3_partial(const float* const* ps, const float* const* qs, floa
 int nvf_wgrad_up1_conv0_partial(const float* const* ps, const float* const* qs, float* const* slabs, int batch,
                                 int* nslabs, void* stream);
 
-/* the five weight gradients of the narrow trunk above the stem in ONE launch (partial sums): jobs 0-2 as
- * nvf_wgrad_mfma3_partial (conv2, up2, conv1), jobs 3-4 as nvf_wgrad_up1_conv0_partial (up1, conv0): the two small VALU
- * jobs fill the slots the short matrix-core workgroups leave while conv2's are still running.  slabs[0..2]: 512 slabs of
- * 4096 / 8000 / 4096 floats, slabs[3..4]: 512 slabs of 16000 floats; nslabs[5], every entry <= 512 at every batch.
- * conv0 (job 4) takes one of two forms: on the matrix cores with one slab per block (nslabs[4] = batch) when
- * batch <= 512 and the context does not ask for the direct forms; otherwise the tile job of
- * nvf_wgrad_up1_conv0_partial, capped at 512 slabs.  The matrix-core form sums in another order: it agrees with the
- * separate launch to fp32 rounding, not bit for bit; the tile form keeps the direct summation order.  Like
- * nvf_wgrad_mfma3_partial it carries a queued latent tail as its first workgroup. */
-int nvf_wgrad_trunk5_partial(const float* const* ps, const float* const* qs, float* const* slabs, int batch,
-                             int* nslabs, NvfStepCtx* ctx, void* stream);
-/* ... and, with bias_slabs[0] / bias_slabs[2] non-NULL (entry 1 is ignored), the per-workgroup channel sums of conv2's
- * / conv1's dY: nslabs[j] slabs of 8 floats each, whose sum (a jtotal = 8 job of nvf_wgrad_reduce_multi) is that
- * layer's bias gradient -- the kernel holds every dY tile in registers, and its tiles partition dY. */
-int nvf_wgrad_trunk5_partial_bias(const float* const* ps, const float* const* qs, float* const* slabs,
-                                  float* const* bias_slabs, int batch, int* nslabs, NvfStepCtx* ctx, void* stream);
-/* ... and the weight gradients of the narrow decoder's three classifier heads (the contract of
- * nvf_heads3_wgrad_partial: three entries each, at most head_max_slabs slabs of cs[h] * 27 floats) as further workgroups
- * of the same launch: they depend on nothing it produces and run in the slots its other jobs leave. */
-int nvf_wgrad_trunk5_heads_partial(const float* const* ps, const float* const* qs, float* const* slabs,
-                                   float* const* bias_slabs, const float* const* head_dls, const float* const* head_xs,
-                                   float* const* head_slabs, int head_max_slabs, int batch, int* nslabs,
-                                   int* head_nslabs, NvfStepCtx* ctx, void* stream);
-/* ... and the FIRST pass of nvf_multi_channel_sum over sum_xs (bias gradients sum_outs that no other kernel leaves
- * behind) as further workgroups of the launch; its final pass is queued in ctx (an open nvf_finals_begin) or launched
- * here.  sum_workspace: nvf_multi_channel_sum_workspace(total channels) bytes, untouched until the flush.  With the
- * partial sums made here, no final pass of the step reads what the slab reduction writes: nvf_wgrad_reduce_finals_tail.
- * coef_src / coef_live (both or neither): the launch copies two floats (the optimiser's step coefficients) from
- * coef_src to coef_live for that call. */
-int nvf_wgrad_trunk5_heads_sums_partial(const float* const* ps, const float* const* qs, float* const* slabs,
-                                        float* const* bias_slabs, const float* const* head_dls,
-                                        const float* const* head_xs, float* const* head_slabs, int head_max_slabs,
-                                        const float* const* sum_xs, float* const* sum_outs, const int* sum_channels,
-                                        const int* sum_spatials, int sum_n, void* sum_workspace,
-                                        size_t sum_workspace_bytes, const float* coef_src, float* coef_live,
-                                        int batch, int* nslabs, int* head_nslabs,
-                                        NvfStepCtx* ctx, void* stream);
+/* The weight gradients of the narrow trunk above the stem in ONE launch (partial sums only), with what rides along.
+ * Jobs (ps[j], qs[j], slabs[j], nslabs[j]), in this order; slabs[j] must hold 512 slabs of the size given:
+ *   0 conv2: p = dY [B,8,32^3], q = X [B,8,35^3],  4096 floats     1 up2: p = X [B,8,16^3], q = dY [B,8,35^3],  8000
+ *   2 conv1: p = dY [B,8,16^3], q = X [B,8,19^3],  4096            3 up1: p = X [B,16,8^3], q = dY [B,8,19^3], 16000
+ *   4 conv0: p = X [B,8,4^3],   q = dY [B,16,8^3], 16000
+ * nslabs[j] receives the number written (<= 512 at every batch), to be added by nvf_wgrad_reduce_multi*.  njobs = 3:
+ * jobs 0-2, the kernels and results of three nvf_wgrad_partial calls.  njobs = 5: all five, jobs 0-3 with the same
+ * bits; the two small jobs fill the slots the short matrix-core workgroups leave while conv2's are still running.
+ * conv0 takes one of two forms: on the matrix cores with one slab per block (nslabs[4] = batch) when batch <= 512 and
+ * the context does not ask for the direct forms; otherwise the tile job of nvf_wgrad_up1_conv0_partial, capped at 512
+ * slabs.  The matrix-core form sums in another order: it agrees with that launch to fp32 rounding, not bit for bit.
+ * What rides along (a NULL / zero group is absent, a partly given one NVF_EINVAL; all but the first need njobs = 5):
+ *   - a latent tail queued in ctx as the first workgroup, behind a queued stem backward (nvf_stem_bwd_queue) if any;
+ *   - bias_slabs: three entries, entry 1 ignored; with bias_slabs[0] / bias_slabs[2] non-NULL the per-workgroup channel
+ *     sums of conv2's / conv1's dY: nslabs[j] slabs of 8 floats each, whose sum (a jtotal = 8 reduction job) is that
+ *     layer's bias gradient -- the kernel holds every dY tile in registers, and its tiles partition dY;
+ *   - head_*: the weight gradients of the narrow decoder's three classifier heads (the contract of
+ *     nvf_heads3_wgrad_partial: three entries each, at most head_max_slabs slabs of cs[h] * 27 floats) as further
+ *     workgroups: they depend on nothing the launch produces and run in the slots its other jobs leave;
+ *   - sum_* (needs head_*): the FIRST pass of nvf_multi_channel_sum over sum_xs (bias gradients sum_outs that no other
+ *     kernel leaves behind) into sum_workspace (nvf_multi_channel_sum_workspace(total channels) bytes, NVF_EWORKSPACE
+ *     if fewer; untouched until the flush); the final pass is queued in ctx (an open nvf_finals_begin) or launched
+ *     here.  Then no final pass of the step reads what the slab reduction writes: nvf_wgrad_reduce_finals_tail;
+ *   - coef_src / coef_live (both or neither; needs sum_*): two floats, the optimiser's step coefficients, copied.
+ * A refused request launches nothing and leaves ctx as it was.  nvf_trunk_wgrads_bytes(): sizeof, for bindings. */
+typedef struct NvfTrunkWgrads {
+  const float* const* ps;
+  const float* const* qs;
+  float* const* slabs;
+  int32_t* nslabs;
+  float* const* bias_slabs;
+  const float* const* head_dls;
+  const float* const* head_xs;
+  float* const* head_slabs;
+  int32_t* head_nslabs;
+  const float* const* sum_xs;
+  float* const* sum_outs;
+  const int32_t* sum_channels;
+  const int32_t* sum_spatials;
+  void* sum_workspace;
+  uint64_t sum_workspace_bytes;
+  const float* coef_src;
+  float* coef_live;
+  int32_t batch, njobs, head_max_slabs, sum_n;
+} NvfTrunkWgrads;
+size_t nvf_trunk_wgrads_bytes(void);
+int nvf_wgrad_trunk_partial(const NvfTrunkWgrads* req, NvfStepCtx* ctx, void* stream);
 
 /* per-channel sum over batch and space: out[c] (+)= sum x[b,c,:]  (bias gradients);
  * two launches through a caller-owned workspace of nvf_channel_sum_workspace(c) bytes */
@@ -449,14 +452,9 @@ int nvf_multi_channel_sum(const float* const* xs, float* const* outs, const int*
                           void* stream);
 
 /* nvf_wgrad_reduce_multi and the partial pass of nvf_multi_channel_sum in one launch (independent work), then the
- * bias sums' final pass; same results as the two separate calls */
-int nvf_wgrad_reduce_multi_and_sums(const float* const* slabs, float* const* dws, const int* nslabs,
-                                    const int* jtotals, int n, const float* const* xs, float* const* outs,
-                                    const int* channels, const int* spatials, int ntensors, int batch,
-                                    void* workspace, size_t workspace_bytes, NvfStepCtx* ctx, void* stream);
-/* ... with per-gradient addends (addends[i], or addends itself, may be NULL: dws[i][j] = sum of slabs + addends[i][j] --
- * the weight-rate gradient of nvf_step_head's rate job) and, optionally, the optimiser applied to every element it
- * writes (adam NULL: none). */
+ * bias sums' final pass; same results as the two separate calls.  Per-gradient addends (addends[i], or addends itself,
+ * may be NULL: dws[i][j] = sum of slabs + addends[i][j] -- the weight-rate gradient of nvf_step_head's rate job) and,
+ * optionally, the optimiser applied to every element it writes (adam NULL: none). */
 int nvf_wgrad_reduce_multi_and_sums_fused(const float* const* slabs, float* const* dws, const int* nslabs,
                                           const int* jtotals, int n, const float* const* addends,
                                           const NvfAdamFuse* adam, const float* const* xs, float* const* outs,
@@ -466,7 +464,7 @@ int nvf_wgrad_reduce_multi_and_sums_fused(const float* const* slabs, float* cons
 /* The latent tail of a training step (backward of NVFPCC.py:186-196's latent generator on [batch, c <= 8, spatial]
  * tensors): gradient of the latent rate (+ dx_addend) -> GDN backward -> 1x1x1 weight and bias gradients, i.e.
  * nvf_latent_rate (want_grad) + nvf_gdn_bwd + nvf_wgrad + the bias sum.  Queued in `ctx`, it runs as ONE workgroup of
- * the next nvf_wgrad_mfma3_partial / nvf_wgrad_trunk5_partial or nvf_wgrad_reduce_multi_and_sums call that is given the
+ * the next nvf_wgrad_trunk_partial or nvf_wgrad_reduce_multi_and_sums_fused call that is given the
  * same ctx, whichever comes first (every input must already be enqueued on that call's stream), instead of three
  * dependent launches.  NVF_EINVAL: ctx is not an initialised context, or another tail is pending in it. */
 int nvf_latent_tail_queue(NvfStepCtx* ctx, const float* lat, const int64_t* block_ids, const float* sigma, const float* mu,
@@ -529,7 +527,7 @@ int nvf_weight_rate_batch(const float* const* kernels, float* const* dks, const 
 /* The same rate term split so that its partial pass can ride in the step head (it depends on the parameters only, not
  * on the mini-batch): nvf_step_head given a job computes the per-workgroup partial sums into job->part
  * (nvf_weight_rate_batch_workspace() bytes) and WRITES g * dbits/dk to job->dk[l] (not accumulated: the caller hands
- * those buffers to nvf_wgrad_reduce_multi_and_sums as addends); nvf_weight_rate_batch_final then adds the partials in
+ * those buffers to nvf_wgrad_reduce_multi_and_sums_fused as addends); nvf_weight_rate_batch_final then adds the partials in
  * the usual fixed order (queued in ctx between nvf_finals_begin / nvf_finals_flush, like nvf_weight_rate_batch's). */
 typedef struct NvfRateJob {
   const float* kernel[8];
@@ -546,7 +544,7 @@ int nvf_weight_rate_batch_final(const NvfRateJob* job, float* bits, float* dsigm
 
 
 /* ---- deferred final passes ------------------------------------------------------
- * nvf_focal_loss_multi, nvf_multi_channel_sum / nvf_wgrad_reduce_multi_and_sums and nvf_weight_rate_batch end with a
+ * nvf_focal_loss_multi, nvf_multi_channel_sum / nvf_wgrad_reduce_multi_and_sums_fused and nvf_weight_rate_batch end with a
  * tiny launch that adds per-workgroup partial sums in a fixed order.  Between nvf_finals_begin(ctx) and
  * nvf_finals_flush(ctx, stream) the final passes of calls given that ctx (at most one of each kind; further ones are
  * launched as usual) are queued in the context and flush runs them in ONE launch on `stream`: their outputs (the loss
@@ -666,7 +664,7 @@ int nvf_finals_flush_tail(NvfStepCtx* ctx, const NvfStepTail* tail, const int64_
  * nvf_finals_flush_tail in ONE launch -- for steps whose queued final passes read nothing that reduction writes.
  * Only the final passes' workgroups wait for one another before the schedule hand-over, so the reduction must read
  * nothing from the step buffer: adam->coef_dev may not point into tail->sched_buf (NVF_EINVAL) -- use the copy that
- * nvf_wgrad_trunk5_heads_sums_partial(coef_src, coef_live) staged earlier in the step, or host coefficients. */
+ * nvf_wgrad_trunk_partial (coef_src, coef_live) staged earlier in the step, or host coefficients. */
 int nvf_wgrad_reduce_finals_tail(const float* const* slabs, float* const* dws, const int* nslabs, const int* jtotals,
                                  int n, const float* const* addends, const NvfAdamFuse* adam, NvfStepCtx* ctx,
                                  const NvfStepTail* tail, const int64_t* ranges, int nranges, void* stream);

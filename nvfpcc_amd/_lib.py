@@ -72,19 +72,15 @@ PROTOTYPES = {
     "nvf_wgrad": (I, [P, P, P, P, Z] + [I] * 15 + [P]),
     "nvf_wgrad_partial": (I, [P, P, P, P, Z] + [I] * 14 + [P, P]),
     "nvf_wgrad_reduce_multi": (I, [P, P, P, P, I, P]),
-    "nvf_wgrad_mfma3_partial": (I, [P, P, P, I, P, P, P]),
     "nvf_wgrad_up1_conv0_partial": (I, [P, P, P, I, P, P]),
-    "nvf_wgrad_trunk5_partial": (I, [P, P, P, I, P, P, P]),
-    "nvf_wgrad_trunk5_partial_bias": (I, [P, P, P, P, I, P, P, P]),
-    "nvf_wgrad_trunk5_heads_partial": (I, [P, P, P, P, P, P, P, I, I, P, P, P, P]),
-    "nvf_wgrad_trunk5_heads_sums_partial": (I, [P, P, P, P, P, P, P, I, P, P, P, P, I, P, Z, P, P, I, P, P, P, P]),
+    "nvf_trunk_wgrads_bytes": (Z, []),
+    "nvf_wgrad_trunk_partial": (I, [P, P, P]),
     "nvf_wgrad_reduce_finals_tail": (I, [P, P, P, P, I, P, P, P, P, P, I, P]),
     "nvf_wgrad_reduce_finals": (I, [P, P, P, P, I, P, P, P]),
     "nvf_channel_sum_workspace": (Z, [I]),
     "nvf_channel_sum": (I, [P, P, P, Z, I, I, I, I, P]),
     "nvf_multi_channel_sum_workspace": (Z, [I]),
     "nvf_multi_channel_sum": (I, [P, P, P, P, I, I, P, Z, P, P]),
-    "nvf_wgrad_reduce_multi_and_sums": (I, [P, P, P, P, I, P, P, P, P, I, I, P, Z, P, P]),
     "nvf_latent_tail_queue": (I, [P, P, P, P, P, P, P, P, P, P, F, I, U, U, P, P, P, P, P, P, P, P, P, P, I, I, I]),
     "nvf_stem_bwd_queue": (I, [P] * 16 + [Z, P, I, I, I, I, P]),
     "nvf_stem_bwd_pending": (I, [P]),
@@ -181,6 +177,14 @@ class NvfAdamFuse(C.Structure):
     _fields_ = [("g_base", P), ("p_base", P), ("m_base", P), ("v_base", P), ("n", L), ("coef_dev", P),
                 ("coef0_host", F), ("coef1_host", F), ("beta1", F), ("beta2", F), ("eps", F), ("reserved", F),
                 ("bad_count", P)]
+
+
+class NvfTrunkWgrads(C.Structure):
+    """include/nvf_hip.h: typedef struct NvfTrunkWgrads (field for field)."""
+    _fields_ = [(n, P) for n in ("ps", "qs", "slabs", "nslabs", "bias_slabs", "head_dls", "head_xs", "head_slabs",
+                                 "head_nslabs", "sum_xs", "sum_outs", "sum_channels", "sum_spatials", "sum_workspace")] + \
+               [("sum_workspace_bytes", U), ("coef_src", P), ("coef_live", P)] + \
+               [(n, C.c_int32) for n in ("batch", "njobs", "head_max_slabs", "sum_n")]
 
 
 class NvfPcSparseIndex(C.Structure):

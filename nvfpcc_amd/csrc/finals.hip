@@ -110,7 +110,7 @@ extern "C" int nvf_step_ctx_set_wgrad_forms(NvfStepCtx* ctx, int conv2_zsplit, i
   return NVF_OK;
 }
 
-// Start queueing the final passes of nvf_focal_loss_multi, nvf_wgrad_reduce_multi_and_sums / nvf_multi_channel_sum
+// Start queueing the final passes of nvf_focal_loss_multi, nvf_wgrad_reduce_multi_and_sums_fused / nvf_multi_channel_sum
 // and nvf_weight_rate_batch issued with this context (at most one of each kind; a second one is launched as usual).
 // NVF_EINVAL: not an initialised context, or a queue is already open on it.
 extern "C" int nvf_finals_begin(NvfStepCtx* ctx) {

@@ -230,7 +230,7 @@ extern "C" int nvf_stem_bwd_partial(const float* g1, const float* x0, const floa
 }
 
 // The stem's backward as the FIRST workgroups of the next five-gradient launch given this context
-// (nvf_wgrad_trunk5_heads_sums_partial and its siblings with five jobs) instead of two launches of its own: stem_bwd.h.
+// (nvf_wgrad_trunk_partial with five jobs) instead of two launches of its own: stem_bwd.h.
 // Needs a queued latent tail in the same context by the time of that launch (the tail consumes dx0 inside it) and an open
 // finals queue (nvf_finals_begin: the IGDN parameter gradients are a deferred final pass, as in nvf_stem_bwd_partial).
 // Narrow decoder only (c0 = 8, c1 = 16), batch <= kStemCoopMaxBatch.  Outputs as nvf_stem_bwd_partial, plus

@@ -741,7 +741,7 @@ __global__ __launch_bounds__(256) void wgrad_s2k5_mfma(const float* __restrict__
 // let two workgroups share a CU, so the second kernel's workgroups run in the first one's bubbles.  Same bodies, same
 // slabs, same results as three launches.
 // the latent tail queued in the caller's NvfStepCtx by nvf_latent_tail_queue: consumed by the next
-// nvf_wgrad_mfma3_partial / nvf_wgrad_trunk5_partial or nvf_wgrad_reduce_multi_and_sums call with that context
+// nvf_wgrad_trunk_partial or nvf_wgrad_reduce_multi_and_sums_fused call with that context
 
 #ifndef NVF_SUM_T
 #define NVF_SUM_T 512      // threads that load a row (256: 17.6 us for the step's reduction launch, 512 / 1024: 15.9)
@@ -979,7 +979,7 @@ __global__ __launch_bounds__(256) void wgrad_mfma3_kernel(WgMfma3 m, WgTiled2 u,
   multi_channel_sum_partial_body<256>(sums, sum_part, bid % sums.total_channels, bid / sums.total_channels, lds);
 }
 
-// geometry of the up1 / conv0 jobs (nvf_wgrad_up1_conv0_partial, nvf_wgrad_trunk5_partial)
+// geometry of the up1 / conv0 jobs (nvf_wgrad_up1_conv0_partial, nvf_wgrad_trunk_partial)
 template <class U0, class U1>
 static void fill_up1_conv0(WgTiled2& m, const float* const* ps, const float* const* qs, float* const* slabs, int batch,
                            int* nslabs) {
@@ -1000,30 +1000,48 @@ static void fill_up1_conv0(WgTiled2& m, const float* const* ps, const float* con
   }
 }
 
-// njobs = 3: conv2, up2, conv1 (matrix cores); njobs = 5: + up1, conv0 (the VALU tile kernel with 256-thread workgroups)
-struct HeadsJob {                       // optional: the heads' gradients in the same launch (njobs = 5 only)
-  const float* const* dls;
-  const float* const* xs;
-  float* const* slabs;
-  int max_slabs;
-  int* nslabs;
-};
-struct SumsJob {                        // optional: partial channel sums (nvf_multi_channel_sum's first pass) in the launch
-  MultiSumDesc d;
-  float* part;
-  const float* coef_src;                // optional: two floats copied to coef_live by the launch
-  float* coef_live;
-};
+static int fill_sum_desc(const float* const* xs, float* const* outs, const int* channels, const int* spatials,
+                         int ntensors, int batch, MultiSumDesc& d) {
+  if (!xs || !outs || !channels || !spatials || ntensors <= 0 || ntensors > 12 || batch <= 0) return NVF_EINVAL;
+  int cb = 0;
+  for (int i = 0; i < ntensors; ++i) {
+    if (!xs[i] || !outs[i] || channels[i] <= 0 || spatials[i] <= 0) return NVF_EINVAL;
+    d.x[i] = xs[i]; d.out[i] = outs[i]; d.c[i] = channels[i]; d.spatial[i] = spatials[i]; d.chan_base[i] = cb;
+    cb += channels[i];
+  }
+  d.ntensors = ntensors; d.batch = batch; d.total_channels = cb;
+  d.nchunk = batch < kSumChunks ? batch : kSumChunks;   // groups of consecutive batch entries
+  return NVF_OK;
+}
 
-static int launch_trunk_wgrads(const float* const* ps, const float* const* qs, float* const* slabs, int batch,
-                               int* nslabs, int njobs, NvfStepCtx* ctx, void* stream,
-                               float* const* bias_slabs = nullptr, const HeadsJob* heads = nullptr,
-                               const SumsJob* sums = nullptr) {
-  if (!ps || !qs || !slabs || !nslabs || batch <= 0) return NVF_EINVAL;
-  using C0 = MCfg<32, 4, 4>; using T1 = TWCfg<2, 2>; using C2 = MCfg<16, 2, 8>;
-  using U0 = WCfg<16, 5, 2, 2, 8, 4, 2, 0>; using U1 = WCfg<8, 5, 2, 2, 4, 4, 4, 0>;
+// The trunk's weight gradients in one launch, with what rides along: the contract is nvf_wgrad_trunk_partial's in
+// include/nvf_hip.h.  Every refusal comes before the first launch and before a pending flag of the context is cleared.
+static int launch_trunk_wgrads(const NvfTrunkWgrads& r, NvfStepCtx* ctx, void* stream) {
+  const int batch = r.batch, njobs = r.njobs;
+  const float* const* ps = r.ps;
+  const float* const* qs = r.qs;
+  float* const* slabs = r.slabs;
+  int* nslabs = r.nslabs;
+  if (!ps || !qs || !slabs || !nslabs || batch <= 0 || (njobs != 3 && njobs != 5)) return NVF_EINVAL;
   for (int j = 0; j < njobs; ++j)
     if (!ps[j] || !qs[j] || !slabs[j]) return NVF_EINVAL;
+  // a group is given whole or not at all; the workgroup ranges put the heads' job in front of the sums, and the sums'
+  // first workgroup is the one that copies the coefficients
+  const bool heads = r.head_dls || r.head_xs || r.head_slabs || r.head_nslabs || r.head_max_slabs;
+  const bool sums = r.sum_xs || r.sum_outs || r.sum_channels || r.sum_spatials || r.sum_n || r.sum_workspace ||
+                    r.sum_workspace_bytes;
+  if (heads && (!r.head_dls || !r.head_xs || !r.head_slabs || !r.head_nslabs || r.head_max_slabs <= 0)) return NVF_EINVAL;
+  if ((heads || r.bias_slabs) && njobs != 5) return NVF_EINVAL;
+  if ((sums && (!heads || !r.sum_workspace)) || (!r.coef_src != !r.coef_live) || (r.coef_live && !sums)) return NVF_EINVAL;
+  MultiSumDesc sd{};
+  if (sums) {
+    const int rc = fill_sum_desc(r.sum_xs, r.sum_outs, r.sum_channels, r.sum_spatials, r.sum_n, batch, sd);
+    if (rc != NVF_OK) return rc;
+    if (r.sum_workspace_bytes < nvf_multi_channel_sum_workspace(sd.total_channels)) return NVF_EWORKSPACE;
+  }
+  float* const spart = (float*)r.sum_workspace;
+  using C0 = MCfg<32, 4, 4>; using T1 = TWCfg<2, 2>; using C2 = MCfg<16, 2, 8>;
+  using U0 = WCfg<16, 5, 2, 2, 8, 4, 2, 0>; using U1 = WCfg<8, 5, 2, 2, 4, 4, 4, 0>;
   WgMfma3 m{};
   const int items[3] = {batch * (32 / 4) * (32 / 4), batch * (16 / 2) * (16 / 2), batch * (16 / 8) * (16 / 2)};
   for (int j = 0; j < 3; ++j) {
@@ -1055,7 +1073,7 @@ static int launch_trunk_wgrads(const float* const* ps, const float* const* qs, f
     // 2e-5 of the reference's (entries whose gradient is rounding noise take Adam's first steps with the other sign)
     const bool wino1 = nvf_ctx_ok(ctx) && ctx->wg_conv1_wino;
     if (j == 2 && wino1 && !direct) n = wino_items(d, batch, 1, cap, WgWino1::NGRP);
-    if (bias_slabs && j != 1) d.bias_slab = bias_slabs[j];     // conv2 (job 0) and conv1 (job 2): p = dY
+    if (r.bias_slabs && j != 1) d.bias_slab = r.bias_slabs[j];     // conv2 (job 0) and conv1 (job 2): p = dY
     m.d[j] = d; m.n[j] = n; nslabs[j] = n;
   }
   WgTiled2 u{};
@@ -1091,22 +1109,12 @@ static int launch_trunk_wgrads(const float* const* ps, const float* const* qs, f
   }
   HeadsW3 hw{};
   if (heads) {
-    if (njobs != 5) return NVF_EINVAL;
-    const int rc = heads3_wgrad_mfma_fill<HeadW0, HeadW1, HeadW2>(hw, heads->dls, heads->xs, heads->slabs, batch,
-                                                                  heads->max_slabs, heads->nslabs);
+    const int rc = heads3_wgrad_mfma_fill<HeadW0, HeadW1, HeadW2>(hw, r.head_dls, r.head_xs, r.head_slabs, batch,
+                                                                  r.head_max_slabs, r.head_nslabs);
     if (rc != NVF_OK) return rc;
     grid += hw.n[0] + hw.n[1] + hw.n[2];
   }
-  MultiSumDesc sd{};
-  float* spart = nullptr;
-  const float* csrc = nullptr;
-  float* clive = nullptr;
-  if (sums) {
-    if (!heads) return NVF_EINVAL;        // the block ranges assume the heads' job in front of the sums
-    sd = sums->d; spart = sums->part;
-    grid += sd.total_channels * sd.nchunk;
-    csrc = sums->coef_src; clive = sums->coef_live;
-  }
+  if (sums) grid += sd.total_channels * sd.nchunk;
   if (nvf_ctx_ok(ctx) && ctx->stem_pending) {
     // a queued stem backward (nvf_stem_bwd_queue) rides in front of the tail it feeds: both or neither
     if (!ctx->tail_pending || njobs != 5 || ctx->stem.batch != batch ||
@@ -1120,101 +1128,24 @@ static int launch_trunk_wgrads(const float* const* ps, const float* const* qs, f
             u.nx[1] * u.ny[1], hw.n[0] + hw.n[1] + hw.n[2], sd.total_channels * sd.nchunk);
 #endif
     wgrad_mfma3_kernel<C0, T1, C2, U0, U1, true, true><<<nstem + 1 + grid, 256, 0, nvf_stream(stream)>>>(
-        m, u, ctx->tail, hw, sd, spart, csrc, clive, ctx->stem);
+        m, u, ctx->tail, hw, sd, spart, r.coef_src, r.coef_live, ctx->stem);
   } else if (nvf_ctx_ok(ctx) && ctx->tail_pending) {
     ctx->tail_pending = 0;
-    wgrad_mfma3_kernel<C0, T1, C2, U0, U1, true, false><<<1 + grid, 256, 0, nvf_stream(stream)>>>(m, u, ctx->tail, hw, sd, spart, csrc, clive, StemBwdJob{});
+    wgrad_mfma3_kernel<C0, T1, C2, U0, U1, true, false><<<1 + grid, 256, 0, nvf_stream(stream)>>>(m, u, ctx->tail, hw, sd, spart, r.coef_src, r.coef_live, StemBwdJob{});
   } else {
-    wgrad_mfma3_kernel<C0, T1, C2, U0, U1, false, false><<<grid, 256, 0, nvf_stream(stream)>>>(m, u, LatentTail{}, hw, sd, spart, csrc, clive, StemBwdJob{});
+    wgrad_mfma3_kernel<C0, T1, C2, U0, U1, false, false><<<grid, 256, 0, nvf_stream(stream)>>>(m, u, LatentTail{}, hw, sd, spart, r.coef_src, r.coef_live, StemBwdJob{});
   }
   NVF_LAUNCH_CHECK();
-  return NVF_OK;
-}
-
-// job 0: conv2 (p = dY [B,8,32^3], q = X [B,8,35^3]); job 1: up2 (p = X [B,8,16^3], q = dY [B,8,35^3]);
-// job 2: conv1 (p = dY [B,8,16^3], q = X [B,8,19^3]).  slabs[j] must hold 512 slabs of 4096 / 8000 / 4096 floats;
-// nslabs[j] receives the number written (to be added by nvf_wgrad_reduce_multi).
-extern "C" int nvf_wgrad_mfma3_partial(const float* const* ps, const float* const* qs, float* const* slabs, int batch,
-                                       int* nslabs, NvfStepCtx* ctx, void* stream) {
-  return launch_trunk_wgrads(ps, qs, slabs, batch, nslabs, 3, ctx, stream);
-}
-
-// ... and jobs 3, 4 = up1 (p = X [B,16,8^3], q = dY [B,8,19^3]), conv0 (p = X [B,8,4^3], q = dY [B,16,8^3]) of
-// nvf_wgrad_up1_conv0_partial in the same launch: all five weight gradients of the narrow trunk above the stem.
-// slabs[3], slabs[4]: room for 512 slabs of 16000 floats each; no job reports more than 512.  conv2 / up2 / conv1 / up1
-// give the bits of nvf_wgrad_mfma3_partial and of the direct forms' choices there.  conv0 runs on the matrix cores (one
-// slab per block) at batch <= 512 unless the context asks for the direct forms, and agrees with
-// nvf_wgrad_up1_conv0_partial to rounding, not bit for bit; above 512 blocks, or with the direct forms, it is the tile
-// job capped at 512 slabs.
-extern "C" int nvf_wgrad_trunk5_partial(const float* const* ps, const float* const* qs, float* const* slabs, int batch,
-                                        int* nslabs, NvfStepCtx* ctx, void* stream) {
-  return launch_trunk_wgrads(ps, qs, slabs, batch, nslabs, 5, ctx, stream);
-}
-
-// ... and, with bias_slabs[0] / bias_slabs[2] (either may be NULL; entry 1 is ignored), the channel sums of conv2's and
-// conv1's dY per workgroup: nslabs[j] slabs of 8 floats whose sum (nvf_wgrad_reduce_multi, jtotal 8) is the bias
-// gradient of that layer -- the kernel holds every dY tile in registers anyway, and the tiles partition dY.
-extern "C" int nvf_wgrad_trunk5_partial_bias(const float* const* ps, const float* const* qs, float* const* slabs,
-                                             float* const* bias_slabs, int batch, int* nslabs, NvfStepCtx* ctx,
-                                             void* stream) {
-  return launch_trunk_wgrads(ps, qs, slabs, batch, nslabs, 5, ctx, stream, bias_slabs);
-}
-
-// ... and the weight gradients of the narrow decoder's three classifier heads (nvf_heads3_wgrad_partial's contract:
-// head_dls / head_xs / head_slabs / head_nslabs have three entries, at most head_max_slabs slabs each) as further
-// workgroups of the same launch.
-extern "C" int nvf_wgrad_trunk5_heads_partial(const float* const* ps, const float* const* qs, float* const* slabs,
-                                              float* const* bias_slabs, const float* const* head_dls,
-                                              const float* const* head_xs, float* const* head_slabs,
-                                              int head_max_slabs, int batch, int* nslabs, int* head_nslabs,
-                                              NvfStepCtx* ctx, void* stream) {
-  if (!head_dls || !head_xs || !head_slabs || !head_nslabs || head_max_slabs <= 0) return NVF_EINVAL;
-  const HeadsJob h{head_dls, head_xs, head_slabs, head_max_slabs, head_nslabs};
-  return launch_trunk_wgrads(ps, qs, slabs, batch, nslabs, 5, ctx, stream, bias_slabs, &h);
-}
-
-static int fill_sum_desc(const float* const* xs, float* const* outs, const int* channels, const int* spatials,
-                         int ntensors, int batch, MultiSumDesc& d) {
-  if (!xs || !outs || !channels || !spatials || ntensors <= 0 || ntensors > 12 || batch <= 0) return NVF_EINVAL;
-  int cb = 0;
-  for (int i = 0; i < ntensors; ++i) {
-    if (!xs[i] || !outs[i] || channels[i] <= 0 || spatials[i] <= 0) return NVF_EINVAL;
-    d.x[i] = xs[i]; d.out[i] = outs[i]; d.c[i] = channels[i]; d.spatial[i] = spatials[i]; d.chan_base[i] = cb;
-    cb += channels[i];
+  if (sums && !nvf_finals_push_sums(ctx, sd, spart)) {
+    multi_channel_sum_final<<<(sd.total_channels + 63) / 64, 64, 0, nvf_stream(stream)>>>(sd, spart);
+    NVF_LAUNCH_CHECK();
   }
-  d.ntensors = ntensors; d.batch = batch; d.total_channels = cb;
-  d.nchunk = batch < kSumChunks ? batch : kSumChunks;
   return NVF_OK;
 }
 
-// ... and the first pass of nvf_multi_channel_sum over sum_xs (the bias gradients sum_outs no other kernel leaves
-// behind) as further workgroups of the launch; its final pass is queued in ctx (nvf_finals_begin must be open) or
-// launched here.  sum_workspace: nvf_multi_channel_sum_workspace(total channels) bytes, untouched until the flush.
-// coef_src / coef_live (both or neither): two floats copied by the launch (see nvf_wgrad_reduce_finals_tail).
-extern "C" int nvf_wgrad_trunk5_heads_sums_partial(const float* const* ps, const float* const* qs, float* const* slabs,
-                                                   float* const* bias_slabs, const float* const* head_dls,
-                                                   const float* const* head_xs, float* const* head_slabs,
-                                                   int head_max_slabs, const float* const* sum_xs,
-                                                   float* const* sum_outs, const int* sum_channels,
-                                                   const int* sum_spatials, int sum_n, void* sum_workspace,
-                                                   size_t sum_workspace_bytes, const float* coef_src,
-                                                   float* coef_live, int batch, int* nslabs, int* head_nslabs,
-                                                   NvfStepCtx* ctx, void* stream) {
-  if (!head_dls || !head_xs || !head_slabs || !head_nslabs || head_max_slabs <= 0 || !sum_workspace) return NVF_EINVAL;
-  if ((coef_src == nullptr) != (coef_live == nullptr)) return NVF_EINVAL;
-  const HeadsJob h{head_dls, head_xs, head_slabs, head_max_slabs, head_nslabs};
-  SumsJob sj{};
-  const int rc = fill_sum_desc(sum_xs, sum_outs, sum_channels, sum_spatials, sum_n, batch, sj.d);
-  if (rc != NVF_OK) return rc;
-  if (sum_workspace_bytes < nvf_multi_channel_sum_workspace(sj.d.total_channels)) return NVF_EWORKSPACE;
-  sj.part = (float*)sum_workspace;
-  sj.coef_src = coef_src; sj.coef_live = coef_live;
-  const int rc2 = launch_trunk_wgrads(ps, qs, slabs, batch, nslabs, 5, ctx, stream, bias_slabs, &h, &sj);
-  if (rc2 != NVF_OK) return rc2;
-  if (!nvf_finals_push_sums(ctx, sj.d, sj.part))
-    multi_channel_sum_final<<<(sj.d.total_channels + 63) / 64, 64, 0, nvf_stream(stream)>>>(sj.d, sj.part);
-  NVF_LAUNCH_CHECK();
-  return NVF_OK;
+extern "C" size_t nvf_trunk_wgrads_bytes(void) { return sizeof(NvfTrunkWgrads); }
+extern "C" int nvf_wgrad_trunk_partial(const NvfTrunkWgrads* req, NvfStepCtx* ctx, void* stream) {
+  return req ? launch_trunk_wgrads(*req, ctx, stream) : NVF_EINVAL;
 }
 
 template <class C>
@@ -1472,22 +1403,43 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_multi(WgReduceMulti d) {
   wgrad_reduce_multi_body(d, blockIdx.x, part);
 }
 
-extern "C" int nvf_wgrad_reduce_multi(const float* const* slabs, float* const* dws, const int* nslabs,
-                                      const int* jtotals, int n, void* stream) {
+// The jobs of a slab reduction: those with nslabs[i] == 0 were written directly by the partial launch and are left out;
+// addends (or an entry) and adam may be null.  Returns the number of workgroups (64 outputs each), or NVF_EINVAL.
+static int fill_reduce(WgReduceMulti& r, const float* const* slabs, float* const* dws, const int* nslabs,
+                       const int* jtotals, int n, const float* const* addends, const NvfAdamFuse* adam) {
   if (!slabs || !dws || !nslabs || !jtotals || n <= 0 || n > 16) return NVF_EINVAL;
-  WgReduceMulti d{};
+  if (adam && (!adam->g_base || !adam->p_base || !adam->m_base || !adam->v_base || adam->n <= 0)) return NVF_EINVAL;
   int base = 0, m = 0;
   for (int i = 0; i < n; ++i) {
-    if (nslabs[i] == 0) continue;     // written directly by the partial launch
+    if (nslabs[i] == 0) continue;
     if (!slabs[i] || !dws[i] || nslabs[i] < 0 || jtotals[i] <= 0) return NVF_EINVAL;
-    d.slabs[m] = slabs[i]; d.dw[m] = dws[i]; d.nslab[m] = nslabs[i]; d.jtotal[m] = jtotals[i];
-    d.blk_base[m] = base;
+    r.slabs[m] = slabs[i]; r.dw[m] = dws[i]; r.nslab[m] = nslabs[i]; r.jtotal[m] = jtotals[i];
+    r.add[m] = addends ? addends[i] : nullptr;
+    r.blk_base[m] = base;
     base += (jtotals[i] + 63) / 64;
     ++m;
   }
-  d.blk_base[m] = base;
-  d.n = m;
-  if (m == 0) return NVF_OK;
+  r.blk_base[m] = base;
+  r.n = m;
+  if (adam) { r.fuse = 1; r.adam = *adam; }
+  return base;
+}
+
+// The queued final passes leave the context, which is empty from here on whatever the caller's launch comes to.
+// Returns finals_sum_blocks of what was queued, or NVF_EINVAL.
+static int take_finals(NvfStepCtx* ctx, FinalsArgs& a) {
+  a = ctx->args;
+  ctx->args = FinalsArgs{};
+  ctx->deferring = 0;
+  if (a.has_f && a.f_nterm > 3) return NVF_EINVAL;
+  return finals_sum_blocks(a);
+}
+
+extern "C" int nvf_wgrad_reduce_multi(const float* const* slabs, float* const* dws, const int* nslabs,
+                                      const int* jtotals, int n, void* stream) {
+  WgReduceMulti d{};
+  const int base = fill_reduce(d, slabs, dws, nslabs, jtotals, n, nullptr, nullptr);
+  if (base <= 0) return base;        // refused, or every gradient was written directly: nothing to launch
   wgrad_reduce_multi<<<base, 1024, 0, nvf_stream(stream)>>>(d);
   NVF_LAUNCH_CHECK();
   return NVF_OK;
@@ -1573,7 +1525,7 @@ __global__ __launch_bounds__(1024, 8) void wgrad_reduce_sums_tail(WgReduceMulti 
 
 // The slab reduction (+ fused optimiser) and the step's final passes + tail (finals_tail_body) in ONE launch: possible
 // when no final pass reads anything this launch's reduction writes (the partial bias sums were made by an earlier
-// launch: nvf_wgrad_trunk5_heads_sums_partial).  The reduction's workgroups read NOTHING from the step buffer (their
+// launch: nvf_wgrad_trunk_partial with sums).  The reduction's workgroups read NOTHING from the step buffer (their
 // optimiser coefficients are the copy that earlier launch staged), so the schedule hand-over waits only for the final
 // passes' workgroups.  (With the ~800 reduction workgroups in the arrival count -- on one counter or through ~sqrt(n)
 // group counters -- the launch took 18 us instead of 13: the device-scope atomics' round trips end up behind the last
@@ -1599,25 +1551,13 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_finals(WgReduceMulti r, int
 extern "C" int nvf_wgrad_reduce_finals(const float* const* slabs, float* const* dws, const int* nslabs,
                                        const int* jtotals, int n, const float* const* addends, NvfStepCtx* ctx,
                                        void* stream) {
-  if (!slabs || !dws || !nslabs || !jtotals || n <= 0 || n > 16 || !nvf_ctx_ok(ctx)) return NVF_EINVAL;
+  if (!nvf_ctx_ok(ctx)) return NVF_EINVAL;
   WgReduceMulti r{};
-  int base = 0, m = 0;
-  for (int i = 0; i < n; ++i) {
-    if (nslabs[i] == 0) continue;
-    if (!slabs[i] || !dws[i] || nslabs[i] < 0 || jtotals[i] <= 0) return NVF_EINVAL;
-    r.slabs[m] = slabs[i]; r.dw[m] = dws[i]; r.nslab[m] = nslabs[i]; r.jtotal[m] = jtotals[i];
-    r.add[m] = addends ? addends[i] : nullptr;
-    r.blk_base[m] = base;
-    base += (jtotals[i] + 63) / 64;
-    ++m;
-  }
-  r.blk_base[m] = base;
-  r.n = m;
-  const FinalsArgs a = ctx->args;
-  ctx->args = FinalsArgs{};
-  ctx->deferring = 0;
-  if (a.has_f && a.f_nterm > 3) return NVF_EINVAL;
-  const int sum_blocks = finals_sum_blocks(a);
+  const int base = fill_reduce(r, slabs, dws, nslabs, jtotals, n, addends, nullptr);
+  if (base < 0) return base;
+  FinalsArgs a;
+  const int sum_blocks = take_finals(ctx, a);
+  if (sum_blocks < 0) return sum_blocks;
   const int f_blocks = 2 + sum_blocks + (a.has_m ? 1 : 0);
   wgrad_reduce_finals<<<f_blocks + base, 1024, 0, nvf_stream(stream)>>>(r, f_blocks, a, sum_blocks);
   NVF_LAUNCH_CHECK();
@@ -1628,44 +1568,29 @@ extern "C" int nvf_wgrad_reduce_finals_tail(const float* const* slabs, float* co
                                             const int* jtotals, int n, const float* const* addends,
                                             const NvfAdamFuse* adam, NvfStepCtx* ctx, const NvfStepTail* tail,
                                             const int64_t* ranges, int nranges, void* stream) {
-  if (!slabs || !dws || !nslabs || !jtotals || n <= 0 || n > 16 || !adam || !tail || !nvf_ctx_ok(ctx)) return NVF_EINVAL;
+  if (!adam || !tail || !nvf_ctx_ok(ctx)) return NVF_EINVAL;
   if (nranges < 0 || nranges > 16 || (nranges > 0 && !ranges)) return NVF_EINVAL;
   const NvfStepTail t = *tail;
   if (!t.p || !t.g || !t.m || !t.v || t.n <= 0) return NVF_EINVAL;
   if (t.acc && (!t.loss_terms || !t.lbits || !t.nbits || t.nnb <= 0 || t.nnb > 16)) return NVF_EINVAL;
   if (t.sched_rows && (!t.sched_buf || !t.sched_cursor || t.sched_words <= 0 || !t.done)) return NVF_EINVAL;
-  if (!adam->g_base || !adam->p_base || !adam->m_base || !adam->v_base || adam->n <= 0) return NVF_EINVAL;
   if (t.sched_rows && adam->coef_dev) {     // the reduction must not read what the hand-over of this launch overwrites
     const char* c = (const char*)adam->coef_dev;
     const char* b = (const char*)t.sched_buf;
     if (c + 2 * sizeof(float) > b && c < b + (size_t)t.sched_words * sizeof(int64_t)) return NVF_EINVAL;
   }
   WgReduceMulti r{};
-  int base = 0, m = 0;
-  for (int i = 0; i < n; ++i) {
-    if (nslabs[i] == 0) continue;
-    if (!slabs[i] || !dws[i] || nslabs[i] < 0 || jtotals[i] <= 0) return NVF_EINVAL;
-    r.slabs[m] = slabs[i]; r.dw[m] = dws[i]; r.nslab[m] = nslabs[i]; r.jtotal[m] = jtotals[i];
-    r.add[m] = addends ? addends[i] : nullptr;
-    r.blk_base[m] = base;
-    base += (jtotals[i] + 63) / 64;
-    ++m;
-  }
-  r.blk_base[m] = base;
-  r.n = m;
-  r.fuse = 1;
-  r.adam = *adam;
+  const int base = fill_reduce(r, slabs, dws, nslabs, jtotals, n, addends, adam);
+  if (base < 0) return base;
   TailRanges rg{};
   for (int q = 0; q < nranges; ++q) {
     if (ranges[2 * q] < 0 || ranges[2 * q + 1] > t.n || ranges[2 * q] > ranges[2 * q + 1]) return NVF_EINVAL;
     rg.lo[q] = (long)ranges[2 * q]; rg.hi[q] = (long)ranges[2 * q + 1];
   }
   rg.n = nranges;
-  const FinalsArgs a = ctx->args;
-  ctx->args = FinalsArgs{};
-  ctx->deferring = 0;
-  if (a.has_f && a.f_nterm > 3) return NVF_EINVAL;
-  const int sum_blocks = finals_sum_blocks(a);
+  FinalsArgs a;
+  const int sum_blocks = take_finals(ctx, a);
+  if (sum_blocks < 0) return sum_blocks;
   const int f_blocks = 2 + sum_blocks + 1;
   wgrad_reduce_finals_tail<<<f_blocks + base, 1024, 0, nvf_stream(stream)>>>(r, f_blocks, a, sum_blocks, t, rg);
   NVF_LAUNCH_CHECK();
@@ -1674,8 +1599,8 @@ extern "C" int nvf_wgrad_reduce_finals_tail(const float* const* slabs, float* co
 
 // Queue the latent tail of a training step (NVFPCC.py:186-196 backward of the latent generator): the gradient of the
 // latent rate (+ dx_addend, the decoder's gradient) -> GDN backward -> 1x1x1 weight and bias gradients, on
-// [batch, c <= 8, spatial] tensors.  It runs as one workgroup of the NEXT nvf_wgrad_reduce_multi_and_sums launch on
-// the same stream (all of its inputs must already be enqueued there); results = nvf_latent_rate + nvf_gdn_bwd +
+// [batch, c <= 8, spatial] tensors.  It runs as one workgroup of the NEXT nvf_wgrad_reduce_multi_and_sums_fused launch
+// on the same stream (all of its inputs must already be enqueued there); results = nvf_latent_rate + nvf_gdn_bwd +
 // nvf_wgrad (+ the bias sum, whose summation order differs from nvf_multi_channel_sum).
 extern "C" int nvf_latent_tail_queue(NvfStepCtx* ctx, const float* lat, const int64_t* block_ids, const float* sigma, const float* mu,
                                      const float* dx_addend, float* dlat, float* dsigma, float* dmu,
@@ -1714,21 +1639,11 @@ extern "C" size_t nvf_multi_channel_sum_workspace(int total_channels) {
 extern "C" int nvf_multi_channel_sum(const float* const* xs, float* const* outs, const int* channels,
                                      const int* spatials, int ntensors, int batch, void* workspace,
                                      size_t workspace_bytes, NvfStepCtx* ctx, void* stream) {
-  if (!xs || !outs || !channels || !spatials || ntensors <= 0 || ntensors > 12 || batch <= 0 || !workspace)
-    return NVF_EINVAL;
+  if (!workspace) return NVF_EINVAL;
   MultiSumDesc d{};
-  int base = 0;
-  long biggest = 0;
-  for (int i = 0; i < ntensors; ++i) {
-    if (!xs[i] || !outs[i] || channels[i] <= 0 || spatials[i] <= 0) return NVF_EINVAL;
-    d.x[i] = xs[i]; d.out[i] = outs[i]; d.c[i] = channels[i]; d.spatial[i] = spatials[i]; d.chan_base[i] = base;
-    base += channels[i];
-    if ((long)batch * spatials[i] > biggest) biggest = (long)batch * spatials[i];
-  }
-  d.ntensors = ntensors; d.batch = batch; d.total_channels = base;
-  (void)biggest;
-  long nchunk = batch < kSumChunks ? batch : kSumChunks;   // groups of consecutive batch entries
-  d.nchunk = (int)nchunk;
+  const int rc = fill_sum_desc(xs, outs, channels, spatials, ntensors, batch, d);
+  if (rc != NVF_OK) return rc;
+  const int base = d.total_channels;
   if (workspace_bytes < nvf_multi_channel_sum_workspace(base)) return NVF_EWORKSPACE;
   hipStream_t s = nvf_stream(stream);
   multi_channel_sum_partial<<<dim3(base, d.nchunk), NVF_SUM_T, 0, s>>>(d, (float*)workspace);
@@ -1738,53 +1653,23 @@ extern "C" int nvf_multi_channel_sum(const float* const* xs, float* const* outs,
   return NVF_OK;
 }
 
-// nvf_wgrad_reduce_multi and the partial pass of nvf_multi_channel_sum in ONE launch (they are independent), then the
-// final pass of the bias sums: the tail of a backward pass in two launches instead of three.  Results are those of
-// the two separate calls, bit for bit.
-extern "C" int nvf_wgrad_reduce_multi_and_sums(const float* const* slabs, float* const* dws, const int* nslabs,
-                                               const int* jtotals, int n, const float* const* xs, float* const* outs,
-                                               const int* channels, const int* spatials, int ntensors, int batch,
-                                               void* workspace, size_t workspace_bytes, NvfStepCtx* ctx, void* stream) {
-  return nvf_wgrad_reduce_multi_and_sums_fused(slabs, dws, nslabs, jtotals, n, nullptr, nullptr, xs, outs, channels,
-                                               spatials, ntensors, batch, workspace, workspace_bytes, ctx, stream);
-}
-
+// nvf_wgrad_reduce_multi (with addends and, optionally, the fused optimiser) and the partial pass of
+// nvf_multi_channel_sum in ONE launch (they are independent), then the final pass of the bias sums: the tail of a
+// backward pass in two launches instead of three.  Results are those of the two separate calls, bit for bit.
 extern "C" int nvf_wgrad_reduce_multi_and_sums_fused(const float* const* slabs, float* const* dws, const int* nslabs,
                                                      const int* jtotals, int n, const float* const* addends,
                                                      const NvfAdamFuse* adam, const float* const* xs,
                                                      float* const* outs, const int* channels, const int* spatials,
                                                      int ntensors, int batch, void* workspace, size_t workspace_bytes,
                                                      NvfStepCtx* ctx, void* stream) {
-  if (!slabs || !dws || !nslabs || !jtotals || n <= 0 || n > 16) return NVF_EINVAL;
-  if (!xs || !outs || !channels || !spatials || ntensors <= 0 || ntensors > 12 || batch <= 0 || !workspace)
-    return NVF_EINVAL;
+  if (!workspace) return NVF_EINVAL;
   WgReduceMulti r{};
-  int base = 0, m = 0;
-  for (int i = 0; i < n; ++i) {
-    if (nslabs[i] == 0) continue;
-    if (!slabs[i] || !dws[i] || nslabs[i] < 0 || jtotals[i] <= 0) return NVF_EINVAL;
-    r.slabs[m] = slabs[i]; r.dw[m] = dws[i]; r.nslab[m] = nslabs[i]; r.jtotal[m] = jtotals[i];
-    r.add[m] = addends ? addends[i] : nullptr;
-    r.blk_base[m] = base;
-    base += (jtotals[i] + 63) / 64;
-    ++m;
-  }
-  r.blk_base[m] = base;
-  r.n = m;
-  if (adam) {
-    if (!adam->g_base || !adam->p_base || !adam->m_base || !adam->v_base || adam->n <= 0) return NVF_EINVAL;
-    r.fuse = 1;
-    r.adam = *adam;
-  }
+  const int base = fill_reduce(r, slabs, dws, nslabs, jtotals, n, addends, adam);
+  if (base < 0) return base;
   MultiSumDesc d{};
-  int cb = 0;
-  for (int i = 0; i < ntensors; ++i) {
-    if (!xs[i] || !outs[i] || channels[i] <= 0 || spatials[i] <= 0) return NVF_EINVAL;
-    d.x[i] = xs[i]; d.out[i] = outs[i]; d.c[i] = channels[i]; d.spatial[i] = spatials[i]; d.chan_base[i] = cb;
-    cb += channels[i];
-  }
-  d.ntensors = ntensors; d.batch = batch; d.total_channels = cb;
-  d.nchunk = batch < kSumChunks ? batch : kSumChunks;
+  const int rc = fill_sum_desc(xs, outs, channels, spatials, ntensors, batch, d);
+  if (rc != NVF_OK) return rc;
+  const int cb = d.total_channels;
   if (workspace_bytes < nvf_multi_channel_sum_workspace(cb)) return NVF_EWORKSPACE;
   hipStream_t s = nvf_stream(stream);
   if (nvf_ctx_ok(ctx) && ctx->tail_pending) {

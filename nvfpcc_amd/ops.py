@@ -4,9 +4,11 @@ PyTorch is plumbing here: it owns device memory and the stream; every value is c
 hand-written gfx950 kernel in libnvf_hip.so.  All tensors must be fp32, contiguous and on a
 HIP device; anything else raises (no CPU fallback).
 """
+import math
+
 import torch
 
-from ._lib import lib, check
+from ._lib import lib, check, NvfTrunkWgrads
 
 ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 # kernel variant passed to the conv / wgrad entry points: 0 = tuned LDS-tiled kernels, 1 = the
@@ -345,6 +347,9 @@ _MFMA_VARIANT = 0
 # slabs (= workgroups) of the big head's weight gradient: 512 (matrix-core kernel inside the five-gradient launch:
 # 447.7 us of step kernels against 449.6 with 256 and 450.4 with 1024); the VALU kernels did best with 256
 _HEADS_SLABS = 512
+# nvf_wgrad_trunk_partial's slab geometry: floats per slab of conv2 / up2 / conv1 / up1 / conv0; slabs a job's region holds
+_TRUNK_SLAB_FLOATS = (4096, 8000, 4096, 16000, 16000)
+_TRUNK_SLABS = 512
 
 
 def set_mfma_variant(v):
@@ -767,17 +772,35 @@ class WgradBatch:
         self._check_slabs(what, nsl, (max_slabs,) * n)
         self.jobs += [(bases[h], outs[h].data_ptr(), nsl[h], jt[h]) for h in range(n)]
 
+    def _trunk_partial(self, ps, qs, slabs, nsl, bias_slabs=None, heads=None, sums=None, coef=None):
+        """One nvf_wgrad_trunk_partial call for len(ps) = 3 or 5 jobs.  slabs / nsl / bias_slabs: ctypes arrays;
+        ``heads`` = (dls, xs, slab array, count array); ``sums`` = _sum_args(...); ``coef`` = (src, live)."""
+        import ctypes
+        arrs = dict(ps=_parr(ps), qs=_parr(qs), slabs=slabs, nslabs=nsl, bias_slabs=bias_slabs)   # (alive until the call)
+        if heads is not None:
+            arrs.update(head_dls=_parr(heads[0]), head_xs=_parr(heads[1]), head_slabs=heads[2], head_nslabs=heads[3])
+        if sums is not None:
+            arrs.update(zip(("sum_xs", "sum_outs", "sum_channels", "sum_spatials"), sums))
+        req = NvfTrunkWgrads(batch=ps[0].shape[0], njobs=len(ps), head_max_slabs=0 if heads is None else _HEADS_SLABS,
+                             **{k: ctypes.addressof(v) for k, v in arrs.items() if v is not None})
+        if sums is not None:
+            req.sum_n, ws = sums[4:]
+            req.sum_workspace, req.sum_workspace_bytes = _ptr(ws), ws.numel()
+        if coef:
+            req.coef_src, req.coef_live = _ptr(coef[0]), _ptr(coef[1])
+        return lib().nvf_wgrad_trunk_partial(ctypes.byref(req), _ctx(self.ctx), _stream())
+
     def add_mfma3(self, ps, qs, outs):
         """conv2 / up2 / conv1 weight gradients of the narrow trunk: one partial-sum launch, three reduction jobs."""
         _f32(*ps, *qs, *outs)
-        self._grouped("nvf_wgrad_mfma3_partial", lambda bases, nsl: lib().nvf_wgrad_mfma3_partial(
-            _parr(ps), _parr(qs), bases, ps[0].shape[0], nsl, _ctx(self.ctx), _stream()), outs, (4096, 8000, 4096), 512)
+        self._grouped("nvf_wgrad_trunk_partial", lambda bases, nsl: self._trunk_partial(ps, qs, bases, nsl), outs,
+                      _TRUNK_SLAB_FLOATS[:3], _TRUNK_SLABS)
 
     def add_up1_conv0(self, ps, qs, outs):
         """up1 / conv0 weight gradients of the narrow trunk: one partial-sum launch, two reduction jobs."""
         _f32(*ps, *qs, *outs)
         self._grouped("nvf_wgrad_up1_conv0_partial", lambda bases, nsl: lib().nvf_wgrad_up1_conv0_partial(
-            _parr(ps), _parr(qs), bases, ps[0].shape[0], nsl, _stream()), outs, (16000, 16000), 512)
+            _parr(ps), _parr(qs), bases, ps[0].shape[0], nsl, _stream()), outs, _TRUNK_SLAB_FLOATS[3:], _TRUNK_SLABS)
 
     def add_trunk5(self, ps, qs, outs, bias_outs=None, heads=None, sums=None, coef=None, stem_jobs=None):
         """conv2 / up2 / conv1 / up1 / conv0 weight gradients of the narrow trunk: one partial-sum launch (which also
@@ -791,11 +814,10 @@ class WgradBatch:
         jobs stem_bwd_queue returned, whose slabs this launch writes; they join the job list after the launch, ahead
         of its own."""
         import ctypes
-        _f32(*ps, *qs, *outs)
-        B = ps[0].shape[0]
+        _f32(*ps, *qs, *outs, *(bias_outs or ()))
         self.sums_done = False
-        jt = (4096, 8000, 4096, 16000, 16000) + ((8, 8) if bias_outs is not None else ())
-        sizes = [512 * j * 4 for j in jt]
+        jt = _TRUNK_SLAB_FLOATS + ((8, 8) if bias_outs is not None else ())
+        sizes = [_TRUNK_SLABS * j * 4 for j in jt]
         if heads is not None:
             hd, hx, ho = heads
             _f32(*hd, *hx, *ho)
@@ -804,37 +826,19 @@ class WgradBatch:
         bases = self._alloc(sizes)
         nsl = (ctypes.c_int * 5)()
         hn = (ctypes.c_int * 3)()
-        if heads is not None and sums is not None:
-            st, so = sums
-            _f32(*st, *so)
-            total = sum(t.shape[1] for t in st)
-            ws = workspace(lib().nvf_multi_channel_sum_workspace(total), st[0].device, "mchsum", self.ctx)
-            check(lib().nvf_wgrad_trunk5_heads_sums_partial(
-                _parr(ps), _parr(qs), (ctypes.c_void_p * 5)(*bases[:5]), (ctypes.c_void_p * 3)(bases[5], None, bases[6]),
-                _parr(hd), _parr(hx), (ctypes.c_void_p * 3)(*bases[7:10]), _HEADS_SLABS, _parr(st), _parr(so),
-                _iarr([t.shape[1] for t in st]), _iarr([t[0, 0].numel() for t in st]), len(st), _ptr(ws), ws.numel(),
-                _ptr(coef[0]) if coef else None, _ptr(coef[1]) if coef else None, B,
-                nsl, hn, _ctx(self.ctx), _stream()), "nvf_wgrad_trunk5_heads_sums_partial")
-            self.sums_done = True
-        elif heads is not None:
-            check(lib().nvf_wgrad_trunk5_heads_partial(
-                _parr(ps), _parr(qs), (ctypes.c_void_p * 5)(*bases[:5]), (ctypes.c_void_p * 3)(bases[5], None, bases[6]),
-                _parr(hd), _parr(hx), (ctypes.c_void_p * 3)(*bases[7:10]), _HEADS_SLABS, B, nsl, hn, _ctx(self.ctx),
-                _stream()), "nvf_wgrad_trunk5_heads_partial")
-        elif bias_outs is None:
-            check(lib().nvf_wgrad_trunk5_partial(_parr(ps), _parr(qs), (ctypes.c_void_p * 5)(*bases[:5]), B, nsl,
-                                                 _ctx(self.ctx), _stream()), "nvf_wgrad_trunk5_partial")
-        else:
-            _f32(*bias_outs)
-            check(lib().nvf_wgrad_trunk5_partial_bias(_parr(ps), _parr(qs), (ctypes.c_void_p * 5)(*bases[:5]),
-                                                      (ctypes.c_void_p * 3)(bases[5], None, bases[6]), B, nsl,
-                                                      _ctx(self.ctx), _stream()), "nvf_wgrad_trunk5_partial_bias")
-        self._check_slabs("add_trunk5", nsl, (512,) * 5)
+        ride = heads is not None and sums is not None
+        check(self._trunk_partial(
+            ps, qs, (ctypes.c_void_p * 5)(*bases[:5]), nsl,
+            None if bias_outs is None else (ctypes.c_void_p * 3)(bases[5], None, bases[6]),
+            None if heads is None else (hd, hx, (ctypes.c_void_p * 3)(*bases[len(jt):]), hn),
+            _sum_args(*sums, self.ctx) if ride else None, coef if ride else None), "nvf_wgrad_trunk_partial")
+        self.sums_done = ride
+        self._check_slabs("add_trunk5", nsl, (_TRUNK_SLABS,) * 5)
         if heads is not None:
             self._check_slabs("add_trunk5 (heads)", hn, (_HEADS_SLABS,) * 3)
         self.jobs += stem_jobs or []
         if heads is not None:
-            self.jobs += [(bases[7 + h], ho[h].data_ptr(), hn[h], hcs[h] * 27) for h in range(3)]
+            self.jobs += [(bases[len(jt) + h], ho[h].data_ptr(), hn[h], hcs[h] * 27) for h in range(3)]
         self.jobs += [(bases[h], outs[h].data_ptr(), nsl[h], jt[h]) for h in range(5)]
         if bias_outs is not None:
             self.jobs.append((bases[5], bias_outs[0].data_ptr(), nsl[0], 8))
@@ -861,15 +865,10 @@ class WgradBatch:
                 multi_channel_sum(tensors, outs, ctx=self.ctx)
             return
         jobs = self._take_jobs()
-        _f32(*tensors)
-        _f32(*outs)
-        total = sum(t.shape[1] for t in tensors)
-        ws = workspace(lib().nvf_multi_channel_sum_workspace(total), tensors[0].device, "mchsum", self.ctx)
+        *arrs, ws = _sum_args(tensors, outs, self.ctx)
         check(lib().nvf_wgrad_reduce_multi_and_sums_fused(
-            *self._job_arrays(jobs, addends), None if adam is None else ctypes.byref(adam),
-            _parr(tensors), _parr(outs), _iarr([t.shape[1] for t in tensors]), _iarr([t[0, 0].numel() for t in tensors]),
-            len(tensors), tensors[0].shape[0], _ptr(ws), ws.numel(), _ctx(self.ctx), _stream()),
-            "nvf_wgrad_reduce_multi_and_sums_fused")
+            *self._job_arrays(jobs, addends), None if adam is None else ctypes.byref(adam), *arrs,
+            tensors[0].shape[0], _ptr(ws), ws.numel(), _ctx(self.ctx), _stream()), "nvf_wgrad_reduce_multi_and_sums_fused")
 
     def finish_and_flush_tail(self, addends, adam, tail, ranges):
         """The slab reduction (addends, fused optimiser) and the context's queued final passes + step tail in ONE
@@ -911,20 +910,20 @@ def channel_sum(x, out=None, accumulate=False):
     return o
 
 
+def _sum_args(tensors, outs, ctx):
+    """What the channel-sum entry points take for outs[i][c] = sum of tensors[i][:, c]: (tensor pointers, output pointers,
+    channel counts, spatial sizes, count, the "mchsum" workspace)."""
+    _f32(*tensors, *outs)
+    ws = workspace(lib().nvf_multi_channel_sum_workspace(sum(t.shape[1] for t in tensors)), tensors[0].device, "mchsum",
+                   ctx)
+    return (_parr(tensors), _parr(outs), _iarr([t.shape[1] for t in tensors]),
+            _iarr([math.prod(t.shape[2:]) for t in tensors]), len(tensors), ws)
+
+
 def multi_channel_sum(tensors, outs, ctx=None):
     """outs[i][c] = sum over batch and space of tensors[i][:, c]; all tensors share the batch size."""
-    import ctypes
-    _f32(*tensors)
-    _f32(*outs)
-    n = len(tensors)
-    B = tensors[0].shape[0]
-    xs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in tensors])
-    os_ = (ctypes.c_void_p * n)(*[t.data_ptr() for t in outs])
-    cs = (ctypes.c_int * n)(*[t.shape[1] for t in tensors])
-    sp = (ctypes.c_int * n)(*[t[0, 0].numel() for t in tensors])
-    total = sum(t.shape[1] for t in tensors)
-    ws = workspace(lib().nvf_multi_channel_sum_workspace(total), tensors[0].device, "mchsum", ctx)
-    check(lib().nvf_multi_channel_sum(xs, os_, cs, sp, n, B, _ptr(ws), ws.numel(), _ctx(ctx), _stream()),
+    *arrs, ws = _sum_args(tensors, outs, ctx)
+    check(lib().nvf_multi_channel_sum(*arrs, tensors[0].shape[0], _ptr(ws), ws.numel(), _ctx(ctx), _stream()),
           "nvf_multi_channel_sum")
 
 

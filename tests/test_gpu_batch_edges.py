@@ -217,7 +217,7 @@ def test_latent_tail_rides_in_the_five_gradient_launch_at_600_blocks(ops, big, l
 
 @pytest.mark.parametrize("B", [513, 600])
 def test_three_and_two_gradient_launches_past_the_slab_cap(ops, big, layer_err, B):
-    """nvf_wgrad_mfma3_partial (conv2 / up2 / conv1; default forms, direct forms, and z split 2 + conv1 in the Winograd
+    """nvf_wgrad_trunk_partial with three jobs (conv2 / up2 / conv1; default forms, direct forms, and z split 2 + conv1 in the Winograd
     form) and nvf_wgrad_up1_conv0_partial (the capped tile jobs) at 513 and 600 blocks against float64."""
     t, ref = big
     for what, setup in (("default", lambda c: None), ("direct", lambda c: c.set_direct(True)),

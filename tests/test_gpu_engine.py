@@ -980,7 +980,7 @@ def test_the_narrow_training_step_is_these_library_calls(gpu, monkeypatch):
         "nvf_heads3_fwd_loss_bwd_data",
         "nvf_conv3d_k4_wino_bwd", "nvf_conv3d_s2k5_mfma", "nvf_conv3d_k4_wino_bwd", "nvf_conv3d_s2k5_mfma",
         "nvf_stem_bwd_workspace_for", "nvf_stem_bwd_queue", "nvf_latent_tail_queue", "nvf_multi_channel_sum_workspace",
-        "nvf_wgrad_trunk5_heads_sums_partial",
+        "nvf_wgrad_trunk_partial",
         "nvf_weight_rate_batch_final",
         "nvf_wgrad_reduce_finals_tail"]
     assert len([c for c in calls if c not in no_launch]) == 12

@@ -223,7 +223,7 @@ def test_three_head_launches_equal_the_single_head_kernels(ops, which):
 
 
 def test_three_mfma_weight_gradients_in_one_launch(ops):
-    """nvf_wgrad_mfma3_partial (conv2, up2, conv1 of the narrow trunk) equals three nvf_wgrad calls bit for bit."""
+    """nvf_wgrad_trunk_partial with three jobs (conv2, up2, conv1 of the narrow trunk) equals three nvf_wgrad calls bit for bit."""
     g = gen(7100)
     B = 2
     R = lambda *s: dev(torch.randn(*s, generator=g))
@@ -270,7 +270,7 @@ def test_three_mfma_weight_gradients_in_one_launch(ops):
     wg.finish()
     assert torch.equal(outs2[0], ops.wgrad(y1, g2, 5, 2, 0, out_mode=0))
     assert torch.equal(outs2[1], ops.wgrad(h0, g1, 5, 2, 2, out_mode=0))
-    # ... and all five in one launch (nvf_wgrad_trunk5_partial: the two VALU jobs run as 256-thread workgroups)
+    # ... and all five in one launch (nvf_wgrad_trunk_partial with five jobs: the two VALU jobs run as 256-thread workgroups)
     outs5 = [torch.empty_like(o) for o in outs + outs2]
     wg.add_trunk5([g5, y3, g3, y1, h0], [y4, g4, y2, g2, g1], outs5)
     wg.finish()
@@ -950,7 +950,7 @@ def test_heads_forward_loss_and_backward_data_in_one_launch(ops, which, B):
 
 @pytest.mark.parametrize("c,B", [(3, 16), (8, 5), (3, 40)])
 def test_latent_tail_inside_the_slab_reduction_launch(ops, c, B):
-    """nvf_latent_tail_queue (one workgroup of the nvf_wgrad_reduce_multi_and_sums launch) against nvf_latent_rate +
+    """nvf_latent_tail_queue (one workgroup of the nvf_wgrad_reduce_multi_and_sums_fused launch) against nvf_latent_rate +
     nvf_gdn_bwd + nvf_wgrad: every gradient bit for bit (same arithmetic, same order); the bias gradient to fp32
     summation order.  40 blocks x 8 voxels = three 128-voxel chunks of the GDN stage."""
     torch.manual_seed(5 + c)
