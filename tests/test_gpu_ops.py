@@ -948,6 +948,171 @@ def test_heads_forward_loss_and_backward_data_in_one_launch(ops, which, B):
                                      [p[1] for p in packed], [None, None, None], ctx)
 
 
+# logit classes of test_heads_at_saturated_logits: (name, lower bound, upper bound) on the float64 logit
+LOGIT_CLASSES = [("expf overflows, p = 0", -np.inf, -104.0), ("p below the smallest normal", -104.0, -88.0),
+                 ("normal p under the 1e-9 clamp", -88.0, -20.8), ("|logit| < 15", -15.0, 15.0),
+                 ("p rounds to 1", 16.7, np.inf)]
+
+
+def saturated_head_inputs(shapes, B, seed):
+    """Inputs (CPU, float32) whose head logits have a standard deviation near 40 around -40: x ~ 2 N(0, 1), weights
+    ~ N(0, (20 / sqrt(27 c))^2), bias -40; gt at one half; dist uniform."""
+    g = gen(seed)
+    xs = [2.0 * torch.randn(B, c, s, s, s, generator=g) for c, s in shapes]
+    ws = [torch.randn(1, c, 3, 3, 3, generator=g) * (20.0 / np.sqrt(27.0 * c)) for c, s in shapes]
+    bs = [torch.full((1,), -40.0) + torch.randn(1, generator=g) for _ in shapes]
+    gts = [(torch.rand(B, 1, s, s, s, generator=g) > 0.5).float() for c, s in shapes]
+    dist = torch.rand(B, 1, shapes[2][1], shapes[2][1], shapes[2][1], generator=g)
+    return xs, ws, bs, gts, dist
+
+
+def focal_reference64(p32, gt, dist, alpha, beta):
+    """One focal term (utils/loss.py:61-72, 94-111) and its gradient w.r.t. the LOGIT in float64, from a float32 p taken as
+    exact input.  F = p or 1 - p and the comparison with the 1e-9 clamp are float32 operations (the same IEEE operations
+    on any side); everything after them is float64; the chain factor is (1 - p) p.  -> (loss sum, d loss / d logit, the
+    mask of entries whose gradient is zero by the clamp branch or by a zero factor)."""
+    assert p32.dtype == torch.float32
+    occ = gt != 0
+    clamp = torch.tensor(1e-9, dtype=torch.float32)
+    F32 = torch.where(occ, p32, 1.0 - p32)
+    clamped = F32 < clamp
+    Fc = torch.where(clamped, clamp, F32).double()
+    a32 = torch.tensor(alpha, dtype=torch.float32)
+    at = torch.where(occ, a32, 1.0 - a32).double()          # fp32 "-alpha + 1", as loss.py:66-67 evaluates it
+    w = torch.ones_like(Fc) if dist is None else dist.double() + occ.double() * beta
+    om, lg = 1.0 - Fc, torch.log(Fc)
+    loss = (-at * om * om * w * lg).sum()
+    d = torch.where(clamped, torch.zeros_like(Fc), -at * w * (-2.0 * om * lg + om * om / Fc))
+    p = p32.double()
+    chain = (1.0 - p) * p
+    dl = torch.where(occ, d, -d) * chain
+    return float(loss), dl, clamped | (chain == 0) | (d == 0)
+
+
+@pytest.mark.parametrize("which", ["narrow", "wide"])
+def test_heads_at_saturated_logits(ops, which):
+    """The one-launch heads against an independent float64 reference where p saturates (a trained decoder: a third or more
+    of the probabilities under the focal loss's 1e-9 clamp, tests/test_gpu_trained_state.py): logits from below -104
+    (expf(-v) overflows, p = 0) through the denormal range and the clamp to above 16.7 (p = 1.0f), B = 2.
+
+    p (heads3_fwd and heads3_fwd_loss_bwd_data) against the float64 sigmoid of the float64 logit: with E = 4 x (the
+    largest |logit32 - logit64| of torch's own float32 conv3d on the CPU, measured here) + 16 * 2^-24 (expf and the
+    division), the relative error of p is at most E where p < 0.5; where p >= 0.5 the error of 1 - p is at most
+    E (1 - p) + 1.5 * 2^-24 -- the second term is what float32 forces on any 1 / (1 + e): half a unit in the last place
+    of 1 + e in [1, 2) and half a unit of the quotient in [0.5, 1] (a float32 next to 1 cannot hold 1 - p more finely, so
+    a purely relative bound on that side holds for no float32 result).  Where the float64 p is below 2^-126, anything in
+    [0, 2^-126] passes: denormal or zero is the device's business.
+
+    Loss terms, logit gradients and input gradients of three routes (heads3_loss_bwd_data, heads3_fwd_loss_bwd_data,
+    focal_loss_multi + heads3_bwd_data) against focal_reference64 at the device's own float32 p: logit gradients to 1e-5
+    relative per element (+ one float32 denormal), zero exactly where the reference's clamp branch or a zero factor makes
+    them zero and nowhere else; input gradients to 1e-5 of the tensor's maximum against the float64 convolution of the
+    device's logit gradients; loss sums to 1e-5 relative; the heads' bias gradients against the float64 sum of the logit
+    gradients.  No voxel is left out.  Among themselves the routes agree as at
+    moderate logits: gradients bit for bit, the loss of the two one-launch forms bit for bit, focal_loss_multi's to
+    summation order."""
+    B = 2
+    shapes = HEAD_TUPLES[which]
+    cs = [c for c, s in shapes]
+    xs, ws, bs, gts, dist = saturated_head_inputs(shapes, B, 7300)
+    z64 = [F.conv3d(x.double(), w.double(), b.double(), padding=1) for x, w, b in zip(xs, ws, bs)]
+    E = 0.0
+    for h, (z, gt) in enumerate(zip(z64, gts)):
+        shares = []
+        for name, lo, hi in LOGIT_CLASSES:
+            m = (z > lo) & (z < hi)
+            shares.append(float(m.double().mean()))
+            assert shares[-1] >= 0.01, (h, name, shares[-1])
+            assert bool((gt[m] != 0).any()) and bool((gt[m] == 0).any()), (h, name)
+        z32 = F.conv3d(xs[h], ws[h], bs[h], padding=1)
+        e = float((z32.double() - z).abs().max())
+        E = max(E, e)
+        print(f"[saturated heads {which}] head {h}: logits {float(z.min()):.1f} .. {float(z.max()):.1f}, class shares "
+              + " / ".join(f"{s:.3f}" for s in shares) + f"; float32 conv3d on the CPU: max |logit32 - logit64| = {e:.2e}")
+    E = 4.0 * E + 16.0 * 2.0 ** -24
+    print(f"[saturated heads {which}] E = {E:.2e}")
+
+    xd, gd, dd = [dev(x) for x in xs], [dev(t) for t in gts], dev(dist)
+    bd = [dev(b) for b in bs]
+    packed = [ops.pack_conv_weight(dev(w)) for w in ws]
+    wf, wb = [p[0] for p in packed], [p[1] for p in packed]
+    dists, masks = [None, None, dd], [None, None, xd[2]]
+    args = ([0.85, 0.85, 0.9], [0.0, 0.0, 1.0], [1, 2, 0])
+    # route A: forward, then loss + backward-data in one launch
+    ps_a = ops.heads3_fwd(xd, wf, bd)
+    loss_a = torch.empty(4, device="cuda")
+    gbs_a = [torch.zeros(1, device="cuda") for _ in range(3)]
+    dls_a, dxs_a = ops.heads3_loss_bwd_data(ps_a, gd, dists, *args, loss_a, wb, cs, masks, bias_outs=gbs_a)
+    # route B: everything in one launch
+    ctx = ops.StepCtx()
+    loss_b = torch.empty(4, device="cuda")
+    gbs_b = [torch.zeros(1, device="cuda") for _ in range(3)]
+    ctx.begin()
+    ps_b, dls_b, dxs_b = ops.heads3_fwd_loss_bwd_data(xd, wf, bd, gd, dists, *args, loss_b, wb, masks, ctx, bias_outs=gbs_b)
+    ctx.flush()
+    # route C: the three focal terms, then the heads' backward-data
+    loss_c = torch.empty(4, device="cuda")
+    dl2, dl0, dl1 = ops.focal_loss_multi([(ps_a[2], gd[2], dd, 0.9, 1.0), (ps_a[0], gd[0], None, 0.85, 0.0),
+                                          (ps_a[1], gd[1], None, 0.85, 0.0)], loss_c)
+    dls_c = [dl0, dl1, dl2]
+    dxs_c = ops.heads3_bwd_data(dls_c, wb, cs, masks)
+    torch.cuda.synchronize()
+
+    # the routes among themselves
+    for h in range(3):
+        assert torch.equal(ps_b[h], ps_a[h]), h
+        for name, a_, b_, c_ in (("dl", dls_a, dls_b, dls_c), ("dx", dxs_a, dxs_b, dxs_c)):
+            assert torch.equal(a_[h], b_[h]) and torch.equal(a_[h], c_[h]), (name, h)
+    assert torch.equal(loss_a[:3], loss_b[:3])
+    np.testing.assert_allclose(loss_c[:3].cpu().numpy(), loss_a[:3].cpu().numpy(), rtol=2e-6)
+
+    tiny, denorm = 2.0 ** -126, 2.0 ** -149
+    for h, (c, s) in enumerate(shapes):
+        # p against the float64 sigmoid of the float64 logit
+        z = z64[h]
+        pr = torch.sigmoid(z)
+        qr = torch.sigmoid(-z)                              # 1 - p without cancellation
+        p32 = ps_a[h].cpu()
+        p = p32.double()
+        assert bool(((p >= 0) & (p <= 1)).all())
+        sub = pr < tiny
+        assert bool((p[sub] <= tiny).all()), h
+        low = (pr < 0.5) & ~sub
+        rel = ((p - pr).abs() / pr)[low]
+        up = pr >= 0.5
+        excess = ((1.0 - p) - qr).abs()[up] - 1.5 * 2.0 ** -24
+        rel_up = (excess.clamp(min=0) / qr[up])
+        print(f"[saturated heads {which}] head {h}: p < 0.5: max relative error {float(rel.max()):.2e}; p >= 0.5: max "
+              f"(|error of 1 - p| - 1.5 * 2^-24) / (1 - p) = {float(rel_up.max()):.2e} (E = {E:.2e}); "
+              f"{int((p32 == 0).sum())} zeros, {int(((p32 > 0) & (p32 < tiny)).sum())} denormals, {int((p32 == 1).sum())} ones")
+        assert float(rel.max()) <= E, (h, float(rel.max()), E)
+        assert float(rel_up.max()) <= E, (h, float(rel_up.max()), E)
+        # loss and logit gradient against float64 at the device's p
+        loss_ref, dl_ref, zero = focal_reference64(p32, gts[h], dist if h == 2 else None, args[0][h], args[1][h])
+        got = float(loss_a[args[2][h]])
+        assert abs(got - loss_ref) <= 1e-5 * abs(loss_ref), (h, got, loss_ref)
+        assert abs(float(loss_c[args[2][h]]) - loss_ref) <= 1e-5 * abs(loss_ref), (h, float(loss_c[args[2][h]]), loss_ref)
+        dl = dls_a[h].cpu().double()
+        assert bool((dl[zero] == 0).all()), (h, int((dl[zero] != 0).sum()))
+        assert bool((dl[~zero & (dl_ref.abs() > denorm)] != 0).all()), h
+        assert bool(zero.any()) and bool((~zero).any())
+        err = (dl - dl_ref).abs() - denorm
+        worst = float((err / dl_ref.abs().clamp(min=1e-300))[~zero].max())
+        print(f"[saturated heads {which}] head {h}: {int(zero.sum())} of {zero.numel()} logit gradients zero by the clamp or a "
+              f"zero factor; the others: max relative error {worst:.2e}")
+        assert bool((err <= 1e-5 * dl_ref.abs()).all()), (h, worst)
+        # the head's bias gradient from the same launches: the sum of the logit gradient (bound as at moderate logits)
+        assert torch.equal(gbs_a[h], gbs_b[h]), h
+        want = float(dl.sum())
+        assert abs(float(gbs_a[h]) - want) <= 2e-6 * float(dl.abs().sum()) + 1e-12, (h, float(gbs_a[h]), want)
+        # input gradient against the float64 convolution of the device's logit gradient
+        dx_ref = F.conv_transpose3d(dl, ws[h].double(), padding=1)
+        if masks[h] is not None:
+            dx_ref = dx_ref * (xs[h] > 0)
+        assert float(dx_ref.abs().max()) > 0
+        assert rel_err(dxs_a[h], dx_ref) <= 1e-5, (h, rel_err(dxs_a[h], dx_ref))
+
+
 @pytest.mark.parametrize("c,B", [(3, 16), (8, 5), (3, 40)])
 def test_latent_tail_inside_the_slab_reduction_launch(ops, c, B):
     """nvf_latent_tail_queue (one workgroup of the nvf_wgrad_reduce_multi_and_sums_fused launch) against nvf_latent_rate +
