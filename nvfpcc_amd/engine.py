@@ -23,7 +23,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from . import ops
+from . import ops, routes
 from ._lib import lib, check
 from .network import NoiseState
 
@@ -31,20 +31,6 @@ R, S, NONE = ops.ACT_RELU, ops.ACT_SIGMOID, ops.ACT_NONE
 # winograd=None: the 4^3 layers of a training step in the Winograd (y, x) form (conv_wino.hip, conv16_wino.hip);
 # NVF_WINO=0 keeps the direct summation order (the strict-trajectory engine)
 _WINO = os.environ.get("NVF_WINO", "1") != "0"
-# (conv1's training FORWARD in that form: measured slower at batch 16 -- 19.1 us two-set / 16.7 us one-set kernel against
-# 12.2 us for the direct kernel, r05 A/B -- 16^3 outputs do not amortise the transforms; used above batch 64 only)
-
-
-def _wino_bwd_ppc(g_out):
-    """Plane pairs per work unit of the Winograd backward-data at a full batch (0: the kernel's batch-16 default; an explicit
-    count without bit 16 = the two-set kernel of conv_wino.hip).  Every choice gives the same bits; batch 917: conv2
-    2182 -> 1945 us, conv1 569 -> 387 us (tools/wino_ppc_sweep.py, tools/wino_bench.py --batch 917)."""
-    if g_out.shape[0] <= 64:
-        return 0
-    # (conv1: the two-set kernel of conv_wino.hip, all ten plane pairs per unit -- 387 us against 466 for the one-set kernel
-    # with 5 at batch 917, tools/wino_bench.py --fwd --batch 917; the same bits)
-    # (conv2 likewise: all 18 pairs in the two-set kernel 1945 us, one-set kernel with 9 / 18: 2203 / 2098 in the same run)
-    return 18 if g_out.shape[-1] == 32 else 10
 
 
 # One-launch groupings of the step.  Plain constants: tests/test_gpu_engine.py switches the first four off to build the
@@ -85,7 +71,7 @@ def plan_step(narrow, wide, winograd, fused_stem, fused_latent_stem, heads3, ch,
     it handed over the optimiser's coefficients; ``step_head``: batch_and_prepare(stem_mode=...) ran; ``defer_heads``:
     forward(defer_heads=True)), ops._NAIVE and the five module switches.  No tensors.  What launch_trunk_wgrads (wgrad.hip)
     answers with NVF_EINVAL is an implication between the fields (tests/test_step_plan.py).  ``winograd`` and the 64-block
-    switch points select kernel forms inside a launch (_conv, _dx_conv, _dx_convT), never a launch."""
+    switch point select kernel forms inside a launch (routes.py), never a launch."""
     # the one-launch groupings bypass the variant switch of the per-layer entry points: only with the tuned kernels
     tuned = naive == 0
     small = batch <= 32         # the cooperative launches keep one arrival counter per block, 32 of them
@@ -108,9 +94,6 @@ def plan_step(narrow, wide, winograd, fused_stem, fused_latent_stem, heads3, ch,
 
 TRUNK = ("up0", "conv0", "up1", "conv1", "up2", "conv2", "conv2_cls")
 HEADS = ("conv1_cls", "conv0_cls")
-# layers whose backward-data also runs on the matrix cores: name -> (pair axis, largest batch it is used for)
-# (above batch 64 the VALU tile kernel is faster for both: conv1 222 vs 367 us, conv2 1167 vs 1234 us at batch 256)
-MFMA_BWD = {"conv1": (2, 64), "conv2": (0, 64)}
 
 _DESC = np.dtype([("kernel", "<u8"), ("kernel_init", "<u8"), ("b", "<u8"), ("b_init", "<u8"), ("w_fwd", "<u8"),
                   ("w_bwd", "<u8"), ("b_eff", "<u8"), ("dim0", "<i4"), ("dim1", "<i4"), ("k3", "<i4"),
@@ -118,8 +101,7 @@ _DESC = np.dtype([("kernel", "<u8"), ("kernel_init", "<u8"), ("b", "<u8"), ("b_i
 
 
 class _Layer:
-    __slots__ = ("name", "mod", "kind", "k", "w_fwd", "w_bwd", "b_eff", "gk", "gb", "cin", "cout", "pad", "wp_f",
-                 "wp_b", "wp_t", "wp_tr", "wp_s", "wp_gf", "wp_gb", "wp_t16", "wp_w", "wp_wf", "bwd_pair", "bwd_max_batch")
+    __slots__ = ("name", "mod", "kind", "k", "w_fwd", "w_bwd", "b_eff", "gk", "gb", "cin", "cout", "pad", "wp")
 
 
 class TrainEngine:
@@ -164,6 +146,7 @@ class TrainEngine:
         self.narrow = chans == (8, 16, 8, 8)
         self.wide = chans == (16, 32, 16, 16)
         self.generic = not (self.narrow or self.wide)
+        self.decoder_class = "narrow" if self.narrow else "wide" if self.wide else "generic"
         self._flatten_parameters()
         self._build_layers()
         self.last = {}
@@ -235,58 +218,9 @@ class TrainEngine:
             L.b_eff = torch.empty(m.b.numel(), device=self.dev)
             L.gk, L.gb = self._g(prefix + ".kernel").view(m.kernel.shape), self._g(prefix + ".b")
             L.cin, L.cout, L.pad = m.in_channels, m.out_channels, m.padding
-            L.wp_f = L.wp_b = L.wp_t = L.wp_tr = L.wp_s = L.wp_gf = L.wp_gb = L.wp_t16 = L.wp_w = L.wp_wf = None
-            L.bwd_pair, L.bwd_max_batch = 2, 0
-            if self.narrow and L.k == 5 and L.cin % 4 == 0 and L.cout == 8 and L.pad == 0 and name in ("up1", "up2"):
-                # matrix-core form of the padding-0 transposed convolutions: forward, and backward-data (a
-                # stride-2 gather convolution with cin output channels)
-                L.wp_t = torch.empty(int(lib().nvf_pack_convT_mfma_floats(L.cin)), device=self.dev)
-                if self.winograd:
-                    # the forward of TRAINING steps with the kx = 4 taps on rows (co, ey): 65 instead of 75 A fragments per
-                    # channel group, another summation order for the even x outputs (pack kind 12, kernel variant 15);
-                    # evaluation / encode / decode keep wp_t
-                    L.wp_tr = torch.empty((L.cin // 4) * 65 * 64, device=self.dev)
-                if L.cin in (8, 16):
-                    L.wp_s = torch.empty(int(lib().nvf_pack_s2k5_mfma_floats(L.cout, L.cin)), device=self.dev)
-            if self.narrow and L.k == 4 and L.cin % 4 == 0 and L.cout == 8 and L.cin == 8 and L.pad == 0:
-                # matrix-core form of the 4^3 convolutions: MFMA A-fragments, re-packed after every weight preparation
-                L.wp_f = torch.empty(int(lib().nvf_pack_mfma_k4_floats(L.cin, 0)), device=self.dev)
-                if name in MFMA_BWD:
-                    # backward-data mapping: rows pair outputs along z with 4x4 patches (conv1) or along x with
-                    # flattened 18-cell rows (conv2; faster than the VALU kernel only while the batch is small)
-                    L.bwd_pair, L.bwd_max_batch = MFMA_BWD[name]
-                    L.wp_b = torch.empty(int(lib().nvf_pack_mfma_k4_floats(L.cout, L.bwd_pair)), device=self.dev)
-                if self.winograd and name in ("conv2", "conv1"):
-                    # backward-data in the reduced-multiplication form (Winograd over (y, x), z pairs on the matrix
-                    # cores: 52 us against 85 for the direct form at batch 16) ...
-                    L.wp_w = torch.empty(int(lib().nvf_pack_wino_k4_floats()), device=self.dev)
-                    # ... and the forward of TRAINING steps (mode 'train': NVFPCC.py:160, 234); the eval / encode / decode
-                    # forward keeps the direct fixed-order kernel (bit-exact batch invariance, the occupancy contract).
-                    # conv1 only above batch 64 (the full-batch latent step: 207 us against 375 for the direct kernel at
-                    # batch 917; at batch 16 its 16^3 outputs do not amortise the transforms: 16.7 against 12.2 us)
-                    L.wp_wf = torch.empty(int(lib().nvf_pack_wino_k4_floats()), device=self.dev)
-            # wide decoder (16 / 32 channels): the output channels are the MFMA rows (conv16_mfma.hip) -- conv1 / conv2
-            # forward and backward-data, and the backward-data of up2 / up1 (stride-2 gather with cin output channels)
-            if self.wide and L.k == 4 and L.cin == 16 and L.cout == 16 and L.pad == 0 and name in ("conv1", "conv2"):
-                L.wp_gf = torch.empty(int(lib().nvf_pack_g16_mfma_floats(16, 16, 4)), device=self.dev)
-                L.wp_gb = torch.empty(int(lib().nvf_pack_g16_mfma_floats(16, 16, 4)), device=self.dev)
-                if self.winograd:
-                    # the Winograd (y, x) form with the 16 output channels as MFMA rows (conv16_wino.hip), training steps
-                    # only: conv2 backward-data 257 -> 140 us, forward 170 -> 95, conv1 backward-data 59 -> 33 at batch 16.
-                    # conv1's FORWARD stays direct (27 -> 25 us would cost the engine == operator-path agreement its 2e-5:
-                    # measured 2.004e-5), so only conv2 gets a forward packing -- and a pack-job slot stays free
-                    L.wp_w = torch.empty(int(lib().nvf_pack_wino16_k4_floats()), device=self.dev)
-                    if name == "conv2":
-                        L.wp_wf = torch.empty(int(lib().nvf_pack_wino16_k4_floats()), device=self.dev)
-            if self.wide and L.k == 5 and L.cout == 16 and L.cin in (16, 32) and L.pad == 0 and name in ("up1", "up2"):
-                L.wp_gb = torch.empty(int(lib().nvf_pack_g16_mfma_floats(16, L.cin, 5)), device=self.dev)
-            if self.wide and L.k == 5 and (name, L.cin, L.cout, L.pad) in (("up1", 32, 16, 0), ("up2", 16, 16, 0),
-                                                                      ("conv0", 16, 32, 2), ("up0", 8, 16, 2)):
-                L.wp_t16 = torch.empty(int(lib().nvf_pack_convT16_mfma_floats(L.cin, L.cout)), device=self.dev)
-            if self.wide and name == "up0" and L.cin == 8 and L.cout == 16 and L.pad == 2:     # 16 -> 8 channels, rows 8..15 zero
-                L.wp_gb = torch.empty(int(lib().nvf_pack_g16_mfma_floats(16, 8, 5)), device=self.dev)
-            if self.wide and name == "conv0" and L.cin == 16 and L.cout == 32 and L.pad == 2:
-                L.wp_gb = torch.empty(int(lib().nvf_pack_g16_mfma_floats(32, 16, 5)), device=self.dev)
+            # the matrix-core forms' packed weights (routes.PACKS), re-packed after every weight preparation
+            L.wp = {p: torch.empty(routes.pack_floats(lib(), p, L.cin, L.cout, L.k), device=self.dev)
+                    for p in routes.layer_packs(self.decoder_class, self.winograd, name, L.cin, L.cout, L.k, L.pad)}
             self.layers[name] = L
             t = table[i]
             t["kernel"], t["kernel_init"] = m.kernel.data_ptr(), m.kernel_init.data_ptr()
@@ -299,26 +233,14 @@ class TrainEngine:
             t["nbias"] = m.b.numel()
         row = {name: i for i, (name, _, _) in enumerate(mods)}
         self._rows = row
-        wk, wc = (41, 16) if self.wide else (40, 8)          # Winograd packing of the decoder class
-        # (_Layer slot, source, (pack kind, c0, c1)): slot by slot, layers in table order, is the job order inside
-        # nvf_pack_mfma_all / nvf_step_head
-        packs = (("wp_f", "w_fwd", lambda L: (0, L.cin, 8)),
-                 ("wp_b", "w_bwd", lambda L: (L.bwd_pair, L.cout, 8)),
-                 ("wp_w", "w_bwd", lambda L: (wk, L.cout, wc)),
-                 ("wp_wf", "w_fwd", lambda L: (wk, L.cin, wc)),
-                 ("wp_t", "w_fwd", lambda L: (10, L.cin, 8)),
-                 ("wp_tr", "w_fwd", lambda L: (12, L.cin, 8)),
-                 ("wp_s", "w_bwd", lambda L: (20, L.cout, L.cin)),
-                 # 16-row gather forms: kind 30 (k = 4) / 31 (k = 5), c0 = input channels of the gather, c1 = its output channels
-                 ("wp_gf", "w_fwd", lambda L: (30, L.cin, L.cout)),
-                 ("wp_gb", "w_bwd", lambda L: (30 if L.k == 4 else 31, L.cout, L.cin)),
-                 ("wp_t16", "w_fwd", lambda L: (11, L.cin, L.cout)))
+        # packing by packing in routes.PACKS order, layers in table order, is the job order inside nvf_pack_mfma_all /
+        # nvf_step_head
         jobs, meta = [], []
-        for slot, src, form in packs:
+        for pack, P in routes.PACKS.items():
             for nm, L in self.layers.items():
-                if getattr(L, slot) is not None:
-                    jobs.append((getattr(L, src), getattr(L, slot)) + form(L))
-                    meta.append((row[nm], int(src == "w_bwd")))
+                if pack in L.wp:
+                    jobs.append((getattr(L, P.src), L.wp[pack]) + routes.pack_job(pack, L.cin, L.cout, L.k))
+                    meta.append((row[nm], int(P.src == "w_bwd")))
         assert len(jobs) <= 16
         self._mfma_jobs = jobs
         self._mfma_job_layers = meta           # (layer-table row, 0 = w_fwd / 1 = w_bwd) of each job's source
@@ -426,37 +348,24 @@ class TrainEngine:
 
     # ------------------------------------------------------------------ forward
     def _convT(self, L, x, act, train=False):
-        if L.wp_t16 is not None:
-            return ops.convT3d_k5s2_mfma16(x, L.wp_t16, L.b_eff, act, cout=L.cout, pad=L.pad)
-        if L.wp_t is not None:
-            # eight waves with one column tile each (variant 5: two waves per SIMD; up1 19.3 -> 15.6 us, up2 34.0 -> 30.7 at
-            # batch 16 -- and at batch 917 (the full-batch latent step; r05 sweep): up2 1115 -> 916 us, up1 389 -> 310;
-            # every variant runs the same per-output fmaf chain: bit-identical)
-            if train and L.wp_tr is not None:
-                return ops.convT3d_k5s2_mfma(x, L.wp_tr, L.b_eff, act, variant=15)
-            return ops.convT3d_k5s2_mfma(x, L.wp_t, L.b_eff, act, variant=5)
+        r = routes.convT_fwd(self.decoder_class, self.winograd, L.name, L.cin, train)
+        if r.form == "convT16":
+            return ops.convT3d_k5s2_mfma16(x, L.wp[r.pack], L.b_eff, act, cout=L.cout, pad=L.pad)
+        if r.form == "convT_mfma":
+            return ops.convT3d_k5s2_mfma(x, L.wp[r.pack], L.b_eff, act, variant=r.variant)
         return ops.convT3d_k5s2_fwd(x, L.w_fwd, L.b_eff, L.cout, L.pad, act)
 
     def _conv(self, L, x, act, train=False):
-        if train and L.wp_wf is not None and act == R and (self.wide or x.shape[-1] == 35 or x.shape[0] > 64):
-            if self.wide:
-                return ops.conv3d_k4_wino16_fwd(x, L.wp_wf, L.b_eff)
-            if x.shape[-1] == 19:      # conv1 at a full batch: the two-set kernel, all eight plane pairs per unit
-                return ops.conv3d_k4_wino_fwd(x, L.wp_wf, L.b_eff, ppc=8)
-            # (a full-batch launch has workgroups to spare: more plane pairs per work unit repeat fewer plane transforms --
-            # conv2 at batch 917: 1667 -> 1481 us with 8 pairs per unit; the same bits, tools/wino_ppc_sweep.py)
-            # (above batch 64 the two-set kernel with all 16 pairs: 1480 us against 1507 for the one-set kernel with 8)
-            return ops.conv3d_k4_wino_fwd(x, L.wp_wf, L.b_eff, ppc=16 if x.shape[0] > 64 else 0)
-        if L.wp_gf is not None:
+        r = routes.conv_fwd(self.decoder_class, self.winograd, L.name, x.shape[0], train, act == R)
+        if r.form == "wino16_fwd":
+            return ops.conv3d_k4_wino16_fwd(x, L.wp[r.pack], L.b_eff)
+        if r.form == "wino_fwd":
+            return ops.conv3d_k4_wino_fwd(x, L.wp[r.pack], L.b_eff, ppc=r.ppc)
+        if r.form == "g16":
             osz = tuple(s - 3 for s in x.shape[2:])
-            return ops.conv3d_g16_mfma(x, L.wp_gf, L.b_eff, L.cout, 4, 1, 0, osz, act)
-        if L.wp_f is not None:
-            # conv1 at large batch: 8 rows x 4 planes on eight waves (variant 5: 34.2 vs 39.4 us at batch 64, 107 vs 120
-            # (variant 2) at 256, 402 vs 443 at 917; at batch 16 the default tile: 12.7 vs 17.6).  Every variant runs
-            # the same per-output fmaf chain, so the bits -- and encode-at-any-batch == decode-at-batch-1 -- do not change
-            # (eval_forward at 66 blocks against batch 1: tests/test_gpu_decode_bits.py)
-            var = 5 if (x.shape[-1] == 19 and x.shape[0] >= 64) else None
-            return ops.conv3d_k4_mfma(x, L.wp_f, L.b_eff, 0, 0, act, variant=var)
+            return ops.conv3d_g16_mfma(x, L.wp[r.pack], L.b_eff, L.cout, 4, 1, 0, osz, act)
+        if r.form == "k4_mfma":
+            return ops.conv3d_k4_mfma(x, L.wp[r.pack], L.b_eff, 0, routes.PAIR_AXIS[r.pack], act, variant=r.variant)
         osz = tuple(s + 2 * L.pad - L.k + 1 for s in x.shape[2:])
         return ops.conv3d_gather(x, L.w_fwd, L.b_eff, L.cout, L.k, 1, L.pad, osz, act)
 
@@ -513,11 +422,10 @@ class TrainEngine:
 
     # ------------------------------------------------------------------ backward
     def _wgrad_conv(self, L, g_out, x_in, sums):
-        if (self.wide and self.winograd and L.k == 4 and L.cin == 16 and L.cout == 16 and L.pad == 0
-                and g_out.shape[-1] in (32, 16)):
-            # the Winograd (y, x) form (wgrad16_wino.hip): slabs for the common reduction (conv2 172 -> 100 us at batch 16)
+        r = routes.conv_wgrad(self.decoder_class, self.winograd, L.name)
+        if r.form == "wino16_partial":
             base = self._wg.reserve(256 * 16384 * 4)
-            n = ops.wgrad16_k4_wino_partial(g_out, x_in, base, zsplit=0 if g_out.shape[-1] == 32 else 8)
+            n = ops.wgrad16_k4_wino_partial(g_out, x_in, base, zsplit=r.zsplit)
             self._wg.add_job(base, L.gk, n, 16384)
         else:
             self._wg.add(g_out, x_in, L.k, 1, L.pad, 0, L.gk)
@@ -531,54 +439,39 @@ class TrainEngine:
         """Backward-data of a 4^3 convolution.  ``bias_out``: the bias gradient of the layer BELOW (whose masked output
         gradient dx this pass writes).  Where the matrix-core kernel leaves dx's channel sums as slabs, they become a job of
         the reduction launch; everywhere else (dx, bias_out) joins ``sums``, the step's list for the channel-sum pass."""
-        slabs = False
-        if self.wide and L.wp_w is not None and mask is not None and addend is None and g_out.shape[-1] in (32, 16):
-            # (the channel sums of dx -- the bias gradient of the layer below -- from this kernel's epilogue, bias_part=:
-            # measured neutral, the reduction launch 48.9 -> 44.0 us against + 2.7 / + 2.1 us in the two epilogues)
-            dx = ops.conv3d_k4_wino16_bwd(g_out, L.wp_w, mask)
-        elif L.wp_gb is not None:
-            dx = ops.conv3d_g16_mfma(g_out, L.wp_gb, None, L.cin, 4, 1, 3, tuple(x_in.shape[2:]), addend=addend,
-                                     mask=mask)
-        elif L.wp_w is not None and mask is not None and addend is None and g_out.shape[-1] in (32, 16):
-            if bias_out is not None and g_out.shape[0] <= 64:
-                # (one slab of 8 sums per work unit: 126 units per block in conv2's default kernel, conv_wino1.hip)
-                base = self._wg.reserve(16384 * 8 * 4)
-                dx, nparts = ops.conv3d_k4_wino_bwd(g_out, L.wp_w, mask, bias_part=base)
-                self._wg.add_job(base, bias_out, nparts, 8)
-                slabs = True
-            else:
-                dx = ops.conv3d_k4_wino_bwd(g_out, L.wp_w, mask, ppc=_wino_bwd_ppc(g_out))
-        elif L.wp_b is not None and g_out.shape[0] <= L.bwd_max_batch:
-            if bias_out is not None and mask is not None and addend is None:
-                base = self._wg.reserve(4096 * 8 * 4)
-                dx, nparts = ops.conv3d_k4_mfma(g_out, L.wp_b, None, 3, L.bwd_pair, NONE, mask=mask, bias_part=base)
-                self._wg.add_job(base, bias_out, nparts, 8)
-                slabs = True
-            else:
-                dx = ops.conv3d_k4_mfma(g_out, L.wp_b, None, 3, L.bwd_pair, NONE, addend=addend, mask=mask)
+        r = routes.conv_dx(self.decoder_class, self.winograd, L.name, g_out.shape[0], mask is not None, addend is not None,
+                           bias_out is not None)
+        wp = L.wp.get(r.pack)
+        if r.form == "wino16_bwd":
+            dx = ops.conv3d_k4_wino16_bwd(g_out, wp, mask)
+        elif r.form == "g16":
+            dx = ops.conv3d_g16_mfma(g_out, wp, None, L.cin, 4, 1, 3, tuple(x_in.shape[2:]), addend=addend, mask=mask)
+        elif r.form == "wino_bwd" and r.bias_slabs:
+            base = self._wg.reserve(16384 * 8 * 4)
+            dx, nparts = ops.conv3d_k4_wino_bwd(g_out, wp, mask, bias_part=base)
+            self._wg.add_job(base, bias_out, nparts, 8)
+        elif r.form == "wino_bwd":
+            dx = ops.conv3d_k4_wino_bwd(g_out, wp, mask, ppc=r.ppc)
+        elif r.form == "k4_mfma" and r.bias_slabs:
+            base = self._wg.reserve(4096 * 8 * 4)
+            dx, nparts = ops.conv3d_k4_mfma(g_out, wp, None, 3, routes.PAIR_AXIS[r.pack], NONE, mask=mask, bias_part=base)
+            self._wg.add_job(base, bias_out, nparts, 8)
+        elif r.form == "k4_mfma":
+            dx = ops.conv3d_k4_mfma(g_out, wp, None, 3, routes.PAIR_AXIS[r.pack], NONE, addend=addend, mask=mask)
         else:
             dx = ops.conv3d_gather(g_out, L.w_bwd, None, L.cin, L.k, 1, L.k - 1 - L.pad, tuple(x_in.shape[2:]),
                                    addend=addend, mask=mask)
-        if bias_out is not None and not slabs:
+        if bias_out is not None and not r.bias_slabs:
             sums.append((dx, bias_out))
         return dx
 
     def _dx_convT(self, L, g_out, x_in, mask=None, addend=None):
-        if L.wp_gb is not None:
-            return ops.conv3d_g16_mfma(g_out, L.wp_gb, None, L.cin, 5, 2, L.pad, tuple(x_in.shape[2:]), addend=addend,
+        r = routes.convT_dx(self.decoder_class, self.winograd, L.name, L.cin, g_out.shape[0])
+        if r.form == "g16":
+            return ops.conv3d_g16_mfma(g_out, L.wp[r.pack], None, L.cin, 5, 2, L.pad, tuple(x_in.shape[2:]), addend=addend,
                                        mask=mask)
-        if L.wp_s is not None:
-            # up1 at large batch: two planes per wave (variant 2: 55 vs 63 us at batch 256; 173 vs 184 at 917)
-            # up2 at batch <= 64: 8 rows x 2 planes on eight waves (variant 6: 25.3 -> 22.8 us at batch 16; bit-identical;
-            # nvf_conv3d_gather's own choice by batch for these layers is held by tests/test_gpu_decode_bits.py);
-            # above: 4 rows x 4 planes on eight waves (variant 5: 1027 vs 1149 us at batch 917)
-            # up1 in training steps of the default engine: the two channel groups of g on different waves, 256 workgroups of
-            # 2 rows x 2 planes (variant 7: another summation order, so not in the strict-trajectory engine)
-            if L.cin == 16:
-                var = 2 if g_out.shape[0] > 64 else (7 if self.winograd else None)
-            else:
-                var = 6 if g_out.shape[0] <= 64 else 5
-            return ops.conv3d_s2k5_mfma(g_out, L.wp_s, L.cin, addend=addend, mask=mask, variant=var)
+        if r.form == "s2k5_mfma":
+            return ops.conv3d_s2k5_mfma(g_out, L.wp[r.pack], L.cin, addend=addend, mask=mask, variant=r.variant)
         return ops.conv3d_gather(g_out, L.w_bwd, None, L.cin, 5, 2, L.pad, tuple(x_in.shape[2:]), addend=addend,
                                  mask=mask)
 

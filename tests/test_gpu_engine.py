@@ -381,8 +381,7 @@ def test_one_launch_step_head_equals_the_three_launches(tag, gpu):
     quantisation mode."""
     net, eng, gt, dist, emb = make(tag, gpu)
     idx = torch.tensor([4, 1, 5, 1], device=gpu)
-    bufs = lambda: [t for L in eng.layers.values() for t in (L.w_fwd, L.w_bwd, L.b_eff, L.wp_f, L.wp_b, L.wp_t, L.wp_s, L.wp_gf, L.wp_gb)
-                    if t is not None]
+    bufs = lambda: [t for L in eng.layers.values() for t in (L.w_fwd, L.w_bwd, L.b_eff, *L.wp.values())]
     for q in (0, 1, 2):
         eng.noise_step = 7 + q
         for t in bufs():
@@ -397,6 +396,46 @@ def test_one_launch_step_head_equals_the_three_launches(tag, gpu):
         assert len(ref) > 0 and all(torch.equal(a, b) for a, b in zip(bufs(), ref)), (tag, q)
         assert all(torch.equal(a, b) for a, b in zip(rows, rows_ref))
         assert not any(torch.isnan(t).any().item() for t in bufs())
+
+
+@pytest.mark.parametrize("winograd", [True, False])
+@pytest.mark.parametrize("tag,ch,channels", [("S", CONFIGS["S"]["ch"], CONFIGS["S"]["channels"]),
+                                             ("W", CONFIGS["W"]["ch"], CONFIGS["W"]["channels"]),
+                                             ("offgrid", 4, (4, 8, 4, 4))])
+def test_engine_holds_the_packings_of_the_route_table(tag, ch, channels, winograd, gpu):
+    """What _build_layers allocates and queues for packing is what routes.py states: every layer's packings are
+    routes.layer_packs of it, every buffer has the size the library gives for that packing, and the pack jobs are the pack
+    table's (kind, c0, c1), packing by packing in table order, layers in the engine's order."""
+    from nvfpcc_amd import network, routes
+    from nvfpcc_amd._lib import lib
+    from nvfpcc_amd.engine import TrainEngine
+    from nvfpcc_amd.model import Net
+    network.reset_seed(synthetic_seed())
+    net = Net(None, "Gaussian", ch, ",".join(str(c) for c in channels), verbose=False).to(gpu)
+    gts, dists = make_blocks(2)
+    eng = TrainEngine(net, torch.from_numpy(gts).float().to(gpu), torch.from_numpy(dists).float().to(gpu),
+                      n_points_total=917 * 936.0, emb=make_emb(2, ch, 1).to(gpu), seed=0, winograd=winograd, **H)
+    cls = {"S": "narrow", "W": "wide", "offgrid": "generic"}[tag]
+    assert eng.decoder_class == cls and eng.winograd == winograd
+    # the library's own size functions, spelled out per pack kind (kind 12 has none: routes.CONVT_ROWS_FRAGMENT_FLOATS)
+    floats = {0: lambda c0, c1: lib().nvf_pack_mfma_k4_floats(c0, 0), 2: lambda c0, c1: lib().nvf_pack_mfma_k4_floats(c0, 2),
+              40: lambda c0, c1: lib().nvf_pack_wino_k4_floats(), 41: lambda c0, c1: lib().nvf_pack_wino16_k4_floats(),
+              10: lambda c0, c1: lib().nvf_pack_convT_mfma_floats(c0), 12: lambda c0, c1: (c0 // 4) * 65 * 64,
+              11: lambda c0, c1: lib().nvf_pack_convT16_mfma_floats(c0, c1),
+              20: lambda c0, c1: lib().nvf_pack_s2k5_mfma_floats(c0, c1),
+              30: lambda c0, c1: lib().nvf_pack_g16_mfma_floats(c0, c1, 4),
+              31: lambda c0, c1: lib().nvf_pack_g16_mfma_floats(c0, c1, 5)}
+    want_jobs = []
+    for name, L in eng.layers.items():
+        assert tuple(L.wp) == routes.layer_packs(cls, winograd, name, L.cin, L.cout, L.k, L.pad), name
+        for pack, t in L.wp.items():
+            kind, c0, c1 = routes.pack_job(pack, L.cin, L.cout, L.k)
+            assert t.numel() == int(floats[kind](c0, c1)) == routes.pack_floats(lib(), pack, L.cin, L.cout, L.k), (name, pack)
+    for pack, P in routes.PACKS.items():
+        want_jobs += [(getattr(L, P.src).data_ptr(), L.wp[pack].data_ptr()) + routes.pack_job(pack, L.cin, L.cout, L.k)
+                      for L in eng.layers.values() if pack in L.wp]
+    assert [(j[0].data_ptr(), j[1].data_ptr()) + tuple(j[2:]) for j in eng._mfma_jobs] == want_jobs
+    assert len(want_jobs) == {"narrow": 14 if winograd else 8, "wide": 15 if winograd else 12, "generic": 0}[cls]
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -725,7 +764,7 @@ def test_direct_forms_follow_the_reference_trajectory_to_rounding(gpu, golden_di
     from tests.test_oracle_golden import summary
     G = np.load(os.path.join(golden_dir, "trajectory.npz"))
     net, eng = _traj_engine(gpu, winograd=False)
-    assert all(L.wp_w is None and L.wp_wf is None for L in eng.layers.values())
+    assert not any(p.startswith("wino") for L in eng.layers.values() for p in L.wp)
     drv = EpochDriver(eng, TRAJ["batch"], use_graph=True)
     for epoch in range(TRAJ["epochs"]):
         q = 1 if epoch < TRAJ["phase_change"] else 2

@@ -250,7 +250,7 @@ def test_winograd_step_equals_the_direct_step(gpu, monkeypatch):
     for wino in (True, False):
         monkeypatch.setattr(E, "_WINO", wino)
         net, eng, P, gt, dist, emb = make(gpu, 3, (8, 16, 8, 8), 24)
-        assert (eng.layers["conv2"].wp_w is not None) == wino and (eng.layers["conv2"].wp_wf is not None) == wino
+        assert ("wino_dx" in eng.layers["conv2"].wp) == wino and ("wino_fwd" in eng.layers["conv2"].wp) == wino
         ids = np.arange(16)
         a = eng.train_step(ids, 1, update=False)
         ev = eng.eval_forward(lo=0, hi=5, q=2)["p2"].clone()
@@ -276,7 +276,7 @@ def test_wide_winograd_step_equals_the_direct_step(gpu, monkeypatch):
     for wino in (True, False):
         monkeypatch.setattr(E, "_WINO", wino)
         net, eng, P, gt, dist, emb = make(gpu, 8, (16, 32, 16, 16), 20)
-        assert eng.wide and (eng.layers["conv2"].wp_w is not None) == wino and (eng.layers["conv2"].wp_wf is not None) == wino and eng.layers["conv1"].wp_wf is None
+        assert eng.wide and ("wino16_dx" in eng.layers["conv2"].wp) == wino and ("wino16_fwd" in eng.layers["conv2"].wp) == wino and "wino16_fwd" not in eng.layers["conv1"].wp
         ids = np.arange(16)
         a = eng.train_step(ids, 1, update=False)
         ev = eng.eval_forward(lo=0, hi=5, q=2)["p2"].clone()

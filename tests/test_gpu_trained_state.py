@@ -170,6 +170,6 @@ def test_direct_engine_matches_the_oracle_at_a_trained_state(trained, gpu):
     net2.load_state_dict({k: v.detach().cpu().clone() for k, v in T.net.state_dict().items()})
     net2 = net2.to(gpu)
     eng2 = TrainEngine(net2, T.gt.to(gpu), T.dist.to(gpu), n_points_total=NPTS, emb=T.eng.emb, seed=0, winograd=False, **H)
-    assert not eng2.winograd and eng2.layers["conv2"].wp_w is None
+    assert not eng2.winograd and not any(p.startswith("wino") for p in eng2.layers["conv2"].wp)
     assert torch.equal(eng2.flat_p, T.eng.flat_p) and torch.equal(eng2.emb, T.eng.emb)
     _check(T, eng2, net2, "direct", "train_step, 4 blocks, q=2", "train", MINI, 2)

@@ -46,8 +46,9 @@ def main():
         y, dx = torch.empty(B, 8, no, no, no, device=dev), torch.empty(B, 8, n, n, n, device=dev)
         macs = B * 8 * no ** 3 * 8 * 64
         cases.append((name + ".fwd", macs, lambda: ops.conv3d_k4_mfma(x, wpf, None, 0, 0, ops.ACT_RELU, out=y)))
-        from nvfpcc_amd.engine import MFMA_BWD
-        pair = MFMA_BWD[name][0]
+        from nvfpcc_amd import routes
+        pair = next(routes.PAIR_AXIS[p] for p in routes.layer_packs("narrow", False, name, 8, 8, 4, 0)
+                    if routes.PACKS[p].src == "w_bwd")
         wpb = ops.pack_mfma_k4(wb, 8, pair)
         cases.append((name + ".bwd_data", macs, lambda: ops.conv3d_k4_mfma(gy, wpb, None, 3, pair, mask=x, out=dx)))
         wpb2 = ops.pack_mfma_k4(wb, 8, 2 - pair)            # the other pair axis, and the VALU tile kernel
