@@ -19,8 +19,10 @@ engine (nvfpcc_amd/engine.py) instead of a DataLoader + autograd loop.
     python NVFPCC.py decode pack.pk --lod 1 ...                                # half resolution: the trunk stops at the 16^3 head
     python NVFPCC.py encode ... --lossless                                     # the true occupancy travels too (lossless_pack)
     python NVFPCC.py decode pack.pk --lossless ...                             # rc_dec.ply holds exactly the input's voxels
+    python NVFPCC.py encode ... --lossless_lod                                 # the occupancy coarse to fine (lossless_lod_pack)
+    python NVFPCC.py decode pack.pk --lossless_lod 0|1|2 ...                   # exact at 32^3, 16^3 or 8^3 per block
 
-Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --thh_mode (count | block-count | d1:
+Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --lossless_lod, --thh_mode (count | block-count | d1:
 nvfpcc_amd/thh_select.py picks the occupancy threshold at encode time and a `thh_pack` key carries it); multi-GPU training when launched
 through torch.distributed.run (one process per GPU, leaf blocks sharded, one RCCL all-reduce per step).
 Headless: no GUI window, no IPython shell.
@@ -236,6 +238,10 @@ def encode(args):
     if getattr(args, 'lossless', False):    # the true occupancy, coded under the field the pack's own bytes decode to
         lossless = _encode_lossless(args, total_pack, data, dev, batch)
         total_pack['lossless_pack'] = lossless['pack']
+    lossless_lod = None
+    if getattr(args, 'lossless_lod', None) is not None:     # the same occupancy coarse to fine: exact at 8^3, 16^3, 32^3
+        lossless_lod = _encode_lossless_lod(args, total_pack, data, dev, batch)
+        total_pack['lossless_lod_pack'] = lossless_lod['pack']
     with open(args.pack_fn, 'wb') as f:
         pickle.dump(total_pack, f)
     print('Start to reconstruct')
@@ -254,6 +260,7 @@ def encode(args):
     latent_bits = len(latent_pack['latent_byte_stream']) * 8
     side_bits = (0 if sel is None else 8 * len(sel['pack'])) + 8 * len(total_pack.get('octree_pack', b''))
     side_bits += 8 * len(total_pack.get('lod_pack', b'')) + 8 * len(total_pack.get('lossless_pack', b''))
+    side_bits += 8 * len(total_pack.get('lossless_lod_pack', b''))
     if sel is not None:
         print(sel['line'])
     print('[Latent code] Gross bpp: %.4f' % ((latent_bits + net_bits + side_bits) / data.N))
@@ -267,6 +274,8 @@ def encode(args):
             write_ply_ascii('rc_enc_lod%d.ply' % level, lod_pts)
     if lossless is not None:
         print(lossless['line'])
+    if lossless_lod is not None:
+        print(lossless_lod['line'])
 
 
 def _encode_lossless(args, total_pack, data, dev, batch):
@@ -289,6 +298,30 @@ def _encode_lossless(args, total_pack, data, dev, batch):
     if not torch.equal(words, info['gt_words']) or int(counts.sum().item()) != int(data.N):
         raise SystemExit("encode --lossless: the stream does not decode to the input's occupancy; no pack written")
     return {'pack': pack, 'line': lp.lossless_line(len(pack), data.N, info['ideal_bits'], lp.GROUP)}
+
+
+def _encode_lossless_lod(args, total_pack, data, dev, batch):
+    """encode --lossless_lod: as _encode_lossless, with the coarse-to-fine coder (nvfpcc_amd.lossless_lod_pack).  The
+    stream is decoded again at all three levels: a pack that does not reproduce the input's occupancy and its two
+    max-pools is not written.  -> {'pack': lossless_lod_pack bytes, 'line': the [LosslessLoD] line}."""
+    import contextlib
+    import io
+    from nvfpcc_amd import lossless_lod_pack as lp
+    with contextlib.redirect_stdout(io.StringIO()):     # the decoder's own progress lines belong to decode
+        net, latents = _decoder_from_pack(args, total_pack, dev)
+    latents = latents[:data.N_leaf].contiguous()
+    gt, _ = data.to_device(dev)
+    try:
+        pack, info = lp.encode_occupancy(net, latents, gt, batch=batch, group=lp.GROUP)
+        for level in (2, 1, 0):
+            words, counts = lp.decode_occupancy(net, latents, pack, level=level, batch=batch)
+            if not torch.equal(words, info['gt_words'][level]) or (level == 0 and int(counts.sum().item()) != int(data.N)):
+                raise SystemExit(f"encode --lossless_lod: the stream does not decode to the input's occupancy at level "
+                                 f"{level}; no pack written")
+    except ValueError as e:
+        raise SystemExit(f"encode --lossless_lod: {e}")
+    return {'pack': pack, 'line': lp.lossless_lod_line(len(pack), data.N, info['ideal_bits'], info['contexts'],
+                                                       info['symbols'], lp.GROUP)}
 
 
 def _encode_lod(args, net, latents, data, origins, dev, batch):
@@ -357,11 +390,13 @@ def decode(args):
     from nvfpcc_amd import weight_codec, latent_codec
     from nvfpcc_amd.recon import reconstruct_points, write_ply_ascii
     lossless_refusals(args, None)
+    lossless_lod_refusals(args, None)
     dev, rank, world = _device(args)
     net = _build_net(args, torch.device('cpu'))
     with open(args.input, 'rb') as f:
         total_pack = pickle.load(f)
     lossless_refusals(args, total_pack)
+    lossless_lod_refusals(args, total_pack)
     lod, lod_side = getattr(args, 'lod', 0), None
     if lod:
         from nvfpcc_amd import lod_pack as lp
@@ -391,6 +426,19 @@ def decode(args):
         print('[Lossless] points: %d' % pts.shape[0])
         write_ply_ascii('rc_dec.ply', pts)
         _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10)
+        return
+    if getattr(args, 'lossless_lod', None) is not None:     # the input's voxels, or their exact 2^3 / 4^3 max-pool
+        from nvfpcc_amd import lossless_lod_pack as llp
+        level = int(args.lossless_lod)
+        try:
+            words, counts = llp.decode_occupancy(net, latents[:n].contiguous(), total_pack['lossless_lod_pack'], level=level,
+                                                 batch=max(int(args.batchsize), 1))
+        except ValueError as e:
+            raise SystemExit(f"decode --lossless_lod {level}: {e}")
+        pts = llp.points_from_words(words, counts, origins, level)
+        print('[LosslessLoD] level: %d points: %d' % (level, pts.shape[0]))
+        write_ply_ascii('rc_dec.ply', pts)
+        _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10, lod=level)
         return
     if lod_side is not None:                # a coarser level of detail: the trunk stops at the level's head
         from nvfpcc_amd.recon import reconstruct_points_lod
@@ -453,6 +501,22 @@ def lossless_refusals(args, total_pack):
                          "coarser level of detail is lossy by construction")
     if total_pack is not None and 'lossless_pack' not in total_pack:
         raise SystemExit(f"decode --lossless: {args.input} carries no lossless_pack (it was encoded without --lossless)")
+
+
+def lossless_lod_refusals(args, total_pack):
+    """decode --lossless_lod: what cannot be served exits here with its reason.  total_pack None: the flags alone."""
+    level = getattr(args, 'lossless_lod', None)
+    if level is None:
+        return
+    if getattr(args, 'lod', 0):
+        raise SystemExit("decode: --lossless_lod and --lod exclude each other: --lossless_lod 1 | 2 is the exact coarse "
+                         "cloud, --lod the coarse heads' lossy one")
+    if getattr(args, 'lossless', False):
+        raise SystemExit("decode: --lossless_lod and --lossless exclude each other: each decodes its own side pack into "
+                         "rc_dec.ply")
+    if total_pack is not None and 'lossless_lod_pack' not in total_pack:
+        raise SystemExit(f"decode --lossless_lod {level}: {args.input} carries no lossless_lod_pack (it was encoded "
+                         f"without --lossless_lod)")
 
 
 def _pack_bits(total_pack, origins):
@@ -553,6 +617,11 @@ def build_parser():
                    help='encode: also code the true occupancy of every leaf block under the decoder\'s probabilities '
                         '(lossless_pack, counted in Gross bpp).  decode: write exactly the input\'s voxels to rc_dec.ply '
                         'from a pack encoded with it; excludes --lod.')
+    p.add_argument('--lossless_lod', type=int, nargs='?', choices=[0, 1, 2], const=0, default=argparse.SUPPRESS,
+                   help='encode (no value): also code the true occupancy coarse to fine (lossless_lod_pack, counted in '
+                        'Gross bpp).  decode --lossless_lod L: write exactly the input\'s voxels (0) or exactly their '
+                        'reduction to bits - L bits per axis (1, 2) to rc_dec.ply, from a prefix of the same stream; '
+                        'excludes --lod and --lossless.')
     p.add_argument('--ref_ply', default=None,
                    help='Original cloud (ASCII PLY): encode / decode also print its D1 / D2 geometry PSNR.')
     return p

@@ -892,6 +892,72 @@ int nvf_occ_rans_decode(const float* p, const int32_t* f1, const uint64_t* state
 int nvf_points_from_bits32(const uint64_t* words, const int32_t* offsets, const int32_t* origins, int32_t* points, int n,
                            int batch, void* stream);
 
+/* ---- scalable lossless geometry (nvfpcc_amd/lossless_lod_pack.py, csrc/occ_hier.hip) --------------------------------
+ * The same occupancy coded coarse to fine in ONE stream per group: a decoder that stops after the first or the second
+ * section holds the exact 8^3 or 16^3 max-pool of every block.  Levels: 0 = the 32^3 voxels, 1 = the 16^3 cells, 2 = the
+ * 8^3 cells, all in raster order (z, y, x); the children of cell (Z, Y, X) are (2Z + dz, 2Y + dy, 2X + dx) one level
+ * down, in order j = 4 dz + 2 dy + dx.
+ * Pyramid of a block, from p with exact float comparisons only: P0 = p; P1[c] = the maximum of the 8 children of 16^3
+ *   cell c, folded in child order as m = c0, m = (cj > m) ? cj : m (so the first of equal values, and of +0.0 / -0.0,
+ *   stays); K1[c] = min(3, number of children with p > 0.5f); P2 and K2 likewise from P1 (children with P1 > 0.5f).  An
+ *   input error (the rule of nvf_occ_ctx_hist) ANYWHERE in p is counted, and the encoder raises before it codes.
+ * Contexts, NVF_OCC_HIER_CONTEXTS = 3 x 4 x 256: ctx = (level * 4 + k) * 256 + occ_ctx(P_level[cell]), with occ_ctx the
+ *   context function above; k = K2[c] for an 8^3 cell c, K1[c] for a 16^3 cell c, K1[parent(v)] for a voxel v.
+ * Symbols of a group of G consecutive blocks, three sections in this order: section 2 = block by block all 512 cells
+ *   of the 8^3 grid; section 1 = block by block, for every OCCUPIED 8^3 cell in raster order, its 8 children in order j;
+ *   section 0 = the same from the occupied 16^3 cells to the voxels.  Occupied = the max-pool of the ground truth.
+ *   Everything under an empty parent is empty and costs no symbol.  Each section is padded to a multiple of 64 with idle
+ *   slots; symbol i of a padded section belongs to lane i % 64 at that section's step i / 64; an idle lane neither
+ *   codes nor renormalises.
+ * Coder: the binary rANS coder above, unchanged (64-bit states from 2^31, 32-bit words, 16-bit frequencies, symbol 1 =
+ *   (start 0, freq f1), the words of a step in ascending lane order for the decoder), ONE stream per group: the 64
+ *   states run through sections 2, 1, 0 without a flush in between; the encoder walks section 0, then 1, then 2, each
+ *   backwards.  A symbol emits at most one word, so a block's worst case is NVF_OCC_HIER_BLOCK_WORDS = 512 + 4096 +
+ *   32768 words.  f1 is int32 [NVF_OCC_HIER_CONTEXTS] on the device (an entry outside [1, 65535] is pulled inside).
+ * Occupancy words of a level: uint64 [batch, 512 >> 3 level], bit k of word w of a block = its cell 64 w + k, the
+ *   format of nvf_head_occ_bits.  batch <= NVF_OCC_HIER_MAX_BATCH everywhere.
+ * nvf_occ_hier_pyramid: p1 float [batch, 4096], k1 uint8 [batch, 4096], p2 float [batch, 512], k2 uint8 [batch, 512];
+ *   bad[0] += input errors (uint64, the caller clears it once).  gt (float [batch, 32768], may be NULL) non-zero =
+ *   occupied: gt_w0, gt_w1, gt_w2 receive its occupancy words at levels 0, 1 and 2 (untouched without gt).
+ * nvf_occ_hier_cells: wpb = words per block, 8, 64 or 512.  counts int32 [batch] = set bits per block.  cells (NULL:
+ *   counts only; must be NULL for wpb = 512) int32 [batch * wpb * 64], room for the all-full case: the occupied cells in
+ *   (block, raster) order, entry = block * (wpb * 64) + cell; entries past the set bits of the call are not written.
+ * nvf_occ_hier_hist: one level's coded symbols.  pv / kv are the level's values and child counts: (p2, k2) at level 2,
+ *   (p1, k1) at level 1, (p, k1) at level 0; gt_words the ground truth's words of that level; cells / counts the
+ *   nvf_occ_hier_cells list of the level above (unused at level 2).  cnt[ctx] += symbols, occ[ctx] += occupied ones
+ *   (uint64 [NVF_OCC_HIER_CONTEXTS] each, accumulated over calls, integers).
+ * nvf_occ_hier_encode: cells2 / counts2 and cells1 / counts1 are the lists of gt_w2 and gt_w1.  states, words, nwords
+ *   as nvf_occ_rans_encode with a region of group * NVF_OCC_HIER_BLOCK_WORDS words per group, filled from the end of
+ *   the region of its own blocks.
+ * nvf_occ_hier_decode: ONE section (level) of every group per call, level 2 first.  states uint64 [groups, 64] (in: the
+ *   pack's states or those the previous section left; out: the states after this section), pos int64 [groups] (words
+ *   consumed so far: 0 before level 2) and status int32 [groups] (cleared by the caller before level 2; flags are ORed
+ *   in) carry the coder from call to call.  pv / kv as nvf_occ_hier_hist; cells / counts the list of the words the
+ *   previous call decoded (unused at level 2).  occ_words of the level: level 2 writes every word; levels 1 and 0 OR
+ *   the occupied cells into words the caller has cleared.  words, word_off, nwords, total_words as
+ *   nvf_occ_rans_decode, and the same guarantee: no content of them makes the kernel read outside words[0 ..
+ *   total_words), and a damaged stream, which can decode ANY occupancy, writes inside occ_words and lists sized as
+ *   above.  Levels 2 and 1 can only report NVF_OCC_RANS_PAST_END, and only for a word that was wanted beyond the
+ *   group's words cut to the buffer: a stop there needs only a prefix of them.  Level 0 reports it as
+ *   nvf_occ_rans_decode does, also for a range that leaves the buffer, and adds NVF_OCC_RANS_BAD_STATE and
+ *   NVF_OCC_RANS_WORDS_LEFT. */
+#define NVF_OCC_HIER_CONTEXTS 3072
+#define NVF_OCC_HIER_BLOCK_WORDS 37376
+#define NVF_OCC_HIER_MAX_BATCH 32768
+int nvf_occ_hier_pyramid(const float* p, const float* gt, int batch, float* p1, uint8_t* k1, float* p2, uint8_t* k2,
+                         uint64_t* bad, uint64_t* gt_w0, uint64_t* gt_w1, uint64_t* gt_w2, void* stream);
+int nvf_occ_hier_cells(const uint64_t* words, int batch, int wpb, int32_t* counts, int32_t* cells, void* stream);
+int nvf_occ_hier_hist(int level, const float* pv, const uint8_t* kv, const uint64_t* gt_words, const int32_t* cells,
+                      const int32_t* counts, int batch, uint64_t* cnt, uint64_t* occ, void* stream);
+int nvf_occ_hier_encode(const float* p, const float* p1, const uint8_t* k1, const float* p2, const uint8_t* k2,
+                        const uint64_t* gt_w0, const uint64_t* gt_w1, const uint64_t* gt_w2, const int32_t* cells2,
+                        const int32_t* counts2, const int32_t* cells1, const int32_t* counts1, const int32_t* f1,
+                        int batch, int group, uint64_t* states, uint32_t* words, uint32_t* nwords, void* stream);
+int nvf_occ_hier_decode(int level, const float* pv, const uint8_t* kv, const int32_t* cells, const int32_t* counts,
+                        const int32_t* f1, uint64_t* states, int64_t* pos, const uint32_t* words, const int64_t* word_off,
+                        const uint32_t* nwords, int64_t total_words, int batch, int group, uint64_t* occ_words,
+                        int32_t* status, void* stream);
+
 /* ---- pre-processing on the device (nvfpcc_amd/preprocess.py: preprocess_device, csrc/pp_device.hip) ----------------
  * From int32 [P,3] points with coordinates of `bits` bits (10, 11 or 12; anything else is NVF_EINVAL) to everything
  * nvf_nearest_dist2 and the trainer take, without a host pass.  D = bits - 5 is the level of the 32^3 leaves.  A CELL

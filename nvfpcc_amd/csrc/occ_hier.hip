@@ -1,0 +1,475 @@
+// Scalable lossless geometry: the occupancy of every leaf block coded coarse to fine (nvfpcc_amd/lossless_lod_pack.py;
+// include/nvf_hip.h, "scalable lossless geometry", is the contract).  A block's 8^3 max-pool is coded first, then the
+// 16^3 cells under occupied 8^3 cells, then the voxels under occupied 16^3 cells: everything under an empty parent is
+// known, and a decoder that stops after the first or second section holds the exact max-pooled occupancy.
+//
+//   nvf_occ_hier_pyramid   p -> P1, K1, P2, K2 (the maxima and the clipped counts of the eight children above 0.5), the
+//                          input errors over ALL voxels, and with gt the ground truth's occupancy words of the three levels
+//   nvf_occ_hier_cells     occupancy words of a level -> set bits per block and the list of occupied cells in (block,
+//                          raster) order, entry = block * cells per block + cell
+//   nvf_occ_hier_hist      per context the coded symbols of one level and the occupied ones, exact integers
+//   nvf_occ_hier_encode    one 64-lane wave per group: sections 0, 1, 2, each backwards, ONE stream
+//   nvf_occ_hier_decode    one section per launch, states and word position in and out; a cell-list launch in between
+//
+// Symbol i of a section belongs to lane i % 64 at step i / 64; a lane past the section's end is idle: it neither codes
+// nor renormalises.  Frequencies depend on the pyramid alone, so a wave fetches OCC_AHEAD steps before it enters the
+// serial chain, as occ_rans.hip does; the gathers of a parent's eight children are four rows of two adjacent floats.
+#include "occ_coder.h"
+
+#define HIER_CTX 3072                                  // 3 levels x 4 child counts x 256
+#define HIER_AHEAD 8
+#define HIER_BLOCK_WORDS NVF_OCC_HIER_BLOCK_WORDS      // 512 + 4096 + 32768: an all-full block
+#define HIER_THREADS 1024
+
+namespace {
+
+__device__ __forceinline__ int hier_wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// sum of c[lo .. hi), the same value in every lane of the wave
+__device__ __forceinline__ int hier_sum(const int32_t* __restrict__ c, int lo, int hi, int lane) {
+  int s = 0;
+  for (int i = lo + lane; i < hi; i += 64) s += c[i];
+  return hier_wave_sum(s);
+}
+
+// symbol i of a section -> the cell whose value and occupancy bit it codes (index into the level's [batch, cells]
+// arrays) and the cell whose K gives its child count.  parents: the group's (or block's) occupied cells of the level
+// above; b0: the first block of the section (level 2 only, dense raster).
+template <int LEVEL>
+__device__ __forceinline__ void hier_where(int i, const int32_t* __restrict__ parents, int b0, int& cell, int& kcell) {
+  if constexpr (LEVEL == 2) {
+    cell = kcell = b0 * 512 + i;
+  } else {
+    const int e = parents[i >> 3], j = i & 7;
+    const int dz = j >> 2, dy = (j >> 1) & 1, dx = j & 1;
+    if constexpr (LEVEL == 1) {
+      const int b = e >> 9, c = e & 511;
+      const int z = 2 * (c >> 6) + dz, y = 2 * ((c >> 3) & 7) + dy, x = 2 * (c & 7) + dx;
+      cell = kcell = b * 4096 + (z * 16 + y) * 16 + x;
+    } else {
+      const int b = e >> 12, c = e & 4095;
+      const int z = 2 * (c >> 8) + dz, y = 2 * ((c >> 4) & 15) + dy, x = 2 * (c & 15) + dx;
+      cell = b * 32768 + (z * 32 + y) * 32 + x;
+      kcell = e;
+    }
+  }
+}
+
+__device__ __forceinline__ int hier_ctx(int level, int k, float v) { return (level * 4 + (k & 3)) * OCC_CTX + occ_ctx(v); }
+
+// m = c0; m = cj > m ? cj : m in child order: exact comparisons, the first of equal values (and of +-0) stays
+__device__ __forceinline__ void hier_fold(float c, float& m, int& k) {
+  m = c > m ? c : m;
+  k += c > 0.5f ? 1 : 0;
+}
+
+// one workgroup per block.  A: the input errors and the occupancy words of gt; B: the 16^3 level from p; C: the 8^3
+// level from P1 in LDS.  The coarse occupancy words come from the finer ones in LDS: a cell is occupied when a child is.
+__global__ __launch_bounds__(HIER_THREADS) void hier_pyramid_kernel(const float* __restrict__ p, const float* __restrict__ gt,
+                                                                    float* __restrict__ p1, uint8_t* __restrict__ k1,
+                                                                    float* __restrict__ p2, uint8_t* __restrict__ k2,
+                                                                    unsigned long long* __restrict__ bad,
+                                                                    unsigned long long* __restrict__ w0,
+                                                                    unsigned long long* __restrict__ w1,
+                                                                    unsigned long long* __restrict__ w2) {
+  __shared__ unsigned long long w0s[512];
+  __shared__ unsigned long long w1s[64];
+  __shared__ float p1s[4096];
+  __shared__ uint32_t nbad_s;
+  const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
+  const float* pb = p + (size_t)b * 32768;
+  if (tid == 0) nbad_s = 0;
+  __syncthreads();
+  uint32_t nbad = 0;
+  for (int it = 0; it < 32; ++it) {
+    const int v = it * HIER_THREADS + tid;
+    nbad += occ_bad(pb[v]) ? 1u : 0u;
+    if (gt) {
+      const unsigned long long word = __ballot(gt[(size_t)b * 32768 + v] != 0.f);
+      if (lane == 0) {
+        w0s[v >> 6] = word;
+        w0[(size_t)b * 512 + (v >> 6)] = word;
+      }
+    }
+  }
+  nbad = (uint32_t)hier_wave_sum((int)nbad);
+  if (lane == 0 && nbad) atomicAdd(&nbad_s, nbad);
+  __syncthreads();
+  if (tid == 0 && nbad_s) atomicAdd(bad, (unsigned long long)nbad_s);
+  for (int it = 0; it < 4; ++it) {
+    const int c = it * HIER_THREADS + tid;
+    const int Z = c >> 8, Y = (c >> 4) & 15, X = c & 15;
+    float m = 0.f;
+    int k = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {                     // four rows of two adjacent floats, in child order
+      const float2 v = *(const float2*)(pb + ((2 * Z + (r >> 1)) * 32 + 2 * Y + (r & 1)) * 32 + 2 * X);
+      if (r == 0) { m = v.x; k = v.x > 0.5f ? 1 : 0; } else hier_fold(v.x, m, k);
+      hier_fold(v.y, m, k);
+    }
+    p1s[c] = m;
+    p1[(size_t)b * 4096 + c] = m;
+    k1[(size_t)b * 4096 + c] = (uint8_t)(k > 3 ? 3 : k);
+    if (gt) {
+      const unsigned long long two = w0s[(2 * Z) * 16 + Y] | w0s[(2 * Z + 1) * 16 + Y];
+      const unsigned long long word = __ballot((((two >> (2 * X)) | (two >> (32 + 2 * X))) & 3ull) != 0ull);
+      if (lane == 0) {
+        w1s[c >> 6] = word;
+        w1[(size_t)b * 64 + (c >> 6)] = word;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid < 512) {                                     // waves 0..7, whole
+    const int c = tid;
+    const int Z = c >> 6, Y = (c >> 3) & 7, X = c & 7;
+    float m = 0.f;
+    int k = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float v = p1s[((2 * Z + (j >> 2)) * 16 + 2 * Y + ((j >> 1) & 1)) * 16 + 2 * X + (j & 1)];
+      if (j == 0) { m = v; k = v > 0.5f ? 1 : 0; } else hier_fold(v, m, k);
+    }
+    p2[(size_t)b * 512 + c] = m;
+    k2[(size_t)b * 512 + c] = (uint8_t)(k > 3 ? 3 : k);
+    if (gt) {
+      const unsigned long long two = w1s[(2 * Z) * 4 + (Y >> 1)] | w1s[(2 * Z + 1) * 4 + (Y >> 1)];
+      const int sh = 32 * (Y & 1) + 2 * X;
+      const unsigned long long word = __ballot((((two >> sh) | (two >> (sh + 16))) & 3ull) != 0ull);
+      if (lane == 0) w2[(size_t)b * 8 + (c >> 6)] = word;
+    }
+  }
+}
+
+// one wave per block, four blocks per workgroup
+__global__ __launch_bounds__(256) void hier_count_kernel(const unsigned long long* __restrict__ words, int batch, int wpb,
+                                                         int32_t* __restrict__ counts) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= batch) return;
+  int n = 0;
+  for (int w = lane; w < wpb; w += 64) n += __popcll(words[(size_t)b * wpb + w]);
+  n = hier_wave_sum(n);
+  if (lane == 0) counts[b] = n;
+}
+
+// the shape of points_from_bits32_kernel; a block's slots start at the set bits of the blocks before it, so every slot
+// is below the set bits of the call, and the list holds batch * wpb * 64 entries
+__global__ __launch_bounds__(256) void hier_cells_kernel(const unsigned long long* __restrict__ words, int batch, int wpb,
+                                                         const int32_t* __restrict__ counts, int32_t* __restrict__ cells) {
+  const int lane = threadIdx.x & 63;
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= batch) return;
+  int run = hier_sum(counts, 0, b, lane);
+  for (int w0 = 0; w0 < wpb; w0 += 64) {
+    const unsigned long long mine = w0 + lane < wpb ? words[(size_t)b * wpb + w0 + lane] : 0ull;
+    if (__ballot(mine != 0ull) == 0ull) continue;     // wave-uniform
+    for (int wi = 0; wi < 64; ++wi) {
+      const unsigned long long word = __shfl(mine, wi, 64);
+      if (word == 0ull) continue;                      // wave-uniform
+      if ((word >> lane) & 1ull)
+        cells[run + __popcll(word & ((1ull << lane) - 1ull))] = b * (wpb * 64) + 64 * (w0 + wi) + lane;
+      run += __popcll(word);
+    }
+  }
+}
+
+// one workgroup per block over the block's coded symbols of the level
+template <int LEVEL>
+__global__ __launch_bounds__(HIER_THREADS) void hier_hist_kernel(const float* __restrict__ pv, const uint8_t* __restrict__ kv,
+                                                                 const unsigned long long* __restrict__ gw,
+                                                                 const int32_t* __restrict__ cells,
+                                                                 const int32_t* __restrict__ counts,
+                                                                 unsigned long long* __restrict__ cnt,
+                                                                 unsigned long long* __restrict__ occ) {
+  __shared__ uint32_t h_cnt[4 * OCC_CTX];              // the level's own 1024 contexts
+  __shared__ uint32_t h_occ[4 * OCC_CTX];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  h_cnt[tid] = 0;
+  h_occ[tid] = 0;
+  __syncthreads();
+  int n = 512;
+  const int32_t* parents = nullptr;
+  if constexpr (LEVEL < 2) {
+    parents = cells + hier_sum(counts, 0, b, tid & 63);
+    n = 8 * counts[b];
+  }
+  for (int i = tid; i < n; i += HIER_THREADS) {
+    int cell, kcell;
+    hier_where<LEVEL>(i, parents, b, cell, kcell);
+    const int c = hier_ctx(0, kv[kcell], pv[cell]);
+    atomicAdd(&h_cnt[c], 1u);
+    if ((gw[cell >> 6] >> (cell & 63)) & 1ull) atomicAdd(&h_occ[c], 1u);
+  }
+  __syncthreads();
+  // integers: any order of these adds gives the same totals
+  if (h_cnt[tid]) atomicAdd(cnt + LEVEL * 4 * OCC_CTX + tid, (unsigned long long)h_cnt[tid]);
+  if (h_occ[tid]) atomicAdd(occ + LEVEL * 4 * OCC_CTX + tid, (unsigned long long)h_occ[tid]);
+}
+
+// the table in LDS, an entry outside [1, 65535] pulled inside: no frequency is ever 0
+__device__ __forceinline__ void hier_load_table(const int32_t* __restrict__ f1, uint32_t* tab, int lane) {
+  for (int i = lane; i < HIER_CTX; i += 64) {
+    const int v = f1[i];
+    tab[i] = (uint32_t)(v < 1 ? 1 : (v > 65535 ? 65535 : v));
+  }
+  __syncthreads();
+}
+
+// one section of a group, backwards.  The words written so far are wg[ptr .. region).
+template <int LEVEL>
+__device__ __forceinline__ void hier_encode_section(int n, const int32_t* __restrict__ parents, int b0,
+                                                    const float* __restrict__ pv, const uint8_t* __restrict__ kv,
+                                                    const unsigned long long* __restrict__ gw, const uint32_t* tab,
+                                                    int lane, unsigned long long& x, int& ptr, uint32_t* __restrict__ wg) {
+  const int steps = (n + 63) >> 6;
+  for (int t0 = (steps + HIER_AHEAD - 1) / HIER_AHEAD * HIER_AHEAD - HIER_AHEAD; t0 >= 0; t0 -= HIER_AHEAD) {
+    float val[HIER_AHEAD];
+    int kk[HIER_AHEAD], bit[HIER_AHEAD];
+    unsigned long long gword[HIER_AHEAD];
+#pragma unroll
+    for (int k = 0; k < HIER_AHEAD; ++k) {
+      const int i = (t0 + k) * 64 + lane;
+      int cell = 0, kcell = 0;
+      if (i < n) hier_where<LEVEL>(i, parents, b0, cell, kcell);
+      val[k] = pv[cell];
+      kk[k] = kv[kcell];
+      gword[k] = gw[cell >> 6];
+      bit[k] = cell & 63;
+    }
+    uint32_t fr[HIER_AHEAD], st[HIER_AHEAD];           // fr = 0: an idle lane
+#pragma unroll
+    for (int k = 0; k < HIER_AHEAD; ++k) {
+      const uint32_t one = tab[hier_ctx(LEVEL, kk[k], val[k])];
+      const bool s = (gword[k] >> bit[k]) & 1ull;
+      const bool live = (t0 + k) * 64 + lane < n;
+      fr[k] = !live ? 0u : (s ? one : 65536u - one);
+      st[k] = s ? 0u : one;
+    }
+#pragma unroll
+    for (int k = HIER_AHEAD - 1; k >= 0; --k) {
+      const bool live = fr[k] != 0u;
+      const bool emit = live && x >= ((unsigned long long)fr[k] << 47);
+      const unsigned long long m = __ballot(emit);
+      if (emit) {
+        const int at = ptr - 1 - __popcll((m >> lane) >> 1);   // the lanes above write first
+        if (at >= 0) wg[at] = (uint32_t)x;
+        x >>= 32;
+      }
+      ptr -= __popcll(m);
+      unsigned long long quot;
+      uint32_t rem;
+      occ_divmod(x, live ? fr[k] : 1u, quot, rem);
+      if (live) x = (quot << 16) + rem + st[k];
+    }
+  }
+}
+
+// one wave per group
+__global__ __launch_bounds__(64) void hier_encode_kernel(const float* __restrict__ p, const float* __restrict__ p1,
+                                                         const uint8_t* __restrict__ k1, const float* __restrict__ p2,
+                                                         const uint8_t* __restrict__ k2,
+                                                         const unsigned long long* __restrict__ w0,
+                                                         const unsigned long long* __restrict__ w1,
+                                                         const unsigned long long* __restrict__ w2,
+                                                         const int32_t* __restrict__ cells2, const int32_t* __restrict__ counts2,
+                                                         const int32_t* __restrict__ cells1, const int32_t* __restrict__ counts1,
+                                                         const int32_t* __restrict__ f1, int batch, int G,
+                                                         unsigned long long* __restrict__ states, uint32_t* __restrict__ words,
+                                                         uint32_t* __restrict__ nwords) {
+  __shared__ uint32_t tab[HIER_CTX];
+  const int lane = threadIdx.x, g = blockIdx.x;
+  hier_load_table(f1, tab, lane);
+  const int b0 = g * G, nb = min(G, batch - b0);
+  const int region = nb * HIER_BLOCK_WORDS;            // a symbol emits one word at the most
+  uint32_t* wg = words + (size_t)g * G * HIER_BLOCK_WORDS;
+  unsigned long long x = OCC_RANS_L;
+  int ptr = region;
+  hier_encode_section<0>(8 * hier_sum(counts1, b0, b0 + nb, lane), cells1 + hier_sum(counts1, 0, b0, lane), b0, p, k1, w0,
+                         tab, lane, x, ptr, wg);
+  hier_encode_section<1>(8 * hier_sum(counts2, b0, b0 + nb, lane), cells2 + hier_sum(counts2, 0, b0, lane), b0, p1, k1, w1,
+                         tab, lane, x, ptr, wg);
+  hier_encode_section<2>(nb * 512, nullptr, b0, p2, k2, w2, tab, lane, x, ptr, wg);
+  states[(size_t)g * 64 + lane] = x;
+  if (lane == 0) nwords[g] = (uint32_t)(region - ptr);
+}
+
+// one section of every group, forwards.  states, pos and status carry the coder from one section's launch to the next.
+template <int LEVEL>
+__global__ __launch_bounds__(64) void hier_decode_kernel(const float* __restrict__ pv, const uint8_t* __restrict__ kv,
+                                                         const int32_t* __restrict__ cells, const int32_t* __restrict__ counts,
+                                                         const int32_t* __restrict__ f1,
+                                                         unsigned long long* __restrict__ states, long long* __restrict__ pos_io,
+                                                         const uint32_t* __restrict__ words,
+                                                         const long long* __restrict__ word_off,
+                                                         const uint32_t* __restrict__ nwords, long long total_words,
+                                                         int batch, int G, unsigned long long* __restrict__ occ_words,
+                                                         int32_t* __restrict__ status) {
+  __shared__ uint32_t tab[HIER_CTX];
+  const int lane = threadIdx.x, g = blockIdx.x;
+  hier_load_table(f1, tab, lane);
+  const int b0 = g * G, nb = min(G, batch - b0);
+  // this group's words are words[off .. off + nw), cut to the buffer: nothing outside is ever read
+  long long off = word_off[g];
+  long long nw = (long long)nwords[g];
+  // (a stop before level 0 needs only a prefix of them: there the cut itself is no damage, a word wanted beyond it is)
+  bool damaged = false;
+  if (off < 0 || off > total_words) { off = 0; nw = 0; damaged = LEVEL == 0; }
+  if (nw > total_words - off) { nw = total_words - off; damaged = damaged || LEVEL == 0; }
+  const uint32_t* wg = words + off;
+  unsigned long long x = states[(size_t)g * 64 + lane];
+  long long pos = pos_io[g];
+  if (pos < 0) pos = 0;
+  int n = nb * 512;
+  const int32_t* parents = nullptr;
+  if constexpr (LEVEL < 2) {
+    n = 8 * hier_sum(counts, b0, b0 + nb, lane);
+    parents = cells + hier_sum(counts, 0, b0, lane);
+  }
+  const int steps = (n + 63) >> 6;
+  for (int t0 = 0; t0 < steps; t0 += HIER_AHEAD) {
+    float val[HIER_AHEAD];
+    int kk[HIER_AHEAD], where[HIER_AHEAD];
+#pragma unroll
+    for (int k = 0; k < HIER_AHEAD; ++k) {
+      const int i = (t0 + k) * 64 + lane;
+      int cell = 0, kcell = 0;
+      if (i < n) hier_where<LEVEL>(i, parents, b0, cell, kcell);
+      val[k] = pv[cell];
+      kk[k] = kv[kcell];
+      where[k] = cell;
+    }
+    uint32_t one[HIER_AHEAD];
+#pragma unroll
+    for (int k = 0; k < HIER_AHEAD; ++k) one[k] = tab[hier_ctx(LEVEL, kk[k], val[k])];
+#pragma unroll
+    for (int k = 0; k < HIER_AHEAD; ++k) {
+      const bool live = (t0 + k) * 64 + lane < n;
+      const uint32_t slot = (uint32_t)x & 0xFFFFu;
+      const bool s = live && slot < one[k];
+      if (live) {
+        const uint32_t f = s ? one[k] : 65536u - one[k];
+        const uint32_t start = s ? 0u : one[k];
+        x = (unsigned long long)f * (x >> 16) + slot - start;
+      }
+      const bool need = live && x < OCC_RANS_L;
+      const unsigned long long m = __ballot(need);
+      if (need) {
+        const long long at = pos + __popcll(m & ((1ull << lane) - 1ull));
+        uint32_t w = 0u;
+        if (at < nw) w = wg[at]; else damaged = true;          // past the end: a zero, and the status says so
+        x = (x << 32) | w;
+      }
+      pos += __popcll(m);
+      if constexpr (LEVEL == 2) {                      // dense raster: the ballot is the word
+        const unsigned long long word = __ballot(s);
+        if (lane == 0 && t0 + k < steps) occ_words[(size_t)b0 * 8 + t0 + k] = word;
+      } else {
+        if (s) atomicOr(&occ_words[where[k] >> 6], 1ull << (where[k] & 63));   // integer OR: any order, the same word
+      }
+    }
+  }
+  states[(size_t)g * 64 + lane] = x;
+  int st = 0;
+  if (__ballot(damaged) != 0ull) st |= NVF_OCC_RANS_PAST_END;
+  if constexpr (LEVEL == 0) {
+    if (__ballot(x != OCC_RANS_L) != 0ull) st |= NVF_OCC_RANS_BAD_STATE;
+    if (pos < (long long)nwords[g]) st |= NVF_OCC_RANS_WORDS_LEFT;
+  }
+  if (lane == 0) {
+    pos_io[g] = pos;
+    status[g] |= st;
+  }
+}
+
+}  // namespace
+
+extern "C" int nvf_occ_hier_pyramid(const float* p, const float* gt, int batch, float* p1, uint8_t* k1, float* p2,
+                                    uint8_t* k2, uint64_t* bad, uint64_t* gt_w0, uint64_t* gt_w1, uint64_t* gt_w2,
+                                    void* stream) {
+  if (!p || !p1 || !k1 || !p2 || !k2 || !bad || batch <= 0 || batch > NVF_OCC_HIER_MAX_BATCH) return NVF_EINVAL;
+  if (gt && (!gt_w0 || !gt_w1 || !gt_w2)) return NVF_EINVAL;
+  hier_pyramid_kernel<<<batch, HIER_THREADS, 0, nvf_stream(stream)>>>(
+      p, gt, p1, k1, p2, k2, (unsigned long long*)bad, (unsigned long long*)gt_w0, (unsigned long long*)gt_w1,
+      (unsigned long long*)gt_w2);
+  NVF_LAUNCH_CHECK();
+  return NVF_OK;
+}
+
+extern "C" int nvf_occ_hier_cells(const uint64_t* words, int batch, int wpb, int32_t* counts, int32_t* cells,
+                                  void* stream) {
+  if (!words || !counts || batch <= 0 || batch > NVF_OCC_HIER_MAX_BATCH || (wpb != 8 && wpb != 64 && wpb != 512))
+    return NVF_EINVAL;
+  if (cells && wpb == 512) return NVF_EINVAL;          // voxels have no children: their list is the point cloud
+  hier_count_kernel<<<(batch + 3) / 4, 256, 0, nvf_stream(stream)>>>((const unsigned long long*)words, batch, wpb, counts);
+  NVF_LAUNCH_CHECK();
+  if (cells) {
+    hier_cells_kernel<<<(batch + 3) / 4, 256, 0, nvf_stream(stream)>>>((const unsigned long long*)words, batch, wpb, counts,
+                                                                       cells);
+    NVF_LAUNCH_CHECK();
+  }
+  return NVF_OK;
+}
+
+extern "C" int nvf_occ_hier_hist(int level, const float* pv, const uint8_t* kv, const uint64_t* gt_words,
+                                 const int32_t* cells, const int32_t* counts, int batch, uint64_t* cnt, uint64_t* occ,
+                                 void* stream) {
+  if (!pv || !kv || !gt_words || !cnt || !occ || batch <= 0 || batch > NVF_OCC_HIER_MAX_BATCH || level < 0 || level > 2 ||
+      (level < 2 && (!cells || !counts)))
+    return NVF_EINVAL;
+  const unsigned long long* gw = (const unsigned long long*)gt_words;
+  unsigned long long *c = (unsigned long long*)cnt, *o = (unsigned long long*)occ;
+  hipStream_t s = nvf_stream(stream);
+  if (level == 2) hier_hist_kernel<2><<<batch, HIER_THREADS, 0, s>>>(pv, kv, gw, cells, counts, c, o);
+  if (level == 1) hier_hist_kernel<1><<<batch, HIER_THREADS, 0, s>>>(pv, kv, gw, cells, counts, c, o);
+  if (level == 0) hier_hist_kernel<0><<<batch, HIER_THREADS, 0, s>>>(pv, kv, gw, cells, counts, c, o);
+  NVF_LAUNCH_CHECK();
+  return NVF_OK;
+}
+
+extern "C" int nvf_occ_hier_encode(const float* p, const float* p1, const uint8_t* k1, const float* p2, const uint8_t* k2,
+                                   const uint64_t* gt_w0, const uint64_t* gt_w1, const uint64_t* gt_w2,
+                                   const int32_t* cells2, const int32_t* counts2, const int32_t* cells1,
+                                   const int32_t* counts1, const int32_t* f1, int batch, int group, uint64_t* states,
+                                   uint32_t* words, uint32_t* nwords, void* stream) {
+  if (!p || !p1 || !k1 || !p2 || !k2 || !gt_w0 || !gt_w1 || !gt_w2 || !cells2 || !counts2 || !cells1 || !counts1 || !f1 ||
+      !states || !words || !nwords || batch <= 0 || batch > NVF_OCC_HIER_MAX_BATCH || group < 1 ||
+      group > NVF_OCC_RANS_MAX_GROUP)
+    return NVF_EINVAL;
+  const int groups = (batch + group - 1) / group;
+  hier_encode_kernel<<<groups, 64, 0, nvf_stream(stream)>>>(
+      p, p1, k1, p2, k2, (const unsigned long long*)gt_w0, (const unsigned long long*)gt_w1,
+      (const unsigned long long*)gt_w2, cells2, counts2, cells1, counts1, f1, batch, group, (unsigned long long*)states,
+      words, nwords);
+  NVF_LAUNCH_CHECK();
+  return NVF_OK;
+}
+
+extern "C" int nvf_occ_hier_decode(int level, const float* pv, const uint8_t* kv, const int32_t* cells,
+                                   const int32_t* counts, const int32_t* f1, uint64_t* states, int64_t* pos,
+                                   const uint32_t* words, const int64_t* word_off, const uint32_t* nwords,
+                                   int64_t total_words, int batch, int group, uint64_t* occ_words, int32_t* status,
+                                   void* stream) {
+  if (!pv || !kv || !f1 || !states || !pos || !words || !word_off || !nwords || !occ_words || !status || total_words < 0 ||
+      batch <= 0 || batch > NVF_OCC_HIER_MAX_BATCH || group < 1 || group > NVF_OCC_RANS_MAX_GROUP || level < 0 ||
+      level > 2 || (level < 2 && (!cells || !counts)))
+    return NVF_EINVAL;
+  const int groups = (batch + group - 1) / group;
+  hipStream_t s = nvf_stream(stream);
+  unsigned long long *x = (unsigned long long*)states, *ow = (unsigned long long*)occ_words;
+  const long long* wo = (const long long*)word_off;
+  long long* ps = (long long*)pos;
+  const long long tw = (long long)total_words;
+  if (level == 2)
+    hier_decode_kernel<2><<<groups, 64, 0, s>>>(pv, kv, cells, counts, f1, x, ps, words, wo, nwords, tw, batch, group, ow, status);
+  if (level == 1)
+    hier_decode_kernel<1><<<groups, 64, 0, s>>>(pv, kv, cells, counts, f1, x, ps, words, wo, nwords, tw, batch, group, ow, status);
+  if (level == 0)
+    hier_decode_kernel<0><<<groups, 64, 0, s>>>(pv, kv, cells, counts, f1, x, ps, words, wo, nwords, tw, batch, group, ow, status);
+  NVF_LAUNCH_CHECK();
+  return NVF_OK;
+}

@@ -1494,3 +1494,147 @@ def points_from_bits32(words, counts, origins):
     check(lib().nvf_points_from_bits32(_ptr(words), _ptr(offsets), _ptr(origins), _ptr(points), total, B, _stream()),
           "nvf_points_from_bits32")
     return points[:total]
+
+
+# ---------------------------------------------------------------- scalable lossless geometry (csrc/occ_hier.hip)
+OCC_HIER_CONTEXTS = 3072
+OCC_HIER_BLOCK_WORDS = 512 + 4096 + 32768
+OCC_HIER_MAX_BATCH = 32768
+
+
+def occ_hier_cells(words, fill=True):
+    """Occupancy words int64 [B, 8 | 64 | 512] of a level -> (counts int32 [B] the set bits per block, cells int32
+    [B * cells per block]: the occupied cells in (block, raster) order, entry = block * cells per block + cell, the
+    first counts.sum() entries written; None with fill=False, and a 32^3 level has no list)."""
+    _chk(words)
+    B = words.shape[0]
+    if words.dtype != torch.int64 or words.dim() != 2 or words.shape[1] not in (8, 64, 512) or not 1 <= B <= OCC_HIER_MAX_BATCH:
+        raise RuntimeError("occ_hier_cells: words must be int64 [B, 8 | 64 | 512]")
+    wpb = words.shape[1]
+    if fill and wpb == 512:
+        raise RuntimeError("occ_hier_cells: the 32^3 level has no cell list (points_from_bits32 gives its points)")
+    counts = torch.empty(B, dtype=torch.int32, device=words.device)
+    cells = torch.empty(B * wpb * 64, dtype=torch.int32, device=words.device) if fill else None
+    check(lib().nvf_occ_hier_cells(_ptr(words), B, wpb, _ptr(counts), _ptr(cells), _stream()), "nvf_occ_hier_cells")
+    return counts, cells
+
+
+def occ_hier_pyramid(p, gt=None, bad=None):
+    """The pyramid of B blocks (include/nvf_hip.h, "scalable lossless geometry") -> a dict: 'p' [B, 32768], 'p1' float32
+    [B, 4096], 'k1' uint8 [B, 4096], 'p2' float32 [B, 512], 'k2' uint8 [B, 512], 'bad' int64 [1] (the input errors are
+    ADDED to the `bad` passed in; absent, it starts at zero).  With gt also 'gt_words': the ground truth's occupancy
+    words int64 [B, 512], [B, 64], [B, 8] of levels 0, 1, 2, and 'lists' = (cells2, counts2, cells1, counts1): the
+    occ_hier_cells lists of levels 2 and 1."""
+    B = _occ_blocks(p, gt)
+    if B > OCC_HIER_MAX_BATCH:
+        raise RuntimeError(f"the scalable occupancy coder takes at most {OCC_HIER_MAX_BATCH} blocks per call")
+    dev = p.device
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int64, device=dev)
+    _chk(bad)
+    if bad.dtype != torch.int64 or bad.shape != (1,):
+        raise RuntimeError("occ_hier_pyramid: bad is int64 [1]")
+    out = {"p": p.reshape(B, 32768), "bad": bad,
+           "p1": torch.empty((B, 4096), dtype=torch.float32, device=dev), "k1": torch.empty((B, 4096), dtype=torch.uint8, device=dev),
+           "p2": torch.empty((B, 512), dtype=torch.float32, device=dev), "k2": torch.empty((B, 512), dtype=torch.uint8, device=dev)}
+    gw = None if gt is None else tuple(torch.empty((B, n), dtype=torch.int64, device=dev) for n in (512, 64, 8))
+    check(lib().nvf_occ_hier_pyramid(_ptr(p), _ptr(gt), B, _ptr(out["p1"]), _ptr(out["k1"]), _ptr(out["p2"]), _ptr(out["k2"]),
+                                     _ptr(bad), *((None,) * 3 if gw is None else (_ptr(w) for w in gw)), _stream()),
+          "nvf_occ_hier_pyramid")
+    if gw is not None:
+        counts2, cells2 = occ_hier_cells(gw[2])
+        counts1, cells1 = occ_hier_cells(gw[1])
+        out["gt_words"], out["lists"] = gw, (cells2, counts2, cells1, counts1)
+    return out
+
+
+def _occ_hier_level(pyr, level):
+    """(values, child counts) a level's symbols are coded under."""
+    return ((pyr["p"], pyr["k1"]), (pyr["p1"], pyr["k1"]), (pyr["p2"], pyr["k2"]))[level]
+
+
+def _occ_hier_table(f1, dev):
+    _chk(f1)
+    if f1.dtype != torch.int32 or f1.shape != (OCC_HIER_CONTEXTS,) or f1.device != dev:
+        raise RuntimeError(f"f1 must be int32 [{OCC_HIER_CONTEXTS}] on the device of p")
+
+
+def occ_hier_hist(pyr, cnt=None, occ=None):
+    """Coded symbols and occupied ones per context of a pyramid with ground truth, over the three levels, added to cnt
+    and occ (int64 [3072] holding the uint64 sums; absent, they start at zero).  -> (cnt, occ)."""
+    B, dev = pyr["p"].shape[0], pyr["p"].device
+    if cnt is None:
+        cnt, occ = (torch.zeros(OCC_HIER_CONTEXTS, dtype=torch.int64, device=dev) for _ in range(2))
+    _chk(cnt, occ)
+    if any(t.dtype != torch.int64 or t.shape != (OCC_HIER_CONTEXTS,) for t in (cnt, occ)):
+        raise RuntimeError(f"occ_hier_hist: cnt and occ are int64 [{OCC_HIER_CONTEXTS}]")
+    cells2, counts2, cells1, counts1 = pyr["lists"]
+    for level, cells, counts in ((2, None, None), (1, cells2, counts2), (0, cells1, counts1)):
+        pv, kv = _occ_hier_level(pyr, level)
+        check(lib().nvf_occ_hier_hist(level, _ptr(pv), _ptr(kv), _ptr(pyr["gt_words"][level]), _ptr(cells), _ptr(counts), B,
+                                      _ptr(cnt), _ptr(occ), _stream()), "nvf_occ_hier_hist")
+    return cnt, occ
+
+
+def occ_hier_encode(pyr, f1, group):
+    """The three sections of every group of `group` blocks of a pyramid with ground truth, coded under the table f1
+    (int32 [3072]) into one stream per group -> (states int64 [groups, 64], words: one int32 tensor per group, in the
+    decoder's reading order)."""
+    B, dev = pyr["p"].shape[0], pyr["p"].device
+    _occ_hier_table(f1, dev)
+    G = int(group)
+    if not 1 <= G <= OCC_RANS_MAX_GROUP:
+        raise RuntimeError(f"group must be in [1, {OCC_RANS_MAX_GROUP}], got {group!r}")
+    ng = (B + G - 1) // G
+    states = torch.empty((ng, 64), dtype=torch.int64, device=dev)
+    region = torch.empty((ng, G * OCC_HIER_BLOCK_WORDS), dtype=torch.int32, device=dev)
+    nwords = torch.empty(ng, dtype=torch.int32, device=dev)
+    w0, w1, w2 = pyr["gt_words"]
+    cells2, counts2, cells1, counts1 = pyr["lists"]
+    check(lib().nvf_occ_hier_encode(_ptr(pyr["p"]), _ptr(pyr["p1"]), _ptr(pyr["k1"]), _ptr(pyr["p2"]), _ptr(pyr["k2"]),
+                                    _ptr(w0), _ptr(w1), _ptr(w2), _ptr(cells2), _ptr(counts2), _ptr(cells1), _ptr(counts1),
+                                    _ptr(f1), B, G, _ptr(states), _ptr(region), _ptr(nwords), _stream()),
+          "nvf_occ_hier_encode")
+    words = []
+    for g, n in enumerate(nwords.tolist()):
+        end = min(G, B - g * G) * OCC_HIER_BLOCK_WORDS
+        words.append(region[g, end - n:end].clone())
+    return states, words
+
+
+def occ_hier_decode(pyr, f1, states, words, nwords, group, level=0):
+    """The inverse of occ_hier_encode down to `level` (2: the first section only, 1: two sections, 0: all three):
+    states int64 [groups, 64], words int32 [total] the groups' words back to back, nwords int32 [groups] ->
+    (occ_words int64 [B, 512 >> 3 * level] of that level, counts int32 [B], status int32 [groups], pos int64 [groups]
+    the words each group consumed).  status: 0, or OCC_RANS_PAST_END; at level 0 also _BAD_STATE / _WORDS_LEFT.  A
+    damaged stream cannot make a kernel read outside `words` or write outside its outputs."""
+    B, dev = pyr["p"].shape[0], pyr["p"].device
+    _occ_hier_table(f1, dev)
+    G = int(group)
+    if not 1 <= G <= OCC_RANS_MAX_GROUP:
+        raise RuntimeError(f"group must be in [1, {OCC_RANS_MAX_GROUP}], got {group!r}")
+    if level not in (0, 1, 2):
+        raise RuntimeError(f"level must be 0, 1 or 2, got {level!r}")
+    ng = (B + G - 1) // G
+    _chk(states, words, nwords)
+    if states.dtype != torch.int64 or states.shape != (ng, 64) or words.dtype != torch.int32 or words.dim() != 1 or \
+            nwords.dtype != torch.int32 or nwords.shape != (ng,):
+        raise RuntimeError(f"occ_hier_decode: {B} blocks in groups of {G} take states int64 [{ng}, 64], words int32 [n] "
+                           f"and nwords int32 [{ng}]")
+    n64 = nwords.to(torch.int64) & 0xFFFFFFFF
+    word_off = (torch.cumsum(n64, 0) - n64).contiguous()
+    total = words.numel()
+    if total == 0:                              # a pointer to pass; total_words = 0 keeps the kernels away from it
+        words = torch.zeros(1, dtype=torch.int32, device=dev)
+    x = states.clone()
+    pos = torch.zeros(ng, dtype=torch.int64, device=dev)
+    status = torch.zeros(ng, dtype=torch.int32, device=dev)
+    cells = counts = None
+    for lv in (2, 1, 0)[:3 - level]:
+        pv, kv = _occ_hier_level(pyr, lv)
+        occ_words = torch.zeros((B, 512 >> 3 * lv), dtype=torch.int64, device=dev)
+        check(lib().nvf_occ_hier_decode(lv, _ptr(pv), _ptr(kv), _ptr(cells), _ptr(counts), _ptr(f1), _ptr(x), _ptr(pos),
+                                        _ptr(words), _ptr(word_off), _ptr(nwords), total, B, G, _ptr(occ_words),
+                                        _ptr(status), _stream()), "nvf_occ_hier_decode")
+        counts, cells = occ_hier_cells(occ_words, fill=lv > level)
+    return occ_words, counts, status, pos
