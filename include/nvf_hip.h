@@ -845,9 +845,10 @@ int nvf_threshold_compact_v(const float* p, const float* thh, const int32_t* off
  *   the same fmaf chain and the same sigmoid, never written to memory.  counts int32 [batch] = set bits per block
  *   (cleared by the call, popcounts added in integers).  (c, d) is (8, 16), (16, 16), (16, 8) or (32, 8); anything
  *   else is NVF_EINVAL before any device work.
- * nvf_points_from_bits: words as above, d = 16 or 8; offsets int32 [batch] the exclusive prefix sum of counts; origins
- *   int32 [batch, 3] (NULL: zeros); points int32 [n, 3] receives (origin >> shift) + (z, y, x) per set bit in (block,
- *   z, y, x) order, the order of nvf_threshold_compact.  shift = 0..2.  A slot outside [0, n) is not written. */
+ * nvf_points_from_bits: words as above, d = 8, 16 or 32 (8, 64 or 512 words per block; 32 is the grid of the lossless
+ *   coders' occupancy words, below); offsets int32 [batch] the exclusive prefix sum of counts; origins int32 [batch, 3]
+ *   (NULL: zeros); points int32 [n, 3] receives (origin >> shift) + (z, y, x) per set bit in (block, z, y, x) order,
+ *   the order of nvf_threshold_compact.  shift = 0..2.  A slot outside [0, n) is not written. */
 int nvf_head_occ_bits(const float* x, const float* w_fwd, const float* bias, float thh, const float* thh_v,
                       uint64_t* words, int32_t* counts, int batch, int c, int d, void* stream);
 int nvf_points_from_bits(const uint64_t* words, const int32_t* offsets, const int32_t* origins, int32_t* points, int n,
@@ -877,7 +878,8 @@ int nvf_points_from_bits(const uint64_t* words, const int32_t* offsets, const in
  *   was wanted beyond the group's words, or its range leaves [0, total_words): such reads yield 0 and touch no memory),
  *   NVF_OCC_RANS_BAD_STATE (a final state is not 2^31) and NVF_OCC_RANS_WORDS_LEFT (words were left over).  No content
  *   of states, words, word_off or nwords makes the kernel read outside words[0 .. total_words).
- * nvf_points_from_bits32: nvf_points_from_bits for d = 32 (512 words per block), shift 0. */
+ * nvf_points_from_bits (d = 32, shift 0) turns occ_words and counts into the points.
+ * The coder's step, a group's word window and the status are csrc/occ_coder.h's, shared with the scalable coder below. */
 #define NVF_OCC_RANS_MAX_GROUP 1024
 #define NVF_OCC_RANS_PAST_END 1
 #define NVF_OCC_RANS_BAD_STATE 2
@@ -889,8 +891,6 @@ int nvf_occ_rans_encode(const float* p, const float* gt, const int32_t* f1, int 
 int nvf_occ_rans_decode(const float* p, const int32_t* f1, const uint64_t* states, const uint32_t* words,
                         const int64_t* word_off, const uint32_t* nwords, int64_t total_words, int batch, int group,
                         uint64_t* occ_words, int32_t* counts, int32_t* status, void* stream);
-int nvf_points_from_bits32(const uint64_t* words, const int32_t* offsets, const int32_t* origins, int32_t* points, int n,
-                           int batch, void* stream);
 
 /* ---- scalable lossless geometry (nvfpcc_amd/lossless_lod_pack.py, csrc/occ_hier.hip) --------------------------------
  * The same occupancy coded coarse to fine in ONE stream per group: a decoder that stops after the first or the second

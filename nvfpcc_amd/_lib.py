@@ -139,7 +139,6 @@ PROTOTYPES = {
     "nvf_occ_ctx_hist": (I, [P, P, I, I, P, P, P, P]),
     "nvf_occ_rans_encode": (I, [P, P, P, I, I, P, P, P, P, P]),
     "nvf_occ_rans_decode": (I, [P, P, P, P, P, P, L, I, I, P, P, P, P]),
-    "nvf_points_from_bits32": (I, [P, P, P, P, I, I, P]),
     "nvf_occ_hier_pyramid": (I, [P, P, I, P, P, P, P, P, P, P, P, P]),
     "nvf_occ_hier_cells": (I, [P, I, I, P, P, P]),
     "nvf_occ_hier_hist": (I, [I, P, P, P, P, P, I, P, P, P]),

@@ -7,9 +7,12 @@
 //                          sixteen consecutive lanes own 64 consecutive voxels; each lane fetches the hit bit of "its"
 //                          voxel of word j from lane 16 j + lane / 4 and ONE ballot of the wave is word j.  Counts are
 //                          popcounts, added in integers.
-//   nvf_points_from_bits   one wave per block walks the block's words in order; lane k owns bit k, its output slot is the
-//                          block's offset + the bits before it.  No workgroup waits for another.
+//   nvf_points_from_bits   one wave per block walks the block's words in order (occ_coder.h: occ_walk_bits, the walk
+//                          the lossless coder's cell lists share); lane k owns bit k, its output slot is the block's
+//                          offset + the bits before it.  d = 8, 16 or 32: 8, 64 or 512 words per block, 64 at a time.
+//                          No workgroup waits for another.
 #include "head_fwd.h"
+#include "occ_coder.h"
 
 namespace {
 
@@ -66,24 +69,16 @@ __global__ __launch_bounds__(256) void points_from_bits_kernel(const unsigned lo
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= batch) return;
-  const int wpb = d * d * d / 64;                     // 64 (16^3) or 8 (8^3): one word per lane at the most
-  const unsigned long long mine = lane < wpb ? words[(size_t)b * wpb + lane] : 0ull;
+  const int ld = d == 8 ? 3 : (d == 16 ? 4 : 5);       // d is a power of two: shifts, the integers of / and %
   const int oz = origins ? origins[3 * b] >> shift : 0, oy = origins ? origins[3 * b + 1] >> shift : 0,
             ox = origins ? origins[3 * b + 2] >> shift : 0;
-  int run = offsets[b];
-  for (int wi = 0; wi < wpb; ++wi) {
-    const unsigned long long word = __shfl(mine, wi, 64);
-    if (word == 0ull) continue;                       // wave-uniform
-    const int slot = run + __popcll(word & ((1ull << lane) - 1ull));
-    if (((word >> lane) & 1ull) && slot >= 0 && slot < n) {
-      const int v = 64 * wi + lane;
-      int32_t* o = points + (size_t)slot * 3;
-      o[0] = oz + v / (d * d);
-      o[1] = oy + (v / d) % d;
-      o[2] = ox + v % d;
-    }
-    run += __popcll(word);
-  }
+  occ_walk_bits(words, b, d * d * d / 64, offsets[b], lane, [=](int slot, int v) {
+    if (slot < 0 || slot >= n) return;
+    int32_t* o = points + (size_t)slot * 3;
+    o[0] = oz + (v >> (2 * ld));
+    o[1] = oy + ((v >> ld) & (d - 1));
+    o[2] = ox + (v & (d - 1));
+  });
 }
 
 }  // namespace
@@ -113,7 +108,7 @@ extern "C" int nvf_head_occ_bits(const float* x, const float* w_fwd, const float
 
 extern "C" int nvf_points_from_bits(const uint64_t* words, const int32_t* offsets, const int32_t* origins,
                                     int32_t* points, int n, int batch, int d, int shift, void* stream) {
-  if (!words || !offsets || !points || n < 0 || batch <= 0 || (d != 8 && d != 16) || shift < 0 || shift > 2)
+  if (!words || !offsets || !points || n < 0 || batch <= 0 || (d != 8 && d != 16 && d != 32) || shift < 0 || shift > 2)
     return NVF_EINVAL;
   points_from_bits_kernel<<<(batch + 3) / 4, 256, 0, nvf_stream(stream)>>>((const unsigned long long*)words, offsets,
                                                                            origins, points, batch, d, shift, n);

@@ -14,6 +14,8 @@
 // Symbol i of a section belongs to lane i % 64 at step i / 64; a lane past the section's end is idle: it neither codes
 // nor renormalises.  Frequencies depend on the pyramid alone, so a wave fetches OCC_AHEAD steps before it enters the
 // serial chain, as occ_rans.hip does; the gathers of a parent's eight children are four rows of two adjacent floats.
+// The chain itself -- the step with its idle lanes, the word window, the status -- and the walk behind the cell lists
+// are occ_coder.h's.
 #include "occ_coder.h"
 
 #define HIER_CTX 3072                                  // 3 levels x 4 child counts x 256
@@ -157,25 +159,15 @@ __global__ __launch_bounds__(256) void hier_count_kernel(const unsigned long lon
   if (lane == 0) counts[b] = n;
 }
 
-// the shape of points_from_bits32_kernel; a block's slots start at the set bits of the blocks before it, so every slot
-// is below the set bits of the call, and the list holds batch * wpb * 64 entries
+// occ_walk_bits with the cell list as its sink; a block's slots start at the set bits of the blocks before it, so every
+// slot is below the set bits of the call, and the list holds batch * wpb * 64 entries
 __global__ __launch_bounds__(256) void hier_cells_kernel(const unsigned long long* __restrict__ words, int batch, int wpb,
                                                          const int32_t* __restrict__ counts, int32_t* __restrict__ cells) {
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= batch) return;
-  int run = hier_sum(counts, 0, b, lane);
-  for (int w0 = 0; w0 < wpb; w0 += 64) {
-    const unsigned long long mine = w0 + lane < wpb ? words[(size_t)b * wpb + w0 + lane] : 0ull;
-    if (__ballot(mine != 0ull) == 0ull) continue;     // wave-uniform
-    for (int wi = 0; wi < 64; ++wi) {
-      const unsigned long long word = __shfl(mine, wi, 64);
-      if (word == 0ull) continue;                      // wave-uniform
-      if ((word >> lane) & 1ull)
-        cells[run + __popcll(word & ((1ull << lane) - 1ull))] = b * (wpb * 64) + 64 * (w0 + wi) + lane;
-      run += __popcll(word);
-    }
-  }
+  occ_walk_bits(words, b, wpb, hier_sum(counts, 0, b, lane), lane,
+                [=](int slot, int cell) { cells[slot] = b * (wpb * 64) + cell; });
 }
 
 // one workgroup per block over the block's coded symbols of the level
@@ -211,15 +203,6 @@ __global__ __launch_bounds__(HIER_THREADS) void hier_hist_kernel(const float* __
   if (h_occ[tid]) atomicAdd(occ + LEVEL * 4 * OCC_CTX + tid, (unsigned long long)h_occ[tid]);
 }
 
-// the table in LDS, an entry outside [1, 65535] pulled inside: no frequency is ever 0
-__device__ __forceinline__ void hier_load_table(const int32_t* __restrict__ f1, uint32_t* tab, int lane) {
-  for (int i = lane; i < HIER_CTX; i += 64) {
-    const int v = f1[i];
-    tab[i] = (uint32_t)(v < 1 ? 1 : (v > 65535 ? 65535 : v));
-  }
-  __syncthreads();
-}
-
 // one section of a group, backwards.  The words written so far are wg[ptr .. region).
 template <int LEVEL>
 __device__ __forceinline__ void hier_encode_section(int n, const int32_t* __restrict__ parents, int b0,
@@ -251,21 +234,8 @@ __device__ __forceinline__ void hier_encode_section(int n, const int32_t* __rest
       st[k] = s ? 0u : one;
     }
 #pragma unroll
-    for (int k = HIER_AHEAD - 1; k >= 0; --k) {
-      const bool live = fr[k] != 0u;
-      const bool emit = live && x >= ((unsigned long long)fr[k] << 47);
-      const unsigned long long m = __ballot(emit);
-      if (emit) {
-        const int at = ptr - 1 - __popcll((m >> lane) >> 1);   // the lanes above write first
-        if (at >= 0) wg[at] = (uint32_t)x;
-        x >>= 32;
-      }
-      ptr -= __popcll(m);
-      unsigned long long quot;
-      uint32_t rem;
-      occ_divmod(x, live ? fr[k] : 1u, quot, rem);
-      if (live) x = (quot << 16) + rem + st[k];
-    }
+    for (int k = HIER_AHEAD - 1; k >= 0; --k)
+      occ_encode_step<true>(x, fr[k], st[k], ptr, wg, lane);
   }
 }
 
@@ -283,7 +253,7 @@ __global__ __launch_bounds__(64) void hier_encode_kernel(const float* __restrict
                                                          uint32_t* __restrict__ nwords) {
   __shared__ uint32_t tab[HIER_CTX];
   const int lane = threadIdx.x, g = blockIdx.x;
-  hier_load_table(f1, tab, lane);
+  occ_load_table<HIER_CTX>(f1, tab, lane);
   const int b0 = g * G, nb = min(G, batch - b0);
   const int region = nb * HIER_BLOCK_WORDS;            // a symbol emits one word at the most
   uint32_t* wg = words + (size_t)g * G * HIER_BLOCK_WORDS;
@@ -311,19 +281,12 @@ __global__ __launch_bounds__(64) void hier_decode_kernel(const float* __restrict
                                                          int32_t* __restrict__ status) {
   __shared__ uint32_t tab[HIER_CTX];
   const int lane = threadIdx.x, g = blockIdx.x;
-  hier_load_table(f1, tab, lane);
+  occ_load_table<HIER_CTX>(f1, tab, lane);
   const int b0 = g * G, nb = min(G, batch - b0);
-  // this group's words are words[off .. off + nw), cut to the buffer: nothing outside is ever read
-  long long off = word_off[g];
-  long long nw = (long long)nwords[g];
-  // (a stop before level 0 needs only a prefix of them: there the cut itself is no damage, a word wanted beyond it is)
-  bool damaged = false;
-  if (off < 0 || off > total_words) { off = 0; nw = 0; damaged = LEVEL == 0; }
-  if (nw > total_words - off) { nw = total_words - off; damaged = damaged || LEVEL == 0; }
-  const uint32_t* wg = words + off;
+  // a stop before level 0 needs only a prefix of the group's words: there the cut alone is no damage
+  OccWindow w = occ_window_open(words, word_off[g], (long long)nwords[g], total_words, LEVEL == 0);
   unsigned long long x = states[(size_t)g * 64 + lane];
-  long long pos = pos_io[g];
-  if (pos < 0) pos = 0;
+  w.pos = max(pos_io[g], 0ll);
   int n = nb * 512;
   const int32_t* parents = nullptr;
   if constexpr (LEVEL < 2) {
@@ -348,23 +311,7 @@ __global__ __launch_bounds__(64) void hier_decode_kernel(const float* __restrict
     for (int k = 0; k < HIER_AHEAD; ++k) one[k] = tab[hier_ctx(LEVEL, kk[k], val[k])];
 #pragma unroll
     for (int k = 0; k < HIER_AHEAD; ++k) {
-      const bool live = (t0 + k) * 64 + lane < n;
-      const uint32_t slot = (uint32_t)x & 0xFFFFu;
-      const bool s = live && slot < one[k];
-      if (live) {
-        const uint32_t f = s ? one[k] : 65536u - one[k];
-        const uint32_t start = s ? 0u : one[k];
-        x = (unsigned long long)f * (x >> 16) + slot - start;
-      }
-      const bool need = live && x < OCC_RANS_L;
-      const unsigned long long m = __ballot(need);
-      if (need) {
-        const long long at = pos + __popcll(m & ((1ull << lane) - 1ull));
-        uint32_t w = 0u;
-        if (at < nw) w = wg[at]; else damaged = true;          // past the end: a zero, and the status says so
-        x = (x << 32) | w;
-      }
-      pos += __popcll(m);
+      const bool s = occ_decode_step<true>(x, one[k], (t0 + k) * 64 + lane < n, w, lane);
       if constexpr (LEVEL == 2) {                      // dense raster: the ballot is the word
         const unsigned long long word = __ballot(s);
         if (lane == 0 && t0 + k < steps) occ_words[(size_t)b0 * 8 + t0 + k] = word;
@@ -374,14 +321,10 @@ __global__ __launch_bounds__(64) void hier_decode_kernel(const float* __restrict
     }
   }
   states[(size_t)g * 64 + lane] = x;
-  int st = 0;
-  if (__ballot(damaged) != 0ull) st |= NVF_OCC_RANS_PAST_END;
-  if constexpr (LEVEL == 0) {
-    if (__ballot(x != OCC_RANS_L) != 0ull) st |= NVF_OCC_RANS_BAD_STATE;
-    if (pos < (long long)nwords[g]) st |= NVF_OCC_RANS_WORDS_LEFT;
-  }
+  // the final states and the word count are the whole stream's: only level 0 has them behind it
+  const int st = occ_window_status(w, x, (long long)nwords[g]) & (LEVEL == 0 ? ~0 : NVF_OCC_RANS_PAST_END);
   if (lane == 0) {
-    pos_io[g] = pos;
+    pos_io[g] = w.pos;
     status[g] |= st;
   }
 }

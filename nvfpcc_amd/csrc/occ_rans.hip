@@ -15,10 +15,10 @@
 //                           step t IS occupancy word t % 512 of block t / 512, the word format of nvf_head_occ_bits.
 //                           Every word index is checked against the group's word count: a damaged stream sets the group's
 //                           status and reads zeros, it cannot make the kernel read outside its words.
-//   nvf_points_from_bits32  nvf_points_from_bits for the 32^3 grid: 512 words per block, 64 at a time.
 //
 // Only the state recurrence is serial: contexts and frequencies depend on p alone, so each wave fetches OCC_AHEAD steps
-// of p (and of the ground truth) at once and looks their frequencies up in LDS before it enters the chain.
+// of p (and of the ground truth) at once and looks their frequencies up in LDS before it enters the chain.  The chain
+// itself -- the step, the word window, the status -- is occ_coder.h's, shared with occ_hier.hip; no lane is ever idle here.
 #include "occ_coder.h"
 
 #define OCC_VOX 32768                                  // voxels of a 32^3 block
@@ -84,16 +84,6 @@ __global__ __launch_bounds__(OCC_HIST_THREADS) void occ_ctx_hist_kernel(const fl
   if (tid == 0 && h_bad) atomicAdd(bad, (unsigned long long)h_bad);
 }
 
-// the table in LDS, an entry outside [1, 65535] pulled inside: no frequency is ever 0
-__device__ __forceinline__ void occ_load_table(const int32_t* __restrict__ f1, uint32_t* tab, int lane) {
-#pragma unroll
-  for (int i = lane; i < OCC_CTX; i += 64) {
-    const int v = f1[i];
-    tab[i] = (uint32_t)(v < 1 ? 1 : (v > 65535 ? 65535 : v));
-  }
-  __syncthreads();
-}
-
 // one wave per group
 __global__ __launch_bounds__(64) void occ_rans_encode_kernel(const float* __restrict__ p, const float* __restrict__ gt,
                                                              const int32_t* __restrict__ f1, int batch, int G,
@@ -102,7 +92,7 @@ __global__ __launch_bounds__(64) void occ_rans_encode_kernel(const float* __rest
                                                              unsigned long long* __restrict__ gt_words) {
   __shared__ uint32_t tab[OCC_CTX];
   const int lane = threadIdx.x, g = blockIdx.x;
-  occ_load_table(f1, tab, lane);
+  occ_load_table<OCC_CTX>(f1, tab, lane);
   const int b0 = g * G, nb = min(G, batch - b0);
   const int steps = nb * OCC_WPB;
   const int region = nb * OCC_VOX;                     // a symbol emits one word at the most
@@ -129,20 +119,8 @@ __global__ __launch_bounds__(64) void occ_rans_encode_kernel(const float* __rest
       if (gt_words && lane == 0) gt_words[(size_t)b0 * OCC_WPB + t0 + k] = word;
     }
 #pragma unroll
-    for (int k = OCC_AHEAD - 1; k >= 0; --k) {
-      const bool emit = x >= ((unsigned long long)fr[k] << 47);
-      const unsigned long long m = __ballot(emit);
-      if (emit) {
-        const int at = ptr - 1 - __popcll((m >> lane) >> 1);   // the lanes above write first
-        if (at >= 0) wg[at] = (uint32_t)x;
-        x >>= 32;
-      }
-      ptr -= __popcll(m);
-      unsigned long long quot;
-      uint32_t rem;
-      occ_divmod(x, fr[k], quot, rem);
-      x = (quot << 16) + rem + st[k];
-    }
+    for (int k = OCC_AHEAD - 1; k >= 0; --k)
+      occ_encode_step<false>(x, fr[k], st[k], ptr, wg, lane);
   }
   states[(size_t)g * 64 + lane] = x;
   if (lane == 0) nwords[g] = (uint32_t)(region - ptr);
@@ -157,18 +135,11 @@ __global__ __launch_bounds__(64) void occ_rans_decode_kernel(const float* __rest
                                                              int32_t* __restrict__ counts, int32_t* __restrict__ status) {
   __shared__ uint32_t tab[OCC_CTX];
   const int lane = threadIdx.x, g = blockIdx.x;
-  occ_load_table(f1, tab, lane);
+  occ_load_table<OCC_CTX>(f1, tab, lane);
   const int b0 = g * G, nb = min(G, batch - b0);
   const float* pg = p + (size_t)b0 * OCC_VOX;
-  // this group's words are words[off .. off + n), cut to the buffer: nothing outside is ever read
-  long long off = word_off[g];
-  long long n = (long long)nwords[g];
-  bool damaged = false;
-  if (off < 0 || off > total_words) { off = 0; n = 0; damaged = true; }
-  if (n > total_words - off) { n = total_words - off; damaged = true; }
-  const uint32_t* wg = words + off;
+  OccWindow w = occ_window_open(words, word_off[g], (long long)nwords[g], total_words, true);
   unsigned long long x = states[(size_t)g * 64 + lane];
-  long long pos = 0;
   for (int bl = 0; bl < nb; ++bl) {
     int cnt = 0;
     for (int t0 = 0; t0 < OCC_WPB; t0 += OCC_AHEAD) {
@@ -177,20 +148,7 @@ __global__ __launch_bounds__(64) void occ_rans_decode_kernel(const float* __rest
       for (int k = 0; k < OCC_AHEAD; ++k) one[k] = tab[occ_ctx(pg[((size_t)bl * OCC_WPB + t0 + k) * 64 + lane])];
 #pragma unroll
       for (int k = 0; k < OCC_AHEAD; ++k) {
-        const uint32_t slot = (uint32_t)x & 0xFFFFu;
-        const bool s = slot < one[k];
-        const uint32_t f = s ? one[k] : 65536u - one[k];
-        const uint32_t start = s ? 0u : one[k];
-        x = (unsigned long long)f * (x >> 16) + slot - start;
-        const bool need = x < OCC_RANS_L;
-        const unsigned long long m = __ballot(need);
-        if (need) {
-          const long long at = pos + __popcll(m & ((1ull << lane) - 1ull));
-          uint32_t w = 0u;
-          if (at < n) w = wg[at]; else damaged = true;          // past the end: a zero, and the status says so
-          x = (x << 32) | w;
-        }
-        pos += __popcll(m);
+        const bool s = occ_decode_step<false>(x, one[k], true, w, lane);
         const unsigned long long word = __ballot(s);
         cnt += __popcll(word);
         if (lane == 0) occ_words[((size_t)b0 + bl) * OCC_WPB + t0 + k] = word;
@@ -198,40 +156,8 @@ __global__ __launch_bounds__(64) void occ_rans_decode_kernel(const float* __rest
     }
     if (lane == 0) counts[b0 + bl] = cnt;
   }
-  int st = 0;
-  if (__ballot(damaged) != 0ull) st |= NVF_OCC_RANS_PAST_END;
-  if (__ballot(x != OCC_RANS_L) != 0ull) st |= NVF_OCC_RANS_BAD_STATE;
-  if (pos < (long long)nwords[g]) st |= NVF_OCC_RANS_WORDS_LEFT;
+  const int st = occ_window_status(w, x, (long long)nwords[g]);
   if (lane == 0) status[g] = st;
-}
-
-// one wave per block, four blocks per workgroup; the block's 512 words 64 at a time, one per lane
-__global__ __launch_bounds__(256) void points_from_bits32_kernel(const unsigned long long* __restrict__ words,
-                                                                 const int32_t* __restrict__ offsets,
-                                                                 const int32_t* __restrict__ origins,
-                                                                 int32_t* __restrict__ points, int batch, int n) {
-  const int lane = threadIdx.x & 63;
-  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (b >= batch) return;
-  const int oz = origins ? origins[3 * b] : 0, oy = origins ? origins[3 * b + 1] : 0, ox = origins ? origins[3 * b + 2] : 0;
-  int run = offsets[b];
-  for (int w0 = 0; w0 < OCC_WPB; w0 += 64) {
-    const unsigned long long mine = words[(size_t)b * OCC_WPB + w0 + lane];
-    if (__ballot(mine != 0ull) == 0ull) continue;     // wave-uniform
-    for (int wi = 0; wi < 64; ++wi) {
-      const unsigned long long word = __shfl(mine, wi, 64);
-      if (word == 0ull) continue;                      // wave-uniform
-      const int slot = run + __popcll(word & ((1ull << lane) - 1ull));
-      if (((word >> lane) & 1ull) && slot >= 0 && slot < n) {
-        const int v = 64 * (w0 + wi) + lane;
-        int32_t* o = points + (size_t)slot * 3;
-        o[0] = oz + (v >> 10);
-        o[1] = oy + ((v >> 5) & 31);
-        o[2] = ox + (v & 31);
-      }
-      run += __popcll(word);
-    }
-  }
 }
 
 }  // namespace
@@ -267,15 +193,6 @@ extern "C" int nvf_occ_rans_decode(const float* p, const int32_t* f1, const uint
   occ_rans_decode_kernel<<<groups, 64, 0, nvf_stream(stream)>>>(
       p, f1, (const unsigned long long*)states, words, (const long long*)word_off, nwords, (long long)total_words, batch,
       group, (unsigned long long*)occ_words, counts, status);
-  NVF_LAUNCH_CHECK();
-  return NVF_OK;
-}
-
-extern "C" int nvf_points_from_bits32(const uint64_t* words, const int32_t* offsets, const int32_t* origins,
-                                      int32_t* points, int n, int batch, void* stream) {
-  if (!words || !offsets || !points || n < 0 || batch <= 0) return NVF_EINVAL;
-  points_from_bits32_kernel<<<(batch + 3) / 4, 256, 0, nvf_stream(stream)>>>((const unsigned long long*)words, offsets,
-                                                                             origins, points, batch, n);
   NVF_LAUNCH_CHECK();
   return NVF_OK;
 }

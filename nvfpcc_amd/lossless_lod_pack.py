@@ -38,47 +38,40 @@ used.  Layout, little-endian:
     then            uint32 word count of each of the ceil(N / G) groups
     then per group  64 uint64 states, then its uint32 words in the order the decoder reads them
 
-The host half of this module needs no device; encode_occupancy / decode_occupancy run the forward and the kernels.
+The framing, the span loops, the table rule and points_from_words are lossless_pack's; this module holds the table
+section (bitmap + present frequencies) and the coder calls.  The host half needs no device; encode_occupancy /
+decode_occupancy run the forward and the kernels.
 """
-import struct
-
 import numpy as np
 import torch
 
-from .lossless_pack import MAX_GROUP, SPAN_GROUPS, _forward, _span, check_status as _check_status, ideal_bits, n_groups
+from . import lossless_pack as _lp
+from .lossless_pack import SPAN_GROUPS, ideal_bits, points_from_words  # noqa: F401  (points_from_words: this pack's too)
 
 VERSION = 1
 CONTEXTS = 3072
 GROUP = 64
 BLOCK_WORDS = 512 + 4096 + 32768
-_HEADER = struct.Struct("<BHIH")
 _BITMAP = CONTEXTS // 8
 _NAME = "lossless_lod_pack"
+_KIND = _lp.Kind(_NAME, VERSION, CONTEXTS, BLOCK_WORDS)
 
 
 def table_from_counts(cnt, occ):
     """Per context the coded symbols and the occupied ones -> (f1 as a list of Python integers, used as a list of
-    bools): clamp((2 * 65536 * occ + cnt) // (2 * cnt), 1, 65535), and 32768, unused, for a context without symbols."""
-    cnt, occ = [int(v) for v in cnt], [int(v) for v in occ]
-    if len(cnt) != CONTEXTS or len(occ) != CONTEXTS or any(o < 0 or o > c for c, o in zip(cnt, occ)):
-        raise ValueError(f"{_NAME}: the counts are {CONTEXTS} pairs with 0 <= occupied <= symbols")
-    f1 = [32768 if c == 0 else min(max((2 * 65536 * o + c) // (2 * c), 1), 65535) for c, o in zip(cnt, occ)]
-    return f1, [c > 0 for c in cnt]
+    bools): lossless_pack's rule (table_rule); a context without symbols is 32768 and unused."""
+    return _lp.table_rule(_KIND, "symbols", cnt, occ)
 
 
 def size(n_blocks, group, n_words, n_used):
     """Bytes of a pack of n_blocks blocks in groups of `group`, n_words words in all, n_used contexts present."""
-    return _HEADER.size + _BITMAP + 2 * int(n_used) + n_groups(n_blocks, group) * (4 + 64 * 8) + 4 * int(n_words)
+    return _lp.frame_size(_BITMAP + 2 * int(n_used), n_blocks, group, n_words)
 
 
 def write(group, n_blocks, f1, used, states, words):
     """f1: the frequencies of the contexts present, ascending (or all 3072, of which those are taken); used: bool
     [3072]; states: uint64 [groups, 64] (or int64 holding them); words: one uint32 array per group -> bytes."""
-    group, n_blocks = int(group), int(n_blocks)
-    if not 1 <= group <= MAX_GROUP:
-        raise ValueError(f"{_NAME}: group {group} outside [1, {MAX_GROUP}]")
-    if not 1 <= n_blocks < 1 << 32:
-        raise ValueError(f"{_NAME}: block count {n_blocks}")
+    group, n_blocks = _lp.frame_counts(_KIND, group, n_blocks)
     used = np.asarray(used).reshape(-1)
     if used.shape != (CONTEXTS,):
         raise ValueError(f"{_NAME}: the bitmap has {CONTEXTS} contexts")
@@ -90,20 +83,25 @@ def write(group, n_blocks, f1, used, states, words):
         raise ValueError(f"{_NAME}: the bitmap names {int(used.sum())} contexts, {f1.size} frequencies given")
     if f1.size and (f1.min() < 1 or f1.max() > 65535):
         raise ValueError(f"{_NAME}: the table's frequencies are in [1, 65535]")
-    ng = n_groups(n_blocks, group)
-    states = np.ascontiguousarray(states).view(np.uint64) if np.asarray(states).dtype == np.int64 else np.asarray(states, np.uint64)
-    if states.shape != (ng, 64) or len(words) != ng:
-        raise ValueError(f"{_NAME}: {n_blocks} blocks in groups of {group} are {ng} groups of 64 states")
-    words = [np.ascontiguousarray(w).view(np.uint32) if np.asarray(w).dtype == np.int32 else np.asarray(w, np.uint32)
-             for w in words]
-    for g, w in enumerate(words):
-        if w.ndim != 1 or w.size > min(group, n_blocks - g * group) * BLOCK_WORDS:
-            raise ValueError(f"{_NAME}: group {g} holds more words than it has symbols")
-    parts = [_HEADER.pack(VERSION, group, n_blocks, CONTEXTS), np.packbits(used, bitorder="little").tobytes(),
-             f1.astype("<u2").tobytes(), np.asarray([w.size for w in words], "<u4").tobytes()]
-    for g in range(ng):
-        parts += [states[g].astype("<u8").tobytes(), words[g].astype("<u4").tobytes()]
-    return b"".join(parts)
+    table = np.packbits(used, bitorder="little").tobytes() + f1.astype("<u2").tobytes()
+    return _lp.frame_write(_KIND, group, n_blocks, table, states, words)
+
+
+def _read_table(data, at, tail):
+    if len(data) < at + _BITMAP:
+        raise ValueError(f"{_NAME}: truncated bitmap")
+    used = np.unpackbits(np.frombuffer(data, np.uint8, _BITMAP, at), bitorder="little").astype(bool)
+    at += _BITMAP
+    n_used = int(used.sum())
+    if len(data) < at + 2 * n_used + tail:
+        raise ValueError(f"{_NAME}: the bitmap names {n_used} contexts and {tail // 4} word counts follow them, "
+                         f"{len(data) - at} bytes are left")
+    present = np.frombuffer(data, "<u2", n_used, at).astype(np.int64)
+    if n_used and present.min() < 1:
+        raise ValueError(f"{_NAME}: a frequency of 0 in the table")
+    f1 = np.full(CONTEXTS, 32768, np.int64)
+    f1[used] = present
+    return at + 2 * n_used, {"f1": f1, "used": used}, f", {n_used} contexts"
 
 
 def read(data, n_blocks=None):
@@ -112,55 +110,7 @@ def read(data, n_blocks=None):
     naming the fault, on a wrong version, a truncated header, a group size or context count out of range, a bitmap
     that names more frequencies than follow, a frequency of 0, a word count no group can have, a block count other than
     `n_blocks`, and a payload that is shorter or longer than its counts say."""
-    data = bytes(data)
-    if len(data) < 1:
-        raise ValueError(f"{_NAME}: empty")
-    if data[0] != VERSION:
-        raise ValueError(f"{_NAME}: version {data[0]}, this reader knows {VERSION}")
-    if len(data) < _HEADER.size:
-        raise ValueError(f"{_NAME}: truncated header")
-    _, group, nb, nctx = _HEADER.unpack_from(data)
-    if not 1 <= group <= MAX_GROUP:
-        raise ValueError(f"{_NAME}: group size {group} outside [1, {MAX_GROUP}]")
-    if nb < 1:
-        raise ValueError(f"{_NAME}: no blocks")
-    if n_blocks is not None and nb != int(n_blocks):
-        raise ValueError(f"{_NAME}: codes {nb} blocks, the pack holds {int(n_blocks)}")
-    if nctx != CONTEXTS:
-        raise ValueError(f"{_NAME}: {nctx} contexts, this reader knows {CONTEXTS}")
-    ng = n_groups(nb, group)
-    at = _HEADER.size
-    if len(data) < at + _BITMAP:
-        raise ValueError(f"{_NAME}: truncated bitmap")
-    used = np.unpackbits(np.frombuffer(data, np.uint8, _BITMAP, at), bitorder="little").astype(bool)
-    at += _BITMAP
-    n_used = int(used.sum())
-    if len(data) < at + 2 * n_used + 4 * ng:
-        raise ValueError(f"{_NAME}: the bitmap names {n_used} contexts and {ng} word counts follow them, "
-                         f"{len(data) - at} bytes are left")
-    present = np.frombuffer(data, "<u2", n_used, at).astype(np.int64)
-    at += 2 * n_used
-    if n_used and present.min() < 1:
-        raise ValueError(f"{_NAME}: a frequency of 0 in the table")
-    f1 = np.full(CONTEXTS, 32768, np.int64)
-    f1[used] = present
-    nwords = np.frombuffer(data, "<u4", ng, at).astype(np.int64)
-    at += 4 * ng
-    for g in range(ng):
-        if nwords[g] > min(group, nb - g * group) * BLOCK_WORDS:
-            raise ValueError(f"{_NAME}: group {g} claims {int(nwords[g])} words, more than it has symbols")
-    need = size(nb, group, int(nwords.sum()), n_used)
-    if len(data) != need:
-        raise ValueError(f"{_NAME}: {len(data)} bytes, {need} expected for {nb} blocks, {n_used} contexts and "
-                         f"{int(nwords.sum())} words")
-    states, words = np.empty((ng, 64), np.uint64), []
-    for g in range(ng):
-        states[g] = np.frombuffer(data, "<u8", 64, at)
-        at += 512
-        words.append(np.frombuffer(data, "<u4", int(nwords[g]), at).astype(np.uint32))
-        at += 4 * int(nwords[g])
-    return {"group": group, "n_blocks": nb, "f1": f1, "used": used, "nwords": nwords, "states": states,
-            "words": np.concatenate(words) if words else np.zeros(0, np.uint32)}
+    return _lp.frame_read(_KIND, _read_table, data, n_blocks)
 
 
 def lossless_lod_line(n_bytes, n_points, ideal, n_used, n_symbols, group):
@@ -171,10 +121,7 @@ def lossless_lod_line(n_bytes, n_points, ideal, n_used, n_symbols, group):
 
 def check_status(status):
     """ValueError naming the first group whose decoder status is not 0."""
-    try:
-        _check_status(status)
-    except ValueError as e:
-        raise ValueError(str(e).replace("lossless_pack:", _NAME + ":", 1)) from None
+    _lp.check_status(status, _NAME)
 
 
 # ---------------------------------------------------------------- device half
@@ -187,16 +134,10 @@ def encode_occupancy(net, latents, gt, batch=64, group=GROUP, span_groups=SPAN_G
     `span_groups` whole groups per launch (lossless_pack._span): memory follows the batch and the span, not the cloud.
     ValueError when a probability is NaN or outside [0, 1]."""
     from . import ops
-    N, batch, group = latents.shape[0], max(int(batch), 1), int(group)
-    if not 1 <= group <= MAX_GROUP:
-        raise ValueError(f"{_NAME}: group {group} outside [1, {MAX_GROUP}]")
-    if gt.shape[0] != N:
-        raise ValueError(f"{_NAME}: {N} latents and {gt.shape[0]} blocks of ground truth")
-    span = _span(batch, group, span_groups)
+    N, batch, group, span = _lp.span_args(_KIND, latents, gt, batch, group, span_groups)
     cnt = occ = bad = None
-    for lo in range(0, N, span):
-        hi = min(lo + span, N)
-        pyr = ops.occ_hier_pyramid(_forward(net, latents, lo, hi, batch), gt[lo:hi].contiguous(), bad)
+    for p, g in _lp.spans(net, latents, gt, batch, span):
+        pyr = ops.occ_hier_pyramid(p, g, bad)
         bad = pyr["bad"]
         cnt, occ = ops.occ_hier_hist(pyr, cnt, occ)
     if int(bad.item()):
@@ -204,15 +145,12 @@ def encode_occupancy(net, latents, gt, batch=64, group=GROUP, span_groups=SPAN_G
     cnt, occ = (t.cpu().numpy().view(np.uint64) for t in (cnt, occ))
     f1, used = table_from_counts(cnt, occ)
     f1_dev = torch.tensor(f1, dtype=torch.int32, device=latents.device)
-    states, words, gt_words = [], [], []
-    for lo in range(0, N, span):
-        hi = min(lo + span, N)
-        pyr = ops.occ_hier_pyramid(_forward(net, latents, lo, hi, batch), gt[lo:hi].contiguous())
-        s, w = ops.occ_hier_encode(pyr, f1_dev, group)
-        states.append(s.cpu().numpy())
-        words += [x.cpu().numpy() for x in w]
-        gt_words.append(pyr["gt_words"])
-    pack = write(group, N, f1, used, np.concatenate(states, 0), words)
+
+    def code(p, g):
+        pyr = ops.occ_hier_pyramid(p, g)
+        return (*ops.occ_hier_encode(pyr, f1_dev, group), pyr["gt_words"])
+    states, words, gt_words = _lp.encode_spans(net, latents, gt, batch, span, code)
+    pack = write(group, N, f1, used, states, words)
     return pack, {"ideal_bits": ideal_bits(f1, cnt, occ), "f1": f1, "used": used, "cnt": cnt, "occ": occ,
                   "contexts": int(sum(used)), "symbols": int(sum(int(c) for c in cnt)),
                   "gt_words": tuple(torch.cat([g[lv] for g in gt_words], 0) for lv in range(3))}
@@ -229,41 +167,5 @@ def decode_occupancy(net, latents, data, level=0, batch=64, span_groups=SPAN_GRO
     from . import ops
     if level not in (0, 1, 2):
         raise ValueError(f"{_NAME}: level {level!r}, the stream holds levels 0, 1 and 2")
-    side = read(data, latents.shape[0])
-    N, group, dev = side["n_blocks"], side["group"], latents.device
-    span = _span(max(int(batch), 1), group, span_groups)
-    f1_dev = torch.from_numpy(side["f1"].astype(np.int32)).to(dev)
-    states = torch.from_numpy(side["states"].view(np.int64)).to(dev)
-    words = torch.from_numpy(side["words"].view(np.int32)).to(dev)
-    nwords = torch.from_numpy(side["nwords"].astype(np.int32)).to(dev)
-    off = np.concatenate([[0], np.cumsum(side["nwords"])])
-    out_w, out_c, out_s = [], [], []
-    for lo in range(0, N, span):
-        hi = min(lo + span, N)
-        g0, g1 = lo // group, n_groups(hi, group)
-        pyr = ops.occ_hier_pyramid(_forward(net, latents, lo, hi, batch))
-        w, c, s, _ = ops.occ_hier_decode(pyr, f1_dev, states[g0:g1].contiguous(), words[int(off[g0]):int(off[g1])].contiguous(),
-                                         nwords[g0:g1].contiguous(), group, level)
-        out_w.append(w)
-        out_c.append(c)
-        out_s.append(s)
-    check_status(torch.cat(out_s).cpu().numpy())
-    return torch.cat(out_w, 0), torch.cat(out_c, 0)
-
-
-@torch.no_grad()
-def points_from_words(words, counts, origins, level=0, batch=64):
-    """Occupancy words of a level + counts -> int64 [n, 3] points (origin >> level) + (z, y, x) in (block, raster) order
-    (numpy): the lattice of decode --lod."""
-    from . import ops
-    from .lossless_pack import points_from_words as points32
-    if level == 0:
-        return points32(words, counts, origins, batch)
-    dev = words.device
-    origins = torch.as_tensor(np.asarray(origins)).to(torch.int32)
-    pts = []
-    for lo in range(0, words.shape[0], batch):
-        hi = min(lo + batch, words.shape[0])
-        pts.append(ops.points_from_bits(words[lo:hi].contiguous(), counts[lo:hi].contiguous(),
-                                        origins[lo:hi].to(dev).contiguous(), 32 >> level, level).cpu())
-    return torch.cat(pts, 0).long().numpy()
+    return _lp.decode_spans(_KIND, net, latents, read(data, latents.shape[0]), batch, span_groups,
+                            lambda p, *stream: ops.occ_hier_decode(ops.occ_hier_pyramid(p), *stream, level)[:3])

@@ -1305,8 +1305,8 @@ def head_occ_bits(x, w_fwd, bias, thh):
 
 
 def points_from_bits(words, counts, origins, d, shift):
-    """Occupancy words [B, d^3/64] + counts int32 [B] -> int32 [n,3] points (origin >> shift) + (z,y,x) in (b,z,y,x)
-    raster order.  origins int32 [B,3] or None."""
+    """Occupancy words [B, d^3/64] (d = 8, 16 or 32) + counts int32 [B] -> int32 [n,3] points (origin >> shift) +
+    (z,y,x) in (b,z,y,x) raster order.  origins int32 [B,3] or None."""
     _chk(words, counts, origins)
     B = words.shape[0]
     if words.dtype != torch.int64 or words.shape != (B, d ** 3 // 64) or counts.dtype != torch.int32 or counts.shape != (B,):
@@ -1425,26 +1425,56 @@ def occ_ctx_hist(p, gt, cnt=None, occ=None, bad=None):
     return cnt, occ, bad
 
 
+def _occ_groups(B, group):
+    """(G, groups) of B blocks in groups of `group`."""
+    G = int(group)
+    if not 1 <= G <= OCC_RANS_MAX_GROUP:
+        raise RuntimeError(f"group must be in [1, {OCC_RANS_MAX_GROUP}], got {group!r}")
+    return G, (B + G - 1) // G
+
+
+def _occ_coded(B, G, ng, block_words, dev, launch):
+    """What an encoder leaves: launch(states, region, nwords) fills states int64 [groups, 64], every group's worst-case
+    region of G * block_words words from the end of the region of its own blocks, and nwords -> (states, the groups'
+    words cut out of their regions: one int32 tensor per group)."""
+    states = torch.empty((ng, 64), dtype=torch.int64, device=dev)
+    region = torch.empty((ng, G * block_words), dtype=torch.int32, device=dev)
+    nwords = torch.empty(ng, dtype=torch.int32, device=dev)
+    launch(states, region, nwords)
+    words = []
+    for g, n in enumerate(nwords.tolist()):
+        end = min(G, B - g * G) * block_words
+        words.append(region[g, end - n:end].clone())
+    return states, words
+
+
+def _occ_stream(name, B, G, ng, states, words, nwords):
+    """What a decoder reads, checked -> (words, or a pointer to pass when there are none; word_off int64 [groups];
+    total_words, which keeps the kernels inside `words`)."""
+    _chk(states, words, nwords)
+    if states.dtype != torch.int64 or states.shape != (ng, 64) or words.dtype != torch.int32 or words.dim() != 1 or \
+            nwords.dtype != torch.int32 or nwords.shape != (ng,):
+        raise RuntimeError(f"{name}: {B} blocks in groups of {G} take states int64 [{ng}, 64], words int32 [n] "
+                           f"and nwords int32 [{ng}]")
+    n64 = nwords.to(torch.int64) & 0xFFFFFFFF
+    word_off = (torch.cumsum(n64, 0) - n64).contiguous()
+    total = words.numel()
+    if total == 0:
+        words = torch.zeros(1, dtype=torch.int32, device=words.device)
+    return words, word_off, total
+
+
 def occ_rans_encode(p, gt, f1, group):
     """The occupancy gt of B blocks coded under p and the table f1 (int32 [256]) in groups of `group` blocks ->
     (states int64 [groups, 64] holding the uint64 final states, words: a list with one int32 tensor (uint32 words, in
     the decoder's reading order) per group, gt_words int64 [B, 512] the occupancy words of gt)."""
     B = _occ_blocks(p, gt)
     _occ_table(f1, p.device)
-    G = int(group)
-    if not 1 <= G <= OCC_RANS_MAX_GROUP:
-        raise RuntimeError(f"group must be in [1, {OCC_RANS_MAX_GROUP}], got {group!r}")
-    ng = (B + G - 1) // G
-    states = torch.empty((ng, 64), dtype=torch.int64, device=p.device)
-    region = torch.empty((ng, G * 32768), dtype=torch.int32, device=p.device)
-    nwords = torch.empty(ng, dtype=torch.int32, device=p.device)
+    G, ng = _occ_groups(B, group)
     gt_words = torch.empty((B, 512), dtype=torch.int64, device=p.device)
-    check(lib().nvf_occ_rans_encode(_ptr(p), _ptr(gt), _ptr(f1), B, G, _ptr(states), _ptr(region), _ptr(nwords),
-                                    _ptr(gt_words), _stream()), "nvf_occ_rans_encode")
-    words = []
-    for g, n in enumerate(nwords.tolist()):
-        end = min(G, B - g * G) * 32768
-        words.append(region[g, end - n:end].clone())
+    states, words = _occ_coded(B, G, ng, 32768, p.device, lambda states, region, nwords: check(
+        lib().nvf_occ_rans_encode(_ptr(p), _ptr(gt), _ptr(f1), B, G, _ptr(states), _ptr(region), _ptr(nwords),
+                                  _ptr(gt_words), _stream()), "nvf_occ_rans_encode"))
     return states, words, gt_words
 
 
@@ -1455,45 +1485,14 @@ def occ_rans_decode(p, f1, states, words, nwords, group):
     `words`; what it decodes then is garbage and the status says so."""
     B = _occ_blocks(p)
     _occ_table(f1, p.device)
-    G = int(group)
-    if not 1 <= G <= OCC_RANS_MAX_GROUP:
-        raise RuntimeError(f"group must be in [1, {OCC_RANS_MAX_GROUP}], got {group!r}")
-    ng = (B + G - 1) // G
-    _chk(states, words, nwords)
-    if states.dtype != torch.int64 or states.shape != (ng, 64) or words.dtype != torch.int32 or words.dim() != 1 or \
-            nwords.dtype != torch.int32 or nwords.shape != (ng,):
-        raise RuntimeError(f"occ_rans_decode: {B} blocks in groups of {G} take states int64 [{ng}, 64], words int32 [n] "
-                           f"and nwords int32 [{ng}]")
-    n64 = nwords.to(torch.int64) & 0xFFFFFFFF
-    word_off = (torch.cumsum(n64, 0) - n64).contiguous()
-    if words.numel() == 0:                      # a pointer to pass; total_words = 0 keeps the kernel away from it
-        words = torch.zeros(1, dtype=torch.int32, device=p.device)
-        total = 0
-    else:
-        total = words.numel()
+    G, ng = _occ_groups(B, group)
+    words, word_off, total = _occ_stream("occ_rans_decode", B, G, ng, states, words, nwords)
     occ_words = torch.empty((B, 512), dtype=torch.int64, device=p.device)
     counts = torch.empty(B, dtype=torch.int32, device=p.device)
     status = torch.empty(ng, dtype=torch.int32, device=p.device)
     check(lib().nvf_occ_rans_decode(_ptr(p), _ptr(f1), _ptr(states), _ptr(words), _ptr(word_off), _ptr(nwords), total, B,
                                     G, _ptr(occ_words), _ptr(counts), _ptr(status), _stream()), "nvf_occ_rans_decode")
     return occ_words, counts, status
-
-
-def points_from_bits32(words, counts, origins):
-    """points_from_bits for the 32^3 grid: occupancy words int64 [B, 512] + counts int32 [B] -> int32 [n, 3] points
-    origin + (z, y, x) in (b, z, y, x) raster order.  origins int32 [B, 3] or None."""
-    _chk(words, counts, origins)
-    B = words.shape[0]
-    if words.dtype != torch.int64 or words.shape != (B, 512) or counts.dtype != torch.int32 or counts.shape != (B,):
-        raise RuntimeError("points_from_bits32: words must be int64 [B, 512] and counts int32 [B]")
-    if origins is not None and (origins.dtype != torch.int32 or origins.shape != (B, 3)):
-        raise RuntimeError("points_from_bits32: origins must be int32 [B, 3]")
-    offsets = (torch.cumsum(counts, 0, dtype=torch.int32) - counts).contiguous()
-    total = int(counts.sum().item())
-    points = torch.empty((max(total, 1), 3), dtype=torch.int32, device=words.device)
-    check(lib().nvf_points_from_bits32(_ptr(words), _ptr(offsets), _ptr(origins), _ptr(points), total, B, _stream()),
-          "nvf_points_from_bits32")
-    return points[:total]
 
 
 # ---------------------------------------------------------------- scalable lossless geometry (csrc/occ_hier.hip)
@@ -1512,7 +1511,7 @@ def occ_hier_cells(words, fill=True):
         raise RuntimeError("occ_hier_cells: words must be int64 [B, 8 | 64 | 512]")
     wpb = words.shape[1]
     if fill and wpb == 512:
-        raise RuntimeError("occ_hier_cells: the 32^3 level has no cell list (points_from_bits32 gives its points)")
+        raise RuntimeError("occ_hier_cells: the 32^3 level has no cell list (points_from_bits gives its points)")
     counts = torch.empty(B, dtype=torch.int32, device=words.device)
     cells = torch.empty(B * wpb * 64, dtype=torch.int32, device=words.device) if fill else None
     check(lib().nvf_occ_hier_cells(_ptr(words), B, wpb, _ptr(counts), _ptr(cells), _stream()), "nvf_occ_hier_cells")
@@ -1582,24 +1581,14 @@ def occ_hier_encode(pyr, f1, group):
     decoder's reading order)."""
     B, dev = pyr["p"].shape[0], pyr["p"].device
     _occ_hier_table(f1, dev)
-    G = int(group)
-    if not 1 <= G <= OCC_RANS_MAX_GROUP:
-        raise RuntimeError(f"group must be in [1, {OCC_RANS_MAX_GROUP}], got {group!r}")
-    ng = (B + G - 1) // G
-    states = torch.empty((ng, 64), dtype=torch.int64, device=dev)
-    region = torch.empty((ng, G * OCC_HIER_BLOCK_WORDS), dtype=torch.int32, device=dev)
-    nwords = torch.empty(ng, dtype=torch.int32, device=dev)
+    G, ng = _occ_groups(B, group)
     w0, w1, w2 = pyr["gt_words"]
     cells2, counts2, cells1, counts1 = pyr["lists"]
-    check(lib().nvf_occ_hier_encode(_ptr(pyr["p"]), _ptr(pyr["p1"]), _ptr(pyr["k1"]), _ptr(pyr["p2"]), _ptr(pyr["k2"]),
-                                    _ptr(w0), _ptr(w1), _ptr(w2), _ptr(cells2), _ptr(counts2), _ptr(cells1), _ptr(counts1),
-                                    _ptr(f1), B, G, _ptr(states), _ptr(region), _ptr(nwords), _stream()),
-          "nvf_occ_hier_encode")
-    words = []
-    for g, n in enumerate(nwords.tolist()):
-        end = min(G, B - g * G) * OCC_HIER_BLOCK_WORDS
-        words.append(region[g, end - n:end].clone())
-    return states, words
+    return _occ_coded(B, G, ng, OCC_HIER_BLOCK_WORDS, dev, lambda states, region, nwords: check(
+        lib().nvf_occ_hier_encode(_ptr(pyr["p"]), _ptr(pyr["p1"]), _ptr(pyr["k1"]), _ptr(pyr["p2"]), _ptr(pyr["k2"]),
+                                  _ptr(w0), _ptr(w1), _ptr(w2), _ptr(cells2), _ptr(counts2), _ptr(cells1), _ptr(counts1),
+                                  _ptr(f1), B, G, _ptr(states), _ptr(region), _ptr(nwords), _stream()),
+        "nvf_occ_hier_encode"))
 
 
 def occ_hier_decode(pyr, f1, states, words, nwords, group, level=0):
@@ -1610,22 +1599,10 @@ def occ_hier_decode(pyr, f1, states, words, nwords, group, level=0):
     damaged stream cannot make a kernel read outside `words` or write outside its outputs."""
     B, dev = pyr["p"].shape[0], pyr["p"].device
     _occ_hier_table(f1, dev)
-    G = int(group)
-    if not 1 <= G <= OCC_RANS_MAX_GROUP:
-        raise RuntimeError(f"group must be in [1, {OCC_RANS_MAX_GROUP}], got {group!r}")
+    G, ng = _occ_groups(B, group)
     if level not in (0, 1, 2):
         raise RuntimeError(f"level must be 0, 1 or 2, got {level!r}")
-    ng = (B + G - 1) // G
-    _chk(states, words, nwords)
-    if states.dtype != torch.int64 or states.shape != (ng, 64) or words.dtype != torch.int32 or words.dim() != 1 or \
-            nwords.dtype != torch.int32 or nwords.shape != (ng,):
-        raise RuntimeError(f"occ_hier_decode: {B} blocks in groups of {G} take states int64 [{ng}, 64], words int32 [n] "
-                           f"and nwords int32 [{ng}]")
-    n64 = nwords.to(torch.int64) & 0xFFFFFFFF
-    word_off = (torch.cumsum(n64, 0) - n64).contiguous()
-    total = words.numel()
-    if total == 0:                              # a pointer to pass; total_words = 0 keeps the kernels away from it
-        words = torch.zeros(1, dtype=torch.int32, device=dev)
+    words, word_off, total = _occ_stream("occ_hier_decode", B, G, ng, states, words, nwords)
     x = states.clone()
     pos = torch.zeros(ng, dtype=torch.int64, device=dev)
     status = torch.zeros(ng, dtype=torch.int32, device=dev)

@@ -1,8 +1,8 @@
 """numpy reference of the scalable lossless occupancy coder (include/nvf_hip.h "scalable lossless geometry",
-csrc/occ_hier.hip): the pyramid, the contexts, the three sections of a group, the table and the 64-lane interleaved
-binary rANS coder with idle lanes.  Everything past the float comparisons of the pyramid is integer arithmetic on
-uint64, so the device must reproduce it byte for byte.  The context function, the input error rule and the table rule
-are v1's (tests/occ_rans_ref.py)."""
+csrc/occ_hier.hip): the pyramid, the contexts, the three sections of a group and the table.  The coder is v1's
+(tests/occ_rans_ref.py: encode_steps / decode_steps, here with idle slots), and so are the context function, the input
+error rule and the table rule.  Everything past the float comparisons of the pyramid is integer arithmetic on uint64,
+so the device must reproduce it byte for byte."""
 import numpy as np
 
 from tests import occ_rans_ref as R
@@ -12,7 +12,6 @@ LANES = 64
 CONTEXTS = 3072
 BLOCK_WORDS = 512 + 4096 + 32768
 L = np.uint64(1 << 31)
-_U = np.uint64
 DIM = {0: 32, 1: 16, 2: 8}
 
 
@@ -103,31 +102,17 @@ def table(cnt, occ):
 ideal_bits = R.ideal_bits
 
 
-def _padded(a, fill):
-    n = -(-a.size // LANES) * LANES
-    return np.concatenate([a, np.full(n - a.size, fill, a.dtype)]).reshape(-1, LANES)
-
-
 def encode_group(p, gt, f1):
     """p float32 [nb, 32768], gt [nb, 32768] (one group), f1 int [3072] -> (states uint64 [64], words uint32 [m] in
     the decoder's reading order)."""
     f1 = np.asarray(f1, np.int64)
     x = np.full(LANES, L, np.uint64)
-    out = []                                    # backwards: the last word written is the first one read
+    out = []
     for level, _, _, ctx, sym in reversed(group_sections(p, gt)):
         one = f1[ctx]
-        freq = _padded(np.where(sym, one, 65536 - one).astype(np.uint64), 0)      # 0: an idle slot
-        start = _padded(np.where(sym, 0, one).astype(np.uint64), 0)
-        for t in range(freq.shape[0] - 1, -1, -1):
-            live = freq[t] != 0
-            f = np.where(live, freq[t], _U(1))
-            emit = live & (x >= (f << _U(47)))
-            if emit.any():
-                out.append((x[emit] & _U(0xFFFFFFFF)).astype(np.uint32)[::-1])    # highest lane first
-                x = np.where(emit, x >> _U(32), x)
-            x = np.where(live, (x // f) * _U(65536) + x % f + start[t], x)
-    words = np.concatenate(out)[::-1] if out else np.zeros(0, np.uint32)
-    return x.copy(), np.ascontiguousarray(words)
+        x = R.encode_steps(x, out, R.padded(np.where(sym, one, 65536 - one).astype(np.uint64)),
+                           R.padded(np.where(sym, 0, one).astype(np.uint64)))
+    return x.copy(), R.stream_words(out)
 
 
 def decode_group(p, f1, states, words, stop=0):
@@ -143,23 +128,7 @@ def decode_group(p, f1, states, words, stop=0):
         if level < stop:
             break
         blk, cell, ctx = section(level, p, pyr, occ)
-        one = _padded(f1[ctx].astype(np.uint64), 0)
-        sym = np.zeros(one.shape, bool)
-        for t in range(one.shape[0]):
-            o = one[t]
-            live = o != 0
-            slot = x & _U(0xFFFF)
-            s = live & (slot < o)
-            f = np.where(s, o, _U(65536) - o)
-            x = np.where(live, f * (x >> _U(16)) + slot - np.where(s, _U(0), o), x)
-            need = live & (x < L)
-            k = int(need.sum())
-            if k:
-                if pos + k > words.size:
-                    raise IndexError("read past the end of the words")
-                x[need] = (x[need] << _U(32)) | words[pos:pos + k].astype(np.uint64)
-                pos += k
-            sym[t] = s
+        sym, x, pos = R.decode_steps(x, words, pos, R.padded(f1[ctx].astype(np.uint64)))
         occ = np.zeros((p.shape[0], DIM[level] ** 3), bool)
         occ[blk, cell] = sym.reshape(-1)[:blk.size]
     return occ, x, pos

@@ -48,43 +48,44 @@ def ideal_bits(f1, cnt, occ):
     return float(np.sum(-occ * np.log2(f1 / 65536.0) - (cnt - occ) * np.log2(1.0 - f1 / 65536.0)))
 
 
-def encode_group(p, gt, f1):
-    """p float32 [n], gt bool [n] (n = blocks * 32768, one group), f1 int [256] -> (states uint64 [64], words uint32
-    [m] in the decoder's reading order)."""
-    f1 = np.asarray(f1, np.int64)
-    one = f1[contexts(p)].reshape(-1, LANES)
-    s = np.asarray(gt).astype(bool).reshape(-1, LANES)
-    freq = np.where(s, one, 65536 - one).astype(np.uint64)
-    start = np.where(s, 0, one).astype(np.uint64)
-    x = np.full(LANES, L, np.uint64)
-    out = []                                    # backwards: the last word written is the first one read
-    for t in range(one.shape[0] - 1, -1, -1):
-        f = freq[t]
-        emit = x >= (f << _U(47))
+def padded(a, fill=0):
+    """1-d array -> [steps, 64], the last step filled up with `fill` (0: idle slots)."""
+    n = -(-a.size // LANES) * LANES
+    return np.concatenate([a, np.full(n - a.size, fill, a.dtype)]).reshape(-1, LANES)
+
+
+def encode_steps(x, out, freq, start):
+    """THE encoder loop.  freq, start uint64 [steps, 64] (padded), walked backwards; freq 0 is an idle slot: the lane
+    neither emits nor changes its state.  x uint64 [64] -> the states after the steps; the words of every step are
+    appended to `out`, highest lane first: the last word written is the first one read (stream_words)."""
+    for t in range(freq.shape[0] - 1, -1, -1):
+        live = freq[t] != 0
+        f = np.where(live, freq[t], _U(1))
+        emit = live & (x >= (f << _U(47)))
         if emit.any():
-            out.append((x[emit] & _U(0xFFFFFFFF)).astype(np.uint32)[::-1])    # highest lane first
+            out.append((x[emit] & _U(0xFFFFFFFF)).astype(np.uint32)[::-1])
             x = np.where(emit, x >> _U(32), x)
-        x = (x // f) * _U(65536) + x % f + start[t]
-    words = np.concatenate(out)[::-1] if out else np.zeros(0, np.uint32)
-    return x.copy(), np.ascontiguousarray(words)
+        x = np.where(live, (x // f) * _U(65536) + x % f + start[t], x)
+    return x
 
 
-def decode_group(p, f1, states, words):
-    """-> (symbols bool [n], final states uint64 [64], words consumed).  IndexError on a read past the end."""
-    f1 = np.asarray(f1, np.int64)
-    one = f1[contexts(p)].reshape(-1, LANES).astype(np.uint64)
-    x = np.asarray(states, np.uint64).copy()
-    words = np.asarray(words, np.uint32)
+def stream_words(out):
+    """What encode_steps appended -> uint32 [m] in the decoder's reading order."""
+    return np.ascontiguousarray(np.concatenate(out)[::-1]) if out else np.zeros(0, np.uint32)
+
+
+def decode_steps(x, words, pos, one):
+    """THE decoder loop.  one uint64 [steps, 64] (padded): the frequency of a 1, 0 for an idle slot, which decodes 0 and
+    keeps its state.  -> (symbols bool [steps, 64], states, words consumed so far).  IndexError on a read past the end."""
     sym = np.zeros(one.shape, bool)
-    pos = 0
     for t in range(one.shape[0]):
         o = one[t]
+        live = o != 0
         slot = x & _U(0xFFFF)
-        s = slot < o
+        s = live & (slot < o)
         f = np.where(s, o, _U(65536) - o)
-        start = np.where(s, _U(0), o)
-        x = f * (x >> _U(16)) + slot - start
-        need = x < L
+        x = np.where(live, f * (x >> _U(16)) + slot - np.where(s, _U(0), o), x)
+        need = live & (x < L)
         k = int(need.sum())
         if k:
             if pos + k > words.size:
@@ -92,7 +93,25 @@ def decode_group(p, f1, states, words):
             x[need] = (x[need] << _U(32)) | words[pos:pos + k].astype(np.uint64)
             pos += k
         sym[t] = s
-    return sym.reshape(-1), x, pos
+    return sym, x, pos
+
+
+def encode_group(p, gt, f1):
+    """p float32 [n], gt bool [n] (n = blocks * 32768, one group), f1 int [256] -> (states uint64 [64], words uint32
+    [m] in the decoder's reading order).  No slot is idle: a frequency is never 0."""
+    one = np.asarray(f1, np.int64)[contexts(p)]
+    s = np.asarray(gt).astype(bool).reshape(-1)
+    out = []
+    x = encode_steps(np.full(LANES, L, np.uint64), out, padded(np.where(s, one, 65536 - one).astype(np.uint64)),
+                     padded(np.where(s, 0, one).astype(np.uint64)))
+    return x.copy(), stream_words(out)
+
+
+def decode_group(p, f1, states, words):
+    """-> (symbols bool [n], final states uint64 [64], words consumed).  IndexError on a read past the end."""
+    one = np.asarray(f1, np.int64)[contexts(p)].reshape(-1).astype(np.uint64)
+    sym, x, pos = decode_steps(np.asarray(states, np.uint64).copy(), np.asarray(words, np.uint32), 0, padded(one))
+    return sym.reshape(-1)[:one.size], x, pos
 
 
 def encode(p, gt, f1, group):

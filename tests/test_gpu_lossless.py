@@ -103,21 +103,26 @@ def test_table_with_the_extreme_frequencies(dev, cloud):
 
 
 def test_points_from_bits32_equals_nonzero_in_order(dev, cloud):
+    """points_from_bits at d = 32 walks a block's 512 words in chunks of 64: besides the cloud, one block whose only set
+    bits lie in words 64..511 (its first chunk is empty and skipped) and one whose bits straddle words 63 / 64."""
     from nvfpcc_amd import ops
-    _, gt, _ = cloud
-    g = torch.from_numpy(gt).reshape(5, 32, 32, 32).to(dev)
+    gt = np.concatenate([cloud[1], np.zeros((2, VOX), bool)])
+    gt[5, [64 * 64, 64 * 64 + 63, 64 * 200 + 17, 64 * 511, VOX - 1]] = True
+    gt[6, 64 * 63 + 60:64 * 64 + 5] = True
+    g = torch.from_numpy(gt).reshape(7, 32, 32, 32).to(dev)
     words = torch.from_numpy(R.occupancy_words(gt).view(np.int64)).to(dev)
-    counts = g.reshape(5, -1).sum(1).to(torch.int32)
-    origins = torch.tensor([[0, 0, 0], [32, 64, 96], [992, 0, 4064], [2048, 32, 32], [4064, 4064, 4064]],
-                           dtype=torch.int32, device=dev)
+    assert not words[5, :64].any() and words[6, 63] != 0 and words[6, 64] != 0
+    counts = g.reshape(7, -1).sum(1).to(torch.int32)
+    origins = torch.tensor([[0, 0, 0], [32, 64, 96], [992, 0, 4064], [2048, 32, 32], [4064, 4064, 4064], [64, 32, 0],
+                            [0, 96, 128]], dtype=torch.int32, device=dev)
     nz = torch.nonzero(g)
     want = nz[:, 1:].to(torch.int32) + origins[nz[:, 0]]
-    got = ops.points_from_bits32(words, counts, origins)
+    got = ops.points_from_bits(words, counts, origins, 32, 0)
     assert got.dtype == torch.int32 and torch.equal(got, want)
-    assert torch.equal(ops.points_from_bits32(words, counts, None), nz[:, 1:].to(torch.int32))
+    assert torch.equal(ops.points_from_bits(words, counts, None, 32, 0), nz[:, 1:].to(torch.int32))
     # a block without points in the middle, and a single block
     assert int(counts[1]) == 0 and int(counts[3]) == VOX
-    assert torch.equal(ops.points_from_bits32(words[2:3].contiguous(), counts[2:3].contiguous(), origins[2:3].contiguous()),
+    assert torch.equal(ops.points_from_bits(words[2:3].contiguous(), counts[2:3].contiguous(), origins[2:3].contiguous(), 32, 0),
                        want[int(counts[:2].sum()):int(counts[:3].sum())])
 
 
