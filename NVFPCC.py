@@ -20,9 +20,10 @@ engine (nvfpcc_amd/engine.py) instead of a DataLoader + autograd loop.
     python NVFPCC.py encode ... --lossless                                     # the true occupancy travels too (lossless_pack)
     python NVFPCC.py decode pack.pk --lossless ...                             # rc_dec.ply holds exactly the input's voxels
     python NVFPCC.py encode ... --lossless_lod                                 # the occupancy coarse to fine (lossless_lod_pack)
+    python NVFPCC.py encode ... --lossless_lod --lossless_ctx nbr              # the voxels under their parents' neighbours
     python NVFPCC.py decode pack.pk --lossless_lod 0|1|2 ...                   # exact at 32^3, 16^3 or 8^3 per block
 
-Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --lossless_lod, --thh_mode (count | block-count | d1:
+Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --lossless_lod, --lossless_ctx, --thh_mode (count | block-count | d1:
 nvfpcc_amd/thh_select.py picks the occupancy threshold at encode time and a `thh_pack` key carries it); multi-GPU training when launched
 through torch.distributed.run (one process per GPU, leaf blocks sharded, one RCCL all-reduce per step).
 Headless: no GUI window, no IPython shell.
@@ -204,6 +205,7 @@ def encode(args):
     """Pack everything the decoder needs (NVFPCC.py:395-554)."""
     from nvfpcc_amd import ops, weight_codec, latent_codec
     from nvfpcc_amd.recon import reconstruct_points, write_ply_ascii
+    lossless_ctx_refusals(args)
     bits = _bits(args)
     dev, rank, world = _device(args)
     data, pre = _load_data(args, dev, shuffle=False)
@@ -303,10 +305,14 @@ def _encode_lossless(args, total_pack, data, dev, batch):
 def _encode_lossless_lod(args, total_pack, data, dev, batch):
     """encode --lossless_lod: as _encode_lossless, with the coarse-to-fine coder (nvfpcc_amd.lossless_lod_pack).  The
     stream is decoded again at all three levels: a pack that does not reproduce the input's occupancy and its two
-    max-pools is not written.  -> {'pack': lossless_lod_pack bytes, 'line': the [LosslessLoD] line}."""
+    max-pools is not written.  --lossless_ctx nbr: the voxels under their parents' neighbours
+    (nvfpcc_amd.lossless_nbr_pack), the same key.  -> {'pack': lossless_lod_pack bytes, 'line': the [LosslessLoD] line}."""
     import contextlib
     import io
-    from nvfpcc_amd import lossless_lod_pack as lp
+    if getattr(args, 'lossless_ctx', 'field') == 'nbr':
+        from nvfpcc_amd import lossless_nbr_pack as lp
+    else:
+        from nvfpcc_amd import lossless_lod_pack as lp
     with contextlib.redirect_stdout(io.StringIO()):     # the decoder's own progress lines belong to decode
         net, latents = _decoder_from_pack(args, total_pack, dev)
     latents = latents[:data.N_leaf].contiguous()
@@ -428,9 +434,10 @@ def decode(args):
         _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10)
         return
     if getattr(args, 'lossless_lod', None) is not None:     # the input's voxels, or their exact 2^3 / 4^3 max-pool
-        from nvfpcc_amd import lossless_lod_pack as llp
+        from nvfpcc_amd import lossless_nbr_pack
         level = int(args.lossless_lod)
         try:
+            llp = lossless_nbr_pack.module_of(total_pack['lossless_lod_pack'])     # byte 0: which contexts coded it
             words, counts = llp.decode_occupancy(net, latents[:n].contiguous(), total_pack['lossless_lod_pack'], level=level,
                                                  batch=max(int(args.batchsize), 1))
         except ValueError as e:
@@ -501,6 +508,13 @@ def lossless_refusals(args, total_pack):
                          "coarser level of detail is lossy by construction")
     if total_pack is not None and 'lossless_pack' not in total_pack:
         raise SystemExit(f"decode --lossless: {args.input} carries no lossless_pack (it was encoded without --lossless)")
+
+
+def lossless_ctx_refusals(args):
+    """encode --lossless_ctx: it chooses the contexts of --lossless_lod and means nothing without it."""
+    if hasattr(args, 'lossless_ctx') and getattr(args, 'lossless_lod', None) is None:
+        raise SystemExit(f"encode: --lossless_ctx {args.lossless_ctx} chooses the contexts of --lossless_lod; give "
+                         f"--lossless_lod too")
 
 
 def lossless_lod_refusals(args, total_pack):
@@ -622,6 +636,10 @@ def build_parser():
                         'Gross bpp).  decode --lossless_lod L: write exactly the input\'s voxels (0) or exactly their '
                         'reduction to bits - L bits per axis (1, 2) to rc_dec.ply, from a prefix of the same stream; '
                         'excludes --lod and --lossless.')
+    p.add_argument('--lossless_ctx', choices=['field', 'nbr'], default=argparse.SUPPRESS,
+                   help='encode --lossless_lod: the contexts of the voxels.  field (the default): the decoder\'s field '
+                        'alone.  nbr: also the exact 16^3 occupancy of the parent cell\'s neighbours, which the decoder '
+                        'holds before the first voxel (fewer bits; decode tells the two apart by the pack).')
     p.add_argument('--ref_ply', default=None,
                    help='Original cloud (ASCII PLY): encode / decode also print its D1 / D2 geometry PSNR.')
     return p

@@ -958,6 +958,37 @@ int nvf_occ_hier_decode(int level, const float* pv, const uint8_t* kv, const int
                         const uint32_t* nwords, int64_t total_words, int batch, int group, uint64_t* occ_words,
                         int32_t* status, void* stream);
 
+/* ---- scalable lossless geometry, neighbour contexts (nvfpcc_amd/lossless_nbr_pack.py, csrc/occ_hier.hip) -------------
+ * A second context model for the same stream: pyramid, sections, symbol order, idle slots, coder, regions and status
+ * rules are those above, and so are the contexts of sections 2 and 1, (level * 4 + k) * 256 + occ_ctx(P): 1024..3071.
+ * A voxel v = (z, y, x) of section 0 is coded under the level-1 occupancy around its parent P = (z >> 1, y >> 1, x >> 1)
+ * as well.  With s_a = +1 where v's coordinate on axis a is odd, else -1, and O(q) the level-1 occupancy of cell q of
+ * the SAME block, 0 outside [0, 16)^3 (blocks do not see each other):
+ *   F = O(P + s_z e_z) + O(P + s_y e_y) + O(P + s_x e_x), E = the same sum over the three two-axis offsets, C = O at the
+ *   three-axis offset, n = (F * 4 + E) * 2 + C in [0, 32), and
+ *   ctx = 3072 + (n * 4 + k) * 256 + occ_ctx(p[v]), k = K1[P] as above.
+ * O is the ground truth's max-pool (gt_w1) at the encoder and what section 1 decoded at the decoder: known before the
+ * first voxel, and no part of the serial chain.  NVF_OCC_NBR_CONTEXTS = 3072 + 32 * 1024; contexts 0..1023 are never
+ * used.  f1 is int32 [NVF_OCC_NBR_CONTEXTS] on the device, 16-byte aligned, entries pulled into [1, 65535].
+ * nvf_occ_nbr_hist: the level-0 symbols, cnt / occ uint64 [NVF_OCC_NBR_CONTEXTS] as nvf_occ_hier_hist (which adds levels
+ *   1 and 2 to entries 1024..3071 of the same arrays); cells1 / counts1 the list of gt_w1.
+ * nvf_occ_nbr_encode: the arguments and results of nvf_occ_hier_encode, with the longer f1.
+ * nvf_occ_nbr_decode: section 0 of every group, as nvf_occ_hier_decode at level 0 (states, pos, status in and out, every
+ *   guarantee about damaged streams), plus w1 uint64 [batch, 64]: the level-1 words the previous call decoded, of which
+ *   cells1 / counts1 are the list.  Sections 2 and 1 are decoded by nvf_occ_hier_decode under the first
+ *   NVF_OCC_HIER_CONTEXTS entries of f1. */
+#define NVF_OCC_NBR_CONTEXTS 35840
+int nvf_occ_nbr_hist(const float* p, const uint8_t* k1, const uint64_t* gt_w0, const uint64_t* gt_w1, const int32_t* cells1,
+                     const int32_t* counts1, int batch, uint64_t* cnt, uint64_t* occ, void* stream);
+int nvf_occ_nbr_encode(const float* p, const float* p1, const uint8_t* k1, const float* p2, const uint8_t* k2,
+                       const uint64_t* gt_w0, const uint64_t* gt_w1, const uint64_t* gt_w2, const int32_t* cells2,
+                       const int32_t* counts2, const int32_t* cells1, const int32_t* counts1, const int32_t* f1,
+                       int batch, int group, uint64_t* states, uint32_t* words, uint32_t* nwords, void* stream);
+int nvf_occ_nbr_decode(const float* p, const uint8_t* k1, const int32_t* cells1, const int32_t* counts1, const uint64_t* w1,
+                       const int32_t* f1, uint64_t* states, int64_t* pos, const uint32_t* words, const int64_t* word_off,
+                       const uint32_t* nwords, int64_t total_words, int batch, int group, uint64_t* occ_words,
+                       int32_t* status, void* stream);
+
 /* ---- pre-processing on the device (nvfpcc_amd/preprocess.py: preprocess_device, csrc/pp_device.hip) ----------------
  * From int32 [P,3] points with coordinates of `bits` bits (10, 11 or 12; anything else is NVF_EINVAL) to everything
  * nvf_nearest_dist2 and the trainer take, without a host pass.  D = bits - 5 is the level of the 32^3 leaves.  A CELL

@@ -144,6 +144,9 @@ PROTOTYPES = {
     "nvf_occ_hier_hist": (I, [I, P, P, P, P, P, I, P, P, P]),
     "nvf_occ_hier_encode": (I, [P] * 13 + [I, I, P, P, P, P]),
     "nvf_occ_hier_decode": (I, [I, P, P, P, P, P, P, P, P, P, P, L, I, I, P, P, P]),
+    "nvf_occ_nbr_hist": (I, [P, P, P, P, P, P, I, P, P, P]),
+    "nvf_occ_nbr_encode": (I, [P] * 13 + [I, I, P, P, P, P]),
+    "nvf_occ_nbr_decode": (I, [P, P, P, P, P, P, P, P, P, P, P, L, I, I, P, P, P]),
     "nvf_pp_keys": (I, [P, I, I, P, P, P, P]),
     "nvf_pp_tree": (I, [P, I, I, P, P, P, P, P, P, P]),
     "nvf_pp_blocks": (I, [P, I, I, P, P, P, P, P]),

@@ -10,15 +10,27 @@
 //   nvf_occ_hier_hist      per context the coded symbols of one level and the occupied ones, exact integers
 //   nvf_occ_hier_encode    one 64-lane wave per group: sections 0, 1, 2, each backwards, ONE stream
 //   nvf_occ_hier_decode    one section per launch, states and word position in and out; a cell-list launch in between
+//   nvf_occ_nbr_hist / _encode / _decode   the second context model: a voxel is coded under the 16^3 occupancy of its
+//                          parent's neighbours as well (NBR below).  Sections 2 and 1 are the first model's
 //
 // Symbol i of a section belongs to lane i % 64 at step i / 64; a lane past the section's end is idle: it neither codes
 // nor renormalises.  Frequencies depend on the pyramid alone, so a wave fetches OCC_AHEAD steps before it enters the
 // serial chain, as occ_rans.hip does; the gathers of a parent's eight children are four rows of two adjacent floats.
 // The chain itself -- the step with its idle lanes, the word window, the status -- and the walk behind the cell lists
 // are occ_coder.h's.
+//
+// NBR: the level-0 contexts grow by the class n in [0, 32) of the parent's seven neighbours on the voxel's side, read
+// from the block's own 64 level-1 words: the ground truth's at the encoder, the ones section 1 left at the decoder, so
+// they are known before the first voxel and are gathered with the probabilities, HIER_AHEAD steps before the chain.
+// A row of 16 cells along x is one uint16 of those words, so a voxel gathers four rows: (Z, Y), (Z + sz, Y), (Z, Y + sy),
+// (Z + sz, Y + sy).  The 32 x 1024 level-0 frequencies sit in LDS as uint16 (64 KiB; a frequency is in [1, 65535]) next
+// to the 3072 uint32 entries the other two sections use; the histogram counts a block in ONE uint32 per context, symbols
+// in the low half and occupied ones in the high half (128 KiB): a block codes at most 32768 voxels, so neither half
+// can carry.
 #include "occ_coder.h"
 
 #define HIER_CTX 3072                                  // 3 levels x 4 child counts x 256
+#define NBR_CTX0 32768                                 // 32 neighbour classes x 4 child counts x 256, from context 3072 on
 #define HIER_AHEAD 8
 #define HIER_BLOCK_WORDS NVF_OCC_HIER_BLOCK_WORDS      // 512 + 4096 + 32768: an all-full block
 #define HIER_THREADS 1024
@@ -62,6 +74,48 @@ __device__ __forceinline__ void hier_where(int i, const int32_t* __restrict__ pa
 }
 
 __device__ __forceinline__ int hier_ctx(int level, int k, float v) { return (level * 4 + (k & 3)) * OCC_CTX + occ_ctx(v); }
+
+// the four rows of 16^3 cells a voxel's neighbour class is read from; a row outside the block is empty
+struct NbrRows {
+  uint32_t r00, r10, r01, r11;
+};
+
+__device__ __forceinline__ uint32_t nbr_row(const uint16_t* __restrict__ rows, int b, int Z, int Y) {
+  const bool in = (unsigned)Z < 16u && (unsigned)Y < 16u;
+  const uint32_t r = rows[(size_t)b * 256 + (in ? Z * 16 + Y : 0)];
+  return in ? r : 0u;
+}
+
+// e = block * 4096 + parent cell (hier_where's kcell at level 0), j = the voxel's child index: its odd coordinates
+__device__ __forceinline__ NbrRows nbr_gather(const uint16_t* __restrict__ rows, int e, int j) {
+  const int b = e >> 12, Z = (e >> 8) & 15, Y = (e >> 4) & 15;
+  const int Zs = Z + ((j & 4) ? 1 : -1), Ys = Y + ((j & 2) ? 1 : -1);
+  return NbrRows{nbr_row(rows, b, Z, Y), nbr_row(rows, b, Zs, Y), nbr_row(rows, b, Z, Ys), nbr_row(rows, b, Zs, Ys)};
+}
+
+// n = (F * 4 + E) * 2 + C: the occupied face, edge and corner neighbours
+__device__ __forceinline__ int nbr_class(const NbrRows& r, int e, int j) {
+  const int X = e & 15, Xs = X + ((j & 1) ? 1 : -1);
+  const uint32_t in = (unsigned)Xs < 16u ? 1u : 0u;
+  const int xs = Xs & 15;
+  const uint32_t F = ((r.r10 >> X) & 1u) + ((r.r01 >> X) & 1u) + ((r.r00 >> xs) & in);
+  const uint32_t E = ((r.r11 >> X) & 1u) + ((r.r10 >> xs) & in) + ((r.r01 >> xs) & in);
+  return (int)((F * 4u + E) * 2u + ((r.r11 >> xs) & in));
+}
+
+// index into the level-0 frequencies: context - 3072
+__device__ __forceinline__ int nbr_ctx0(int n, int k, float v) { return (n * 4 + (k & 3)) * OCC_CTX + occ_ctx(v); }
+
+// the NBR_CTX0 level-0 frequencies f0 (16-byte aligned) as uint16 in LDS, pulled into [1, 65535].  One wave.
+__device__ __forceinline__ void nbr_load_table(const int32_t* __restrict__ f0, uint16_t* tab0, int lane) {
+  const auto pull = [](int v) { return (uint32_t)(v < 1 ? 1 : (v > 65535 ? 65535 : v)); };
+#pragma unroll 8
+  for (int i = lane * 4; i < NBR_CTX0; i += 256) {
+    const int4 v = *(const int4*)(f0 + i);
+    *(uint2*)(tab0 + i) = make_uint2(pull(v.x) | (pull(v.y) << 16), pull(v.z) | (pull(v.w) << 16));
+  }
+  __syncthreads();
+}
 
 // m = c0; m = cj > m ? cj : m in child order: exact comparisons, the first of equal values (and of +-0) stays
 __device__ __forceinline__ void hier_fold(float c, float& m, int& k) {
@@ -203,17 +257,52 @@ __global__ __launch_bounds__(HIER_THREADS) void hier_hist_kernel(const float* __
   if (h_occ[tid]) atomicAdd(occ + LEVEL * 4 * OCC_CTX + tid, (unsigned long long)h_occ[tid]);
 }
 
-// one section of a group, backwards.  The words written so far are wg[ptr .. region).
-template <int LEVEL>
+// the level-0 symbols of one block under the neighbour contexts: one workgroup per block, one uint32 per context
+__global__ __launch_bounds__(HIER_THREADS) void nbr_hist_kernel(const float* __restrict__ p, const uint8_t* __restrict__ k1,
+                                                                const unsigned long long* __restrict__ w0,
+                                                                const uint16_t* __restrict__ rows,
+                                                                const int32_t* __restrict__ cells1,
+                                                                const int32_t* __restrict__ counts1,
+                                                                unsigned long long* __restrict__ cnt,
+                                                                unsigned long long* __restrict__ occ) {
+  __shared__ uint32_t h[NBR_CTX0];                     // occupied << 16 | symbols, each <= 32768
+  const int tid = threadIdx.x, b = blockIdx.x;
+  for (int c = tid; c < NBR_CTX0; c += HIER_THREADS) h[c] = 0;
+  __syncthreads();
+  const int32_t* parents = cells1 + hier_sum(counts1, 0, b, tid & 63);
+  const int n = 8 * counts1[b];
+  for (int i = tid; i < n; i += HIER_THREADS) {
+    int cell, e;
+    hier_where<0>(i, parents, b, cell, e);
+    const int c = nbr_ctx0(nbr_class(nbr_gather(rows, e, i & 7), e, i & 7), k1[e], p[cell]);
+    atomicAdd(&h[c], 1u + ((uint32_t)((w0[cell >> 6] >> (cell & 63)) & 1ull) << 16));
+  }
+  __syncthreads();
+  // integers: any order of these adds gives the same totals
+  for (int c = tid; c < NBR_CTX0; c += HIER_THREADS) {
+    const uint32_t v = h[c];
+    if (v & 0xFFFFu) atomicAdd(cnt + HIER_CTX + c, (unsigned long long)(v & 0xFFFFu));
+    if (v >> 16) atomicAdd(occ + HIER_CTX + c, (unsigned long long)(v >> 16));
+  }
+}
+
+// one section of a group, backwards.  The words written so far are wg[ptr .. region).  NBR (level 0 only): the
+// frequency comes from tab0 under the neighbour class read from `rows`, the ground truth's level-1 words.
+template <int LEVEL, bool NBR = false>
 __device__ __forceinline__ void hier_encode_section(int n, const int32_t* __restrict__ parents, int b0,
                                                     const float* __restrict__ pv, const uint8_t* __restrict__ kv,
                                                     const unsigned long long* __restrict__ gw, const uint32_t* tab,
-                                                    int lane, unsigned long long& x, int& ptr, uint32_t* __restrict__ wg) {
+                                                    int lane, unsigned long long& x, int& ptr, uint32_t* __restrict__ wg,
+                                                    const uint16_t* __restrict__ rows = nullptr,
+                                                    const uint16_t* tab0 = nullptr) {
+  static_assert(!NBR || LEVEL == 0, "only voxels have neighbour contexts");
   const int steps = (n + 63) >> 6;
   for (int t0 = (steps + HIER_AHEAD - 1) / HIER_AHEAD * HIER_AHEAD - HIER_AHEAD; t0 >= 0; t0 -= HIER_AHEAD) {
     float val[HIER_AHEAD];
     int kk[HIER_AHEAD], bit[HIER_AHEAD];
     unsigned long long gword[HIER_AHEAD];
+    NbrRows nr[NBR ? HIER_AHEAD : 1];
+    int ee[NBR ? HIER_AHEAD : 1];
 #pragma unroll
     for (int k = 0; k < HIER_AHEAD; ++k) {
       const int i = (t0 + k) * 64 + lane;
@@ -223,11 +312,17 @@ __device__ __forceinline__ void hier_encode_section(int n, const int32_t* __rest
       kk[k] = kv[kcell];
       gword[k] = gw[cell >> 6];
       bit[k] = cell & 63;
+      if constexpr (NBR) {
+        nr[k] = nbr_gather(rows, kcell, lane & 7);     // i & 7: a step is 64 symbols
+        ee[k] = kcell;
+      }
     }
     uint32_t fr[HIER_AHEAD], st[HIER_AHEAD];           // fr = 0: an idle lane
 #pragma unroll
     for (int k = 0; k < HIER_AHEAD; ++k) {
-      const uint32_t one = tab[hier_ctx(LEVEL, kk[k], val[k])];
+      uint32_t one;
+      if constexpr (NBR) one = tab0[nbr_ctx0(nbr_class(nr[k], ee[k], lane & 7), kk[k], val[k])];
+      else one = tab[hier_ctx(LEVEL, kk[k], val[k])];
       const bool s = (gword[k] >> bit[k]) & 1ull;
       const bool live = (t0 + k) * 64 + lane < n;
       fr[k] = !live ? 0u : (s ? one : 65536u - one);
@@ -239,7 +334,8 @@ __device__ __forceinline__ void hier_encode_section(int n, const int32_t* __rest
   }
 }
 
-// one wave per group
+// one wave per group.  NBR: section 0 under the neighbour contexts, f1 holds NVF_OCC_NBR_CONTEXTS entries
+template <bool NBR>
 __global__ __launch_bounds__(64) void hier_encode_kernel(const float* __restrict__ p, const float* __restrict__ p1,
                                                          const uint8_t* __restrict__ k1, const float* __restrict__ p2,
                                                          const uint8_t* __restrict__ k2,
@@ -254,13 +350,19 @@ __global__ __launch_bounds__(64) void hier_encode_kernel(const float* __restrict
   __shared__ uint32_t tab[HIER_CTX];
   const int lane = threadIdx.x, g = blockIdx.x;
   occ_load_table<HIER_CTX>(f1, tab, lane);
+  const uint16_t* tab0 = nullptr;
+  if constexpr (NBR) {
+    __shared__ __attribute__((aligned(16))) uint16_t t0[NBR_CTX0];
+    nbr_load_table(f1 + HIER_CTX, t0, lane);
+    tab0 = t0;
+  }
   const int b0 = g * G, nb = min(G, batch - b0);
   const int region = nb * HIER_BLOCK_WORDS;            // a symbol emits one word at the most
   uint32_t* wg = words + (size_t)g * G * HIER_BLOCK_WORDS;
   unsigned long long x = OCC_RANS_L;
   int ptr = region;
-  hier_encode_section<0>(8 * hier_sum(counts1, b0, b0 + nb, lane), cells1 + hier_sum(counts1, 0, b0, lane), b0, p, k1, w0,
-                         tab, lane, x, ptr, wg);
+  hier_encode_section<0, NBR>(8 * hier_sum(counts1, b0, b0 + nb, lane), cells1 + hier_sum(counts1, 0, b0, lane), b0, p, k1,
+                              w0, tab, lane, x, ptr, wg, (const uint16_t*)w1, tab0);
   hier_encode_section<1>(8 * hier_sum(counts2, b0, b0 + nb, lane), cells2 + hier_sum(counts2, 0, b0, lane), b0, p1, k1, w1,
                          tab, lane, x, ptr, wg);
   hier_encode_section<2>(nb * 512, nullptr, b0, p2, k2, w2, tab, lane, x, ptr, wg);
@@ -268,20 +370,21 @@ __global__ __launch_bounds__(64) void hier_encode_kernel(const float* __restrict
   if (lane == 0) nwords[g] = (uint32_t)(region - ptr);
 }
 
-// one section of every group, forwards.  states, pos and status carry the coder from one section's launch to the next.
-template <int LEVEL>
-__global__ __launch_bounds__(64) void hier_decode_kernel(const float* __restrict__ pv, const uint8_t* __restrict__ kv,
-                                                         const int32_t* __restrict__ cells, const int32_t* __restrict__ counts,
-                                                         const int32_t* __restrict__ f1,
-                                                         unsigned long long* __restrict__ states, long long* __restrict__ pos_io,
-                                                         const uint32_t* __restrict__ words,
-                                                         const long long* __restrict__ word_off,
-                                                         const uint32_t* __restrict__ nwords, long long total_words,
-                                                         int batch, int G, unsigned long long* __restrict__ occ_words,
-                                                         int32_t* __restrict__ status) {
-  __shared__ uint32_t tab[HIER_CTX];
+// one section of a group, forwards: what the decoder kernels below share.  NBR (level 0 only): the frequency comes
+// from tab0 under the neighbour class read from `rows`, the level-1 words section 1 decoded.
+template <int LEVEL, bool NBR>
+__device__ __forceinline__ void hier_decode_group(const float* __restrict__ pv, const uint8_t* __restrict__ kv,
+                                                  const int32_t* __restrict__ cells, const int32_t* __restrict__ counts,
+                                                  const uint32_t* tab, const uint16_t* tab0,
+                                                  const uint16_t* __restrict__ rows,
+                                                  unsigned long long* __restrict__ states, long long* __restrict__ pos_io,
+                                                  const uint32_t* __restrict__ words,
+                                                  const long long* __restrict__ word_off,
+                                                  const uint32_t* __restrict__ nwords, long long total_words,
+                                                  int batch, int G, unsigned long long* __restrict__ occ_words,
+                                                  int32_t* __restrict__ status) {
+  static_assert(!NBR || LEVEL == 0, "only voxels have neighbour contexts");
   const int lane = threadIdx.x, g = blockIdx.x;
-  occ_load_table<HIER_CTX>(f1, tab, lane);
   const int b0 = g * G, nb = min(G, batch - b0);
   // a stop before level 0 needs only a prefix of the group's words: there the cut alone is no damage
   OccWindow w = occ_window_open(words, word_off[g], (long long)nwords[g], total_words, LEVEL == 0);
@@ -297,6 +400,8 @@ __global__ __launch_bounds__(64) void hier_decode_kernel(const float* __restrict
   for (int t0 = 0; t0 < steps; t0 += HIER_AHEAD) {
     float val[HIER_AHEAD];
     int kk[HIER_AHEAD], where[HIER_AHEAD];
+    NbrRows nr[NBR ? HIER_AHEAD : 1];
+    int ee[NBR ? HIER_AHEAD : 1];
 #pragma unroll
     for (int k = 0; k < HIER_AHEAD; ++k) {
       const int i = (t0 + k) * 64 + lane;
@@ -305,10 +410,17 @@ __global__ __launch_bounds__(64) void hier_decode_kernel(const float* __restrict
       val[k] = pv[cell];
       kk[k] = kv[kcell];
       where[k] = cell;
+      if constexpr (NBR) {
+        nr[k] = nbr_gather(rows, kcell, lane & 7);     // i & 7: a step is 64 symbols
+        ee[k] = kcell;
+      }
     }
     uint32_t one[HIER_AHEAD];
 #pragma unroll
-    for (int k = 0; k < HIER_AHEAD; ++k) one[k] = tab[hier_ctx(LEVEL, kk[k], val[k])];
+    for (int k = 0; k < HIER_AHEAD; ++k) {
+      if constexpr (NBR) one[k] = tab0[nbr_ctx0(nbr_class(nr[k], ee[k], lane & 7), kk[k], val[k])];
+      else one[k] = tab[hier_ctx(LEVEL, kk[k], val[k])];
+    }
 #pragma unroll
     for (int k = 0; k < HIER_AHEAD; ++k) {
       const bool s = occ_decode_step<true>(x, one[k], (t0 + k) * 64 + lane < n, w, lane);
@@ -327,6 +439,39 @@ __global__ __launch_bounds__(64) void hier_decode_kernel(const float* __restrict
     pos_io[g] = w.pos;
     status[g] |= st;
   }
+}
+
+// one section of every group.  states, pos and status carry the coder from one section's launch to the next.
+template <int LEVEL>
+__global__ __launch_bounds__(64) void hier_decode_kernel(const float* __restrict__ pv, const uint8_t* __restrict__ kv,
+                                                         const int32_t* __restrict__ cells, const int32_t* __restrict__ counts,
+                                                         const int32_t* __restrict__ f1,
+                                                         unsigned long long* __restrict__ states, long long* __restrict__ pos_io,
+                                                         const uint32_t* __restrict__ words,
+                                                         const long long* __restrict__ word_off,
+                                                         const uint32_t* __restrict__ nwords, long long total_words,
+                                                         int batch, int G, unsigned long long* __restrict__ occ_words,
+                                                         int32_t* __restrict__ status) {
+  __shared__ uint32_t tab[HIER_CTX];
+  occ_load_table<HIER_CTX>(f1, tab, threadIdx.x);
+  hier_decode_group<LEVEL, false>(pv, kv, cells, counts, tab, nullptr, nullptr, states, pos_io, words, word_off, nwords,
+                                  total_words, batch, G, occ_words, status);
+}
+
+// section 0 of every group under the neighbour contexts: f0 = the level-0 frequencies, w1 = the decoded level-1 words
+__global__ __launch_bounds__(64) void nbr_decode_kernel(const float* __restrict__ p, const uint8_t* __restrict__ k1,
+                                                        const int32_t* __restrict__ cells1, const int32_t* __restrict__ counts1,
+                                                        const uint16_t* __restrict__ rows, const int32_t* __restrict__ f0,
+                                                        unsigned long long* __restrict__ states, long long* __restrict__ pos_io,
+                                                        const uint32_t* __restrict__ words,
+                                                        const long long* __restrict__ word_off,
+                                                        const uint32_t* __restrict__ nwords, long long total_words,
+                                                        int batch, int G, unsigned long long* __restrict__ occ_words,
+                                                        int32_t* __restrict__ status) {
+  __shared__ __attribute__((aligned(16))) uint16_t tab0[NBR_CTX0];
+  nbr_load_table(f0, tab0, threadIdx.x);
+  hier_decode_group<0, true>(p, k1, cells1, counts1, nullptr, tab0, rows, states, pos_io, words, word_off, nwords,
+                             total_words, batch, G, occ_words, status);
 }
 
 }  // namespace
@@ -384,7 +529,7 @@ extern "C" int nvf_occ_hier_encode(const float* p, const float* p1, const uint8_
       group > NVF_OCC_RANS_MAX_GROUP)
     return NVF_EINVAL;
   const int groups = (batch + group - 1) / group;
-  hier_encode_kernel<<<groups, 64, 0, nvf_stream(stream)>>>(
+  hier_encode_kernel<false><<<groups, 64, 0, nvf_stream(stream)>>>(
       p, p1, k1, p2, k2, (const unsigned long long*)gt_w0, (const unsigned long long*)gt_w1,
       (const unsigned long long*)gt_w2, cells2, counts2, cells1, counts1, f1, batch, group, (unsigned long long*)states,
       words, nwords);
@@ -413,6 +558,53 @@ extern "C" int nvf_occ_hier_decode(int level, const float* pv, const uint8_t* kv
     hier_decode_kernel<1><<<groups, 64, 0, s>>>(pv, kv, cells, counts, f1, x, ps, words, wo, nwords, tw, batch, group, ow, status);
   if (level == 0)
     hier_decode_kernel<0><<<groups, 64, 0, s>>>(pv, kv, cells, counts, f1, x, ps, words, wo, nwords, tw, batch, group, ow, status);
+  NVF_LAUNCH_CHECK();
+  return NVF_OK;
+}
+
+extern "C" int nvf_occ_nbr_hist(const float* p, const uint8_t* k1, const uint64_t* gt_w0, const uint64_t* gt_w1,
+                                const int32_t* cells1, const int32_t* counts1, int batch, uint64_t* cnt, uint64_t* occ,
+                                void* stream) {
+  if (!p || !k1 || !gt_w0 || !gt_w1 || !cells1 || !counts1 || !cnt || !occ || batch <= 0 || batch > NVF_OCC_HIER_MAX_BATCH)
+    return NVF_EINVAL;
+  nbr_hist_kernel<<<batch, HIER_THREADS, 0, nvf_stream(stream)>>>(p, k1, (const unsigned long long*)gt_w0,
+                                                                  (const uint16_t*)gt_w1, cells1, counts1,
+                                                                  (unsigned long long*)cnt, (unsigned long long*)occ);
+  NVF_LAUNCH_CHECK();
+  return NVF_OK;
+}
+
+extern "C" int nvf_occ_nbr_encode(const float* p, const float* p1, const uint8_t* k1, const float* p2, const uint8_t* k2,
+                                  const uint64_t* gt_w0, const uint64_t* gt_w1, const uint64_t* gt_w2,
+                                  const int32_t* cells2, const int32_t* counts2, const int32_t* cells1,
+                                  const int32_t* counts1, const int32_t* f1, int batch, int group, uint64_t* states,
+                                  uint32_t* words, uint32_t* nwords, void* stream) {
+  if (!p || !p1 || !k1 || !p2 || !k2 || !gt_w0 || !gt_w1 || !gt_w2 || !cells2 || !counts2 || !cells1 || !counts1 || !f1 ||
+      ((uintptr_t)f1 & 15) || !states || !words || !nwords || batch <= 0 || batch > NVF_OCC_HIER_MAX_BATCH || group < 1 ||
+      group > NVF_OCC_RANS_MAX_GROUP)
+    return NVF_EINVAL;
+  const int groups = (batch + group - 1) / group;
+  hier_encode_kernel<true><<<groups, 64, 0, nvf_stream(stream)>>>(
+      p, p1, k1, p2, k2, (const unsigned long long*)gt_w0, (const unsigned long long*)gt_w1,
+      (const unsigned long long*)gt_w2, cells2, counts2, cells1, counts1, f1, batch, group, (unsigned long long*)states,
+      words, nwords);
+  NVF_LAUNCH_CHECK();
+  return NVF_OK;
+}
+
+extern "C" int nvf_occ_nbr_decode(const float* p, const uint8_t* k1, const int32_t* cells1, const int32_t* counts1,
+                                  const uint64_t* w1, const int32_t* f1, uint64_t* states, int64_t* pos,
+                                  const uint32_t* words, const int64_t* word_off, const uint32_t* nwords,
+                                  int64_t total_words, int batch, int group, uint64_t* occ_words, int32_t* status,
+                                  void* stream) {
+  if (!p || !k1 || !cells1 || !counts1 || !w1 || !f1 || ((uintptr_t)f1 & 15) || !states || !pos || !words || !word_off ||
+      !nwords || !occ_words || !status || total_words < 0 || batch <= 0 || batch > NVF_OCC_HIER_MAX_BATCH || group < 1 ||
+      group > NVF_OCC_RANS_MAX_GROUP)
+    return NVF_EINVAL;
+  const int groups = (batch + group - 1) / group;
+  nbr_decode_kernel<<<groups, 64, 0, nvf_stream(stream)>>>(
+      p, k1, cells1, counts1, (const uint16_t*)w1, f1 + HIER_CTX, (unsigned long long*)states, (long long*)pos, words,
+      (const long long*)word_off, nwords, (long long)total_words, batch, group, (unsigned long long*)occ_words, status);
   NVF_LAUNCH_CHECK();
   return NVF_OK;
 }

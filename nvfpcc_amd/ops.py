@@ -1615,3 +1615,77 @@ def occ_hier_decode(pyr, f1, states, words, nwords, group, level=0):
                                         _ptr(status), _stream()), "nvf_occ_hier_decode")
         counts, cells = occ_hier_cells(occ_words, fill=lv > level)
     return occ_words, counts, status, pos
+
+
+# ---------------------------------------------------------------- neighbour contexts (csrc/occ_hier.hip, NBR)
+OCC_NBR_CONTEXTS = 3072 + 32 * 1024
+
+
+def _occ_nbr_table(f1, dev):
+    _chk(f1)
+    if f1.dtype != torch.int32 or f1.shape != (OCC_NBR_CONTEXTS,) or f1.device != dev or f1.data_ptr() % 16:
+        raise RuntimeError(f"f1 must be int32 [{OCC_NBR_CONTEXTS}] on the device of p, 16-byte aligned")
+
+
+def occ_nbr_hist(pyr, cnt=None, occ=None):
+    """occ_hier_hist under the neighbour contexts (include/nvf_hip.h, "neighbour contexts"): cnt and occ are int64
+    [35840]; levels 2 and 1 land in 1024..3071 through nvf_occ_hier_hist, the voxels in 3072.. -> (cnt, occ)."""
+    B, dev = pyr["p"].shape[0], pyr["p"].device
+    if cnt is None:
+        cnt, occ = (torch.zeros(OCC_NBR_CONTEXTS, dtype=torch.int64, device=dev) for _ in range(2))
+    _chk(cnt, occ)
+    if any(t.dtype != torch.int64 or t.shape != (OCC_NBR_CONTEXTS,) for t in (cnt, occ)):
+        raise RuntimeError(f"occ_nbr_hist: cnt and occ are int64 [{OCC_NBR_CONTEXTS}]")
+    cells2, counts2, cells1, counts1 = pyr["lists"]
+    w0, w1, _ = pyr["gt_words"]
+    for level, cells, counts in ((2, None, None), (1, cells2, counts2)):
+        pv, kv = _occ_hier_level(pyr, level)
+        check(lib().nvf_occ_hier_hist(level, _ptr(pv), _ptr(kv), _ptr(pyr["gt_words"][level]), _ptr(cells), _ptr(counts), B,
+                                      _ptr(cnt), _ptr(occ), _stream()), "nvf_occ_hier_hist")
+    check(lib().nvf_occ_nbr_hist(_ptr(pyr["p"]), _ptr(pyr["k1"]), _ptr(w0), _ptr(w1), _ptr(cells1), _ptr(counts1), B,
+                                 _ptr(cnt), _ptr(occ), _stream()), "nvf_occ_nbr_hist")
+    return cnt, occ
+
+
+def occ_nbr_encode(pyr, f1, group):
+    """occ_hier_encode with the voxels under the neighbour contexts: f1 int32 [35840] -> (states, words)."""
+    B, dev = pyr["p"].shape[0], pyr["p"].device
+    _occ_nbr_table(f1, dev)
+    G, ng = _occ_groups(B, group)
+    w0, w1, w2 = pyr["gt_words"]
+    cells2, counts2, cells1, counts1 = pyr["lists"]
+    return _occ_coded(B, G, ng, OCC_HIER_BLOCK_WORDS, dev, lambda states, region, nwords: check(
+        lib().nvf_occ_nbr_encode(_ptr(pyr["p"]), _ptr(pyr["p1"]), _ptr(pyr["k1"]), _ptr(pyr["p2"]), _ptr(pyr["k2"]),
+                                 _ptr(w0), _ptr(w1), _ptr(w2), _ptr(cells2), _ptr(counts2), _ptr(cells1), _ptr(counts1),
+                                 _ptr(f1), B, G, _ptr(states), _ptr(region), _ptr(nwords), _stream()),
+        "nvf_occ_nbr_encode"))
+
+
+def occ_nbr_decode(pyr, f1, states, words, nwords, group, level=0):
+    """occ_hier_decode of a stream occ_nbr_encode wrote (f1 int32 [35840]): sections 2 and 1 through
+    nvf_occ_hier_decode under f1's first 3072 entries, section 0 through nvf_occ_nbr_decode with the level-1 words
+    just decoded.  The same results, status bits and guarantees."""
+    B, dev = pyr["p"].shape[0], pyr["p"].device
+    _occ_nbr_table(f1, dev)
+    G, ng = _occ_groups(B, group)
+    if level not in (0, 1, 2):
+        raise RuntimeError(f"level must be 0, 1 or 2, got {level!r}")
+    words, word_off, total = _occ_stream("occ_nbr_decode", B, G, ng, states, words, nwords)
+    x = states.clone()
+    pos = torch.zeros(ng, dtype=torch.int64, device=dev)
+    status = torch.zeros(ng, dtype=torch.int32, device=dev)
+    cells = counts = above = None
+    for lv in (2, 1, 0)[:3 - level]:
+        pv, kv = _occ_hier_level(pyr, lv)
+        occ_words = torch.zeros((B, 512 >> 3 * lv), dtype=torch.int64, device=dev)
+        if lv:
+            check(lib().nvf_occ_hier_decode(lv, _ptr(pv), _ptr(kv), _ptr(cells), _ptr(counts), _ptr(f1), _ptr(x), _ptr(pos),
+                                            _ptr(words), _ptr(word_off), _ptr(nwords), total, B, G, _ptr(occ_words),
+                                            _ptr(status), _stream()), "nvf_occ_hier_decode")
+        else:
+            check(lib().nvf_occ_nbr_decode(_ptr(pv), _ptr(kv), _ptr(cells), _ptr(counts), _ptr(above), _ptr(f1), _ptr(x),
+                                           _ptr(pos), _ptr(words), _ptr(word_off), _ptr(nwords), total, B, G,
+                                           _ptr(occ_words), _ptr(status), _stream()), "nvf_occ_nbr_decode")
+        above = occ_words
+        counts, cells = occ_hier_cells(occ_words, fill=lv > level)
+    return occ_words, counts, status, pos

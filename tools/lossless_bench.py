@@ -23,6 +23,9 @@ same run, its routes alternating with v1's inside every repetition:
                      down to L with the cell-list launches between them
     lod_pyramid G    nvf_occ_hier_pyramid and the two cell lists alone on the span (the encoder's side, with ground truth)
     lod_coder G      nvf_occ_hier_encode alone, and the decoder's launches down to level 0, 1 and 2, on the span
+--lod --ctx nbr adds the neighbour contexts (lossless_nbr_pack, nvf_occ_nbr_*) as a third coder, its routes nbr_encode,
+nbr_decodeL, nbr_coder_encode and nbr_coder_decodeL alternating with the other two's in the same repetitions, and the
+bytes and bpp of its packs ("nbr_packs") next to the scalable coder's ("lod_packs") on the same cloud.
   Every whole call ends in a synchronise (its result is on the host or its
 status was read); the routes alternate inside every repetition, the first --warmup repetitions are dropped and the
 median, minimum and maximum of the rest are reported in milliseconds.  Each pack is decoded and compared with the
@@ -51,10 +54,14 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--lod", action="store_true", help="time the scalable coder (lossless_lod_pack) next to v1")
+    ap.add_argument("--ctx", choices=["field", "nbr"], default="field",
+                    help="nbr (with --lod): time the neighbour contexts (lossless_nbr_pack) next to the scalable coder")
     a = ap.parse_args()
+    if a.ctx == "nbr" and not a.lod:
+        raise SystemExit("lossless_bench.py: --ctx nbr is a route of the scalable coder; give --lod too")
     if not torch.cuda.is_available():
         raise SystemExit("lossless_bench.py needs a HIP device: nothing here can be timed on a CPU")
-    from nvfpcc_amd import lossless_lod_pack as llp, lossless_pack as lp, network, ops
+    from nvfpcc_amd import lossless_lod_pack as llp, lossless_nbr_pack as nlp, lossless_pack as lp, network, ops
     from nvfpcc_amd.model import Net
     from nvfpcc_amd.seeds import synthetic_seed
     dev = torch.device("cuda")
@@ -92,25 +99,30 @@ def main():
             raise SystemExit(f"group {G}: the pack does not decode to the ground truth")
         info[G] = {"bytes": len(packs[G]), "bpp": round(8 * len(packs[G]) / n_points, 4),
                    "ideal_bpp": round(side["ideal_bits"] / n_points, 4)}
-    lod_packs, lod_info = {}, {}
-    for G in groups if a.lod else ():
-        lod_packs[G], side = llp.encode_occupancy(net, lat, gt, batch=a.batch, group=G)
-        for level in (0, 1, 2):
-            words, counts = llp.decode_occupancy(net, lat, lod_packs[G], level=level, batch=a.batch)
-            if not torch.equal(words, side["gt_words"][level]) or (level == 0 and int(counts.sum().item()) != n_points):
-                raise SystemExit(f"group {G}: the scalable pack does not decode to the ground truth at level {level}")
-        lod_info[G] = {"bytes": len(lod_packs[G]), "bpp": round(8 * len(lod_packs[G]) / n_points, 4),
-                       "ideal_bpp": round(side["ideal_bits"] / n_points, 4), "contexts": side["contexts"],
-                       "symbols": side["symbols"], "v1_symbols": a.blocks * 32768}
+    lod_packs, lod_info, nbr_packs, nbr_info = {}, {}, {}, {}
+    coders = ([("scalable", llp, lod_packs, lod_info)] if a.lod else []) + \
+             ([("neighbour", nlp, nbr_packs, nbr_info)] if a.ctx == "nbr" else [])
+    for what, mod, out_packs, out_info in coders:
+        for G in groups:
+            out_packs[G], side = mod.encode_occupancy(net, lat, gt, batch=a.batch, group=G)
+            for level in (0, 1, 2):
+                words, counts = mod.decode_occupancy(net, lat, out_packs[G], level=level, batch=a.batch)
+                if not torch.equal(words, side["gt_words"][level]) or (level == 0 and int(counts.sum().item()) != n_points):
+                    raise SystemExit(f"group {G}: the {what} pack does not decode to the ground truth at level {level}")
+            out_info[G] = {"bytes": len(out_packs[G]), "bpp": round(8 * len(out_packs[G]) / n_points, 4),
+                           "ideal_bpp": round(side["ideal_bits"] / n_points, 4), "contexts": side["contexts"],
+                           "symbols": side["symbols"], "v1_symbols": a.blocks * 32768}
     routes = {"forward": forward}
     for G in groups:
         routes[f"encode_G{G}"] = lambda G=G: lp.encode_occupancy(net, lat, gt, batch=a.batch, group=G)
         routes[f"decode_G{G}"] = lambda G=G: lp.decode_occupancy(net, lat, packs[G], batch=a.batch)
-        if a.lod:
-            routes[f"lod_encode_G{G}"] = lambda G=G: llp.encode_occupancy(net, lat, gt, batch=a.batch, group=G)
+        for tag, mod, its_packs in (("lod", llp, lod_packs), ("nbr", nlp, nbr_packs)):
+            if G not in its_packs:
+                continue
+            routes[f"{tag}_encode_G{G}"] = lambda G=G, mod=mod: mod.encode_occupancy(net, lat, gt, batch=a.batch, group=G)
             for level in (0, 1, 2):
-                routes[f"lod_decode{level}_G{G}"] = lambda G=G, level=level: llp.decode_occupancy(
-                    net, lat, lod_packs[G], level=level, batch=a.batch)
+                routes[f"{tag}_decode{level}_G{G}"] = lambda G=G, level=level, mod=mod, its_packs=its_packs: \
+                    mod.decode_occupancy(net, lat, its_packs[G], level=level, batch=a.batch)
     times = {k: [] for k in routes}
     for rep in range(a.warmup + a.reps):
         for name, fn in routes.items():
@@ -141,16 +153,28 @@ def main():
                 span[G] += (pyr, hf1, hs, torch.cat(hw), torch.tensor([w.numel() for w in hw], dtype=torch.int32, device=dev))
                 for name in ("pyramid", "coder_encode", "coder_decode0", "coder_decode1", "coder_decode2"):
                     times[f"lod_{name}_G{G}"] = []
+                if a.ctx == "nbr":
+                    nf1, _ = nlp.table_from_counts(*(t.tolist() for t in ops.occ_nbr_hist(pyr)))
+                    nf1 = torch.tensor(nf1, dtype=torch.int32, device=dev)
+                    ns, nw = ops.occ_nbr_encode(pyr, nf1, G)
+                    span[G] += (nf1, ns, torch.cat(nw), torch.tensor([w.numel() for w in nw], dtype=torch.int32, device=dev))
+                    for name in ("coder_encode", "coder_decode0", "coder_decode1", "coder_decode2"):
+                        times[f"nbr_{name}_G{G}"] = []
         for rep in range(a.warmup + a.reps):
             for G in groups:
                 nb, p, gg, f1, states, flat, nwords = span[G][:7]
                 timed = [(f"coder_encode_G{G}", lambda: ops.occ_rans_encode(p, gg, f1, G)),
                          (f"coder_decode_G{G}", lambda: ops.occ_rans_decode(p, f1, states, flat, nwords, G))]
                 if a.lod:
-                    pyr, hf1, hs, hflat, hn = span[G][7:]
+                    pyr, hf1, hs, hflat, hn = span[G][7:12]
                     timed += [(f"lod_pyramid_G{G}", lambda: ops.occ_hier_pyramid(p, gg)),
                               (f"lod_coder_encode_G{G}", lambda: ops.occ_hier_encode(pyr, hf1, G))]
                     timed += [(f"lod_coder_decode{level}_G{G}", lambda level=level: ops.occ_hier_decode(pyr, hf1, hs, hflat, hn, G, level))
+                              for level in (0, 1, 2)]
+                if a.ctx == "nbr":
+                    nf1, ns, nflat, nn = span[G][12:]
+                    timed += [(f"nbr_coder_encode_G{G}", lambda: ops.occ_nbr_encode(pyr, nf1, G))]
+                    timed += [(f"nbr_coder_decode{level}_G{G}", lambda level=level: ops.occ_nbr_decode(pyr, nf1, ns, nflat, nn, G, level))
                               for level in (0, 1, 2)]
                 for name, fn in timed:
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -164,7 +188,7 @@ def main():
     out = {"tool": "lossless_bench", "device": torch.cuda.get_device_name(0), "blocks": a.blocks, "batch": a.batch,
            "chanstr": a.chanstr, "reps": a.reps, "warmup": a.warmup, "points": n_points,
            "span_blocks": {str(G): span[G][0] for G in groups}, "packs": {str(G): v for G, v in info.items()},
-           "lod_packs": {str(G): v for G, v in lod_info.items()},
+           "lod_packs": {str(G): v for G, v in lod_info.items()}, "nbr_packs": {str(G): v for G, v in nbr_info.items()},
            "ms": {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
                   for k, v in times.items()}}
     print(json.dumps(out))
