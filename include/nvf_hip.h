@@ -660,6 +660,16 @@ int nvf_step_tail(const NvfStepTail* args, void* stream);
  * the next schedule row.  Together with nvf_wgrad_reduce_multi_and_sums_fused (the weight gradients) this covers what
  * nvf_step_tail does; the caller makes the ranges the exact complement. */
 int nvf_finals_flush_tail(NvfStepCtx* ctx, const NvfStepTail* tail, const int64_t* ranges, int nranges, void* stream);
+/* nvf_wgrad_reduce_multi_and_sums_fused with adam (required) and nvf_finals_flush_tail as ONE call, two launches: the
+ * optimiser of such a step is split over both, and a caller that fails or is interrupted between two calls would hold
+ * half-updated parameters.  Same arguments, same bits; what the second call would refuse is refused before the first
+ * launch. */
+int nvf_wgrad_reduce_sums_fused_flush_tail(const float* const* slabs, float* const* dws, const int* nslabs,
+                                           const int* jtotals, int n, const float* const* addends,
+                                           const NvfAdamFuse* adam, const float* const* xs, float* const* outs,
+                                           const int* channels, const int* spatials, int ntensors, int batch,
+                                           void* workspace, size_t workspace_bytes, NvfStepCtx* ctx,
+                                           const NvfStepTail* tail, const int64_t* ranges, int nranges, void* stream);
 /* nvf_wgrad_reduce_multi_and_sums_fused (slab reduction with addends and the fused optimiser; no channel sums) and
  * nvf_finals_flush_tail in ONE launch -- for steps whose queued final passes read nothing that reduction writes.
  * Only the final passes' workgroups wait for one another before the schedule hand-over, so the reduction must read

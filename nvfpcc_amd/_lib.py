@@ -119,6 +119,7 @@ PROTOTYPES = {
     "nvf_weight_rate_batch_final": (I, [P, P, P, P, P, P]),
     "nvf_wgrad_reduce_multi_and_sums_fused": (I, [P, P, P, P, I, P, P, P, P, P, P, I, I, P, Z, P, P]),
     "nvf_finals_flush_tail": (I, [P, P, P, I, P]),
+    "nvf_wgrad_reduce_sums_fused_flush_tail": (I, [P, P, P, P, I, P, P, P, P, P, P, I, I, P, Z, P, P, P, I, P]),
     "nvf_uniform": (I, [P, L, U, U, P]),
     "nvf_nearest_dist2": (I, [P, P, P, P, P, P, I, P]),
     "nvf_threshold_count": (I, [P, F, P, I, I, P]),

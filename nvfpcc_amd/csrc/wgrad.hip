@@ -1684,3 +1684,28 @@ extern "C" int nvf_wgrad_reduce_multi_and_sums_fused(const float* const* slabs, 
   return NVF_OK;
 }
 
+// The two launches of a step whose optimiser is split -- nvf_wgrad_reduce_multi_and_sums_fused with `adam` (the weight
+// gradients' share) and nvf_finals_flush_tail (the rest) -- as ONE call: a caller that fails or is interrupted between two
+// calls then never holds half-updated parameters.  Same launches, same arguments, same bits; what the second call would
+// refuse is refused before the first launch.
+extern "C" int nvf_wgrad_reduce_sums_fused_flush_tail(const float* const* slabs, float* const* dws, const int* nslabs,
+                                                      const int* jtotals, int n, const float* const* addends,
+                                                      const NvfAdamFuse* adam, const float* const* xs,
+                                                      float* const* outs, const int* channels, const int* spatials,
+                                                      int ntensors, int batch, void* workspace, size_t workspace_bytes,
+                                                      NvfStepCtx* ctx, const NvfStepTail* tail, const int64_t* ranges,
+                                                      int nranges, void* stream) {
+  if (!adam || !tail || !nvf_ctx_ok(ctx)) return NVF_EINVAL;
+  if (nranges < 0 || nranges > 16 || (nranges > 0 && !ranges)) return NVF_EINVAL;
+  if (!tail->p || !tail->g || !tail->m || !tail->v || tail->n <= 0) return NVF_EINVAL;
+  if (tail->acc && (!tail->loss_terms || !tail->lbits || !tail->nbits || tail->nnb <= 0 || tail->nnb > 16)) return NVF_EINVAL;
+  if (tail->sched_rows && (!tail->sched_buf || !tail->sched_cursor || tail->sched_words <= 0 || !tail->done)) return NVF_EINVAL;
+  for (int r = 0; r < nranges; ++r)
+    if (ranges[2 * r] < 0 || ranges[2 * r + 1] > tail->n || ranges[2 * r] > ranges[2 * r + 1]) return NVF_EINVAL;
+  if (ctx->args.has_f && ctx->args.f_nterm > 3) return NVF_EINVAL;
+  const int rc = nvf_wgrad_reduce_multi_and_sums_fused(slabs, dws, nslabs, jtotals, n, addends, adam, xs, outs, channels,
+                                                       spatials, ntensors, batch, workspace, workspace_bytes, ctx, stream);
+  if (rc != NVF_OK) return rc;
+  return nvf_finals_flush_tail(ctx, tail, ranges, nranges, stream);
+}
+

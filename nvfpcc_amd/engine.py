@@ -92,6 +92,19 @@ def plan_step(narrow, wide, winograd, fused_stem, fused_latent_stem, heads3, ch,
                     tail_queued=tail, sums_in_trunk5=in_trunk5 and sums_in_trunk5, fused_optimiser=fuse and not hook)
 
 
+def _abandons_step(fn):
+    """A step entry point of TrainEngine: any exception out of it leaves "no step in flight" behind (_abandon_step).  The
+    handler is the only addition to a step that succeeds: no launch, no sync."""
+    @functools.wraps(fn)
+    def run(self, *args, **kw):
+        try:
+            return fn(self, *args, **kw)
+        except BaseException:
+            self._abandon_step()
+            raise
+    return run
+
+
 TRUNK = ("up0", "conv0", "up1", "conv1", "up2", "conv2", "conv2_cls")
 HEADS = ("conv1_cls", "conv0_cls")
 
@@ -475,14 +488,22 @@ class TrainEngine:
         return ops.conv3d_gather(g_out, L.w_bwd, None, L.cin, 5, 2, L.pad, tuple(x_in.shape[2:]), addend=addend,
                                  mask=mask)
 
-    def backward(self, *args, **kw):
-        try:
-            return self._backward(*args, **kw)
-        except BaseException:
-            self.ctx.cancel()              # never leave final passes or a latent tail queued in the context
-            raise
+    def _abandon_step(self):
+        """The step in flight will not finish: forget everything it left for its later launches.  After any exception
+        out of train_step, latent_step, eval_forward or backward the engine is in the state "no step in flight", and its
+        next step is the bits of an engine that never failed.  Nothing queued in the context (final passes, stem
+        backward, latent tail), no reduction job and no slab of the WgradBatch (a next step would append its jobs behind
+        them, leave the one-launch reduction at more than 16 jobs and add stale slabs into its gradients), none of the
+        flags one phase of a step leaves for a later one.  noise_step stays as bumped: the draw is spent.  What a
+        launch already did on the device needs no repair: every cooperative launch returns its arrival counters to
+        zero itself, and every buffer is written before it is read in the next step."""
+        self.ctx.cancel()
+        if self._wg is not None:
+            self._wg.abandon()
+        self._rate_ready = self.tail_done = False
 
-    def _backward(self, a, gt, dist, gt16, gt8, n_pts, mode, block_ids, want_w, want_emb, fuse=None):
+    @_abandons_step
+    def backward(self, a, gt, dist, gt16, gt8, n_pts, mode, block_ids, want_w, want_emb, fuse=None):
         """Loss (NVFPCC.py:161-196) and its gradients.  Weight grads land in self.flat_g.  The phases run in launch order;
         what they return stays referenced here until the last launch has been enqueued (queued stages write it late)."""
         deferred = a.get("p2") is None
@@ -687,10 +708,9 @@ class TrainEngine:
             self.tail_done = True
         # nothing the final passes read is written by the slab reduction: ONE launch for both where the bias partials exist
         one_launch = sums_done and rate_head
-        if not one_launch:
-            todo = [] if sums_done else sums
-            self._wg.finish_with_sums([t for t, _ in todo], [o for _, o in todo], addends=addends,
-                                      adam=adam if fused else None)
+        todo = [] if sums_done else sums
+        if not one_launch and not fused:
+            self._wg.finish_with_sums([t for t, _ in todo], [o for _, o in todo], addends=addends)
         if rate_head:
             ops.weight_rate_final(job, nbits, gs, gm, ctx=self.ctx)
         else:
@@ -704,7 +724,10 @@ class TrainEngine:
         elif one_launch:    # data parallelism (the all-reduce and the step tail follow): the same pairing without the optimiser
             self._wg.finish_and_flush(addends)
         elif fused:
-            self.ctx.flush_tail(tail, ranges)
+            # the optimiser is split over the slab reduction (weight gradients) and the finals launch (the rest): both
+            # launches in ONE library call, so that no exception between them leaves the parameters half updated
+            self._wg.finish_with_sums([t for t, _ in todo], [o for _, o in todo], addends=addends, adam=adam, tail=tail,
+                                      ranges=ranges)
         else:
             self.ctx.flush()
 
@@ -800,9 +823,9 @@ class TrainEngine:
         """All-reduce hook (data parallelism), then Adam (+ the epoch sums): nvf_step_tail with host coefficients."""
         if self.grad_hook is not None:
             self.grad_hook(self.flat_gx)
-        self.opt_step += 1
-        ops.step_tail(coef_host=ops.adam_coefficients(self.lr, self.opt_step), inv_npts_host=1.0 / n_pts,
+        ops.step_tail(coef_host=ops.adam_coefficients(self.lr, self.opt_step + 1), inv_npts_host=1.0 / n_pts,
                       **self._tail_kw(self.last))
+        self.opt_step += 1         # (behind the launch: a step whose optimiser did not run has not happened)
 
     def _idle_backward(self):
         """A rank whose share of a short last mini-batch is empty (NVFPCC.py:149 with 917 mod 16 = 5 blocks on 8
@@ -819,6 +842,7 @@ class TrainEngine:
         self.last = {"loss_terms": torch.zeros(4, device=self.dev), "latent_bits": torch.zeros(1, device=self.dev),
                      "net_bits": nbits, "n_pts": 1.0}
 
+    @_abandons_step
     def train_step(self, idx_host, q, idx_dev=None, update=True, n_pts=None):
         """One mini-batch decoder update (NVFPCC.py:149-223, minus logging).  Under data parallelism
         ``idx_host`` is this rank's share of the global mini-batch (possibly empty) and ``n_pts`` the occupied-voxel
@@ -850,6 +874,7 @@ class TrainEngine:
             self.grad_hook(self.flat_gx)
         return a
 
+    @_abandons_step
     def latent_step(self, q, lo=0, hi=None, update=True):
         """Full-batch latent update over blocks [lo, hi) (NVFPCC.py:225-251); no weight gradients."""
         hi = self.N_leaf if hi is None else hi
@@ -862,11 +887,12 @@ class TrainEngine:
         de = self.backward(a, self.gt[lo:hi], self.dist[lo:hi], self.gt16[lo:hi], self.gt8[lo:hi], n_pts, "train",
                            ids, want_w=False, want_emb=True)
         if update:
-            self.emb_step += 1
             ops.adam_step(self.emb[lo:hi].view(-1), de.view(-1), self.emb_m[lo:hi].view(-1),
-                          self.emb_v[lo:hi].view(-1), self.lr_emb, self.emb_step)
+                          self.emb_v[lo:hi].view(-1), self.lr_emb, self.emb_step + 1)
+            self.emb_step += 1
         return a, de
 
+    @_abandons_step
     def eval_forward(self, lo=0, hi=None, q=2):
         hi = self.N_leaf if hi is None else hi
         ids = torch.arange(lo, hi, device=self.dev)

@@ -95,6 +95,10 @@ class StepCtx:
               "nvf_finals_flush_tail")
 
     def cancel(self):
+        """Drop the queued final passes, the queued stem backward and the queued latent tail without launching them.  It
+        is one part of TrainEngine._abandon_step, whose contract is: after any exception out of train_step, latent_step,
+        eval_forward or backward, the engine is in the state "no step in flight", and its next step is the bits of an
+        engine that never failed."""
         lib().nvf_finals_cancel(self.ptr)
         lib().nvf_latent_tail_cancel(self.ptr)
 
@@ -730,6 +734,12 @@ class WgradBatch:
         jobs, self.jobs, self.offset = self.jobs, [], 0
         return jobs
 
+    def abandon(self):
+        """The backward pass these jobs belong to will not finish: drop them and their slab space (no launch).  Left
+        pending, they would be reduced into the next pass's gradients behind its own jobs.  Retired buffers stay."""
+        self._take_jobs()
+        self.sums_done = False
+
     @staticmethod
     def _check_slabs(what, counts, caps):
         """A launch that reports more slabs than the region allocated for them holds has written over its neighbours:
@@ -852,10 +862,13 @@ class WgradBatch:
             _parr(dls), _parr(xs), bases, _iarr(cs), _iarr([x.shape[-1] for x in xs]), xs[0].shape[0], max_slabs, nsl,
             _stream()), outs, [c * 27 for c in cs], max_slabs)
 
-    def finish_with_sums(self, tensors, outs, addends=None, adam=None):
+    def finish_with_sums(self, tensors, outs, addends=None, adam=None, tail=None, ranges=None):
         """finish() and multi_channel_sum(tensors, outs) with the reduction and the partial bias sums in one launch.
         ``addends``: {gradient data_ptr: tensor added to that gradient}; ``adam``: NvfAdamFuse applied to every weight
-        gradient element written (both need the one-launch form: <= 16 jobs)."""
+        gradient element written (both need the one-launch form: <= 16 jobs).  ``tail``, ``ranges`` (with ``adam``; a
+        step context is required): StepCtx.flush_tail(tail, ranges) follows in the SAME library call
+        (nvf_wgrad_reduce_sums_fused_flush_tail) -- the optimiser is split over the two launches, and no exception may
+        come between them."""
         import ctypes
         if not self.jobs or len(self.jobs) > 16 or not tensors:
             if addends or adam is not None:
@@ -864,11 +877,19 @@ class WgradBatch:
             if tensors:
                 multi_channel_sum(tensors, outs, ctx=self.ctx)
             return
+        if adam is not None and (tail is None or self.ctx is None):
+            raise RuntimeError("finish_with_sums: the fused optimiser needs its tail and a step context")
         jobs = self._take_jobs()
         *arrs, ws = _sum_args(tensors, outs, self.ctx)
-        check(lib().nvf_wgrad_reduce_multi_and_sums_fused(
-            *self._job_arrays(jobs, addends), None if adam is None else ctypes.byref(adam), *arrs,
-            tensors[0].shape[0], _ptr(ws), ws.numel(), _ctx(self.ctx), _stream()), "nvf_wgrad_reduce_multi_and_sums_fused")
+        args = (*self._job_arrays(jobs, addends), None if adam is None else ctypes.byref(adam), *arrs,
+                tensors[0].shape[0], _ptr(ws), ws.numel(), _ctx(self.ctx))
+        if adam is None:
+            check(lib().nvf_wgrad_reduce_multi_and_sums_fused(*args, _stream()), "nvf_wgrad_reduce_multi_and_sums_fused")
+            return
+        flat = [int(v) for r in ranges for v in r]
+        arr = (ctypes.c_int64 * max(len(flat), 1))(*flat)
+        check(lib().nvf_wgrad_reduce_sums_fused_flush_tail(*args, ctypes.byref(tail), arr, len(ranges), _stream()),
+              "nvf_wgrad_reduce_sums_fused_flush_tail")
 
     def finish_and_flush_tail(self, addends, adam, tail, ranges):
         """The slab reduction (addends, fused optimiser) and the context's queued final passes + step tail in ONE

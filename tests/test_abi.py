@@ -173,6 +173,19 @@ def _trunk_refusal_codes():
         out["reduce_finals: %s context" % what] = h.nvf_wgrad_reduce_finals(*jobs(3), None, c, None)
         out["reduce_finals_tail: %s context" % what] = finals_tail(3, c)
     out["reduce_multi: nothing to add"] = h.nvf_wgrad_reduce_multi(ptrs, ptrs, (ctypes.c_int * 17)(), ints, 16, None)
+    # the split optimiser's two launches as one call: whatever its SECOND launch would refuse, refused before the first
+    no_n = _lib.NvfStepTail(p=DUMMY, g=DUMMY, m=DUMMY, v=DUMMY, n=0)
+    past = (ctypes.c_int64 * 2)(0, 65)
+    split = lambda n, a, c, t, rg, nrg: h.nvf_wgrad_reduce_sums_fused_flush_tail(
+        *jobs(n), None, a, ptrs, ptrs, ints, ints, 2, 4, DUMMY, 1 << 20, c, t, rg, nrg, None)
+    for name, args in (("no optimiser", (3, None, ctx, ctypes.byref(tail), None, 0)),
+                       ("no tail", (3, ctypes.byref(adam), ctx, None, None, 0)),
+                       ("a blank context", (3, ctypes.byref(adam), blank, ctypes.byref(tail), None, 0)),
+                       ("a tail of no parameters", (3, ctypes.byref(adam), ctx, ctypes.byref(no_n), None, 0)),
+                       ("a range past the parameters", (3, ctypes.byref(adam), ctx, ctypes.byref(tail), past, 1)),
+                       ("17 ranges", (3, ctypes.byref(adam), ctx, ctypes.byref(tail), past, 17)),
+                       ("17 jobs", (17, ctypes.byref(adam), ctx, ctypes.byref(tail), None, 0))):
+        out["split optimiser: " + name] = split(*args)
     return out
 
 
@@ -202,6 +215,14 @@ def test_reduction_entry_points_refuse_bad_job_counts_and_contexts(trunk_refusal
     assert len(codes) == 2 * 4 + 2 * 2 + 1
     assert codes.pop("reduce_multi: nothing to add") == 0
     assert set(codes.values()) == {EINVAL}, codes
+
+
+def test_the_split_optimisers_one_call_refuses_before_its_first_launch(trunk_refusals):
+    """nvf_wgrad_reduce_sums_fused_flush_tail = the slab reduction with fused Adam + nvf_finals_flush_tail: a request whose
+    second launch would be refused must not run the first (half of the parameters updated).  Seven such requests; the
+    child process sees no GPU, so one wrongly accepted fails in the runtime instead of returning NVF_EINVAL."""
+    codes = {k: v for k, v in trunk_refusals.items() if k.startswith("split optimiser")}
+    assert len(codes) == 7 and set(codes.values()) == {EINVAL}, codes
 
 
 def test_ops_refuse_cpu_tensors():
