@@ -23,7 +23,7 @@ engine (nvfpcc_amd/engine.py) instead of a DataLoader + autograd loop.
     python NVFPCC.py encode ... --lossless_lod --lossless_ctx nbr              # the voxels under their parents' neighbours
     python NVFPCC.py decode pack.pk --lossless_lod 0|1|2 ...                   # exact at 32^3, 16^3 or 8^3 per block
 
-Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --lossless_lod, --lossless_ctx, --thh_mode (count | block-count | d1:
+Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --ply_format, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --lossless_lod, --lossless_ctx, --thh_mode (count | block-count | d1:
 nvfpcc_amd/thh_select.py picks the occupancy threshold at encode time and a `thh_pack` key carries it); multi-GPU training when launched
 through torch.distributed.run (one process per GPU, leaf blocks sharded, one RCCL all-reduce per step).
 Headless: no GUI window, no IPython shell.
@@ -103,8 +103,8 @@ def _load_data(args, dev, shuffle=True):
     DevicePreprocess or None)."""
     from nvfpcc_amd.dataloader import LoadedVoxelDataset
     if getattr(args, 'from_ply', False):
-        from nvfpcc_amd import preprocess as pp
-        pre = pp.preprocess_device(pp.read_ply_xyz(args.input), dev, bits=getattr(args, 'bits', 10))
+        from nvfpcc_amd import ply_io, preprocess as pp
+        pre = pp.preprocess_device(ply_io.read_ply(args.input, device=dev)[0], dev, bits=getattr(args, 'bits', 10))
         return LoadedVoxelDataset.from_device(pre, shuffle=shuffle), pre
     fid = args.input[:-4]
     return LoadedVoxelDataset(f'{fid}_l5_origins.npy', f'{fid}_l5_gt_grid.npy', f'{fid}_l5_dist.npy',
@@ -204,9 +204,11 @@ TEST_LINE = ('[Epoch %04d TEST %.1f seconds] Loss: %.4e PosiPenal: %.4f PosiGain
 def encode(args):
     """Pack everything the decoder needs (NVFPCC.py:395-554)."""
     from nvfpcc_amd import ops, weight_codec, latent_codec
-    from nvfpcc_amd.recon import reconstruct_points, write_ply_ascii
+    from nvfpcc_amd import ply_io
+    from nvfpcc_amd.recon import reconstruct_points
     lossless_ctx_refusals(args)
     bits = _bits(args)
+    fmt = getattr(args, 'ply_format', 'ascii')
     dev, rank, world = _device(args)
     data, pre = _load_data(args, dev, shuffle=False)
     net = _build_net(args, dev)
@@ -268,12 +270,12 @@ def encode(args):
     print('[Latent code] Gross bpp: %.4f' % ((latent_bits + net_bits + side_bits) / data.N))
     print('[Recon] Pacc: %.4f Nacc: %.4f MSE1: %.4f PSNR1: %.4f' % (
         m[0] / max(m[1], 1), m[2] / max(m[3], 1), *_psnr1(m[4], m[5], (1 << bits) - 1)))
-    write_ply_ascii('rc_enc.ply', pts)
+    ply_io.write_ply('rc_enc.ply', pts, fmt=fmt, device=dev)
     _print_pc_error(args, pts, dev)
     if lod is not None:
         for level, (line, lod_pts) in enumerate(zip(lod['lines'], lod['points']), 1):
             print(line)
-            write_ply_ascii('rc_enc_lod%d.ply' % level, lod_pts)
+            ply_io.write_ply('rc_enc_lod%d.ply' % level, lod_pts, fmt=fmt, device=dev)
     if lossless is not None:
         print(lossless['line'])
     if lossless_lod is not None:
@@ -394,9 +396,11 @@ def _select_threshold(mode, net, latents, data, origins, dev, batch):
 def decode(args):
     """Decode from a pack (NVFPCC.py:557-652)."""
     from nvfpcc_amd import weight_codec, latent_codec
-    from nvfpcc_amd.recon import reconstruct_points, write_ply_ascii
+    from nvfpcc_amd import ply_io
+    from nvfpcc_amd.recon import reconstruct_points
     lossless_refusals(args, None)
     lossless_lod_refusals(args, None)
+    fmt = getattr(args, 'ply_format', 'ascii')
     dev, rank, world = _device(args)
     net = _build_net(args, torch.device('cpu'))
     with open(args.input, 'rb') as f:
@@ -430,7 +434,7 @@ def decode(args):
             raise SystemExit(f"decode --lossless: {e}")
         pts = lp.points_from_words(words, counts, origins)
         print('[Lossless] points: %d' % pts.shape[0])
-        write_ply_ascii('rc_dec.ply', pts)
+        ply_io.write_ply('rc_dec.ply', pts, fmt=fmt, device=dev)
         _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10)
         return
     if getattr(args, 'lossless_lod', None) is not None:     # the input's voxels, or their exact 2^3 / 4^3 max-pool
@@ -444,7 +448,7 @@ def decode(args):
             raise SystemExit(f"decode --lossless_lod {level}: {e}")
         pts = llp.points_from_words(words, counts, origins, level)
         print('[LosslessLoD] level: %d points: %d' % (level, pts.shape[0]))
-        write_ply_ascii('rc_dec.ply', pts)
+        ply_io.write_ply('rc_dec.ply', pts, fmt=fmt, device=dev)
         _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10, lod=level)
         return
     if lod_side is not None:                # a coarser level of detail: the trunk stops at the level's head
@@ -453,7 +457,7 @@ def decode(args):
         pts, counts = reconstruct_points_lod(net, latents[:n].contiguous(), origins, lod, t,
                                              batch=max(int(args.batchsize), 1))
         print(lp.lod_line(lod, t, pts.shape[0]))
-        write_ply_ascii('rc_dec.ply', pts)
+        ply_io.write_ply('rc_dec.ply', pts, fmt=fmt, device=dev)
         _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10, lod=lod)
         return
     thh, block_counts, used = args.thh, None, []
@@ -473,7 +477,7 @@ def decode(args):
                                      batch=max(int(args.batchsize), 1), block_counts=block_counts, thh_out=used)
     if block_counts is not None:
         print(ts.threshold_line('block-count', block_counts=block_counts, thresholds=torch.cat(used).cpu().numpy()))
-    write_ply_ascii('rc_dec.ply', pts)
+    ply_io.write_ply('rc_dec.ply', pts, fmt=fmt, device=dev)
     _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10)
 
 
@@ -552,10 +556,12 @@ def _print_pc_error(args, pts, dev, bits=10, lod=0):
     D2 uses estimated ones) and bits - lod is the domain and the peak."""
     if args.ref_ply is None:
         return
-    from nvfpcc_amd.pc_metrics import geometry_psnr, read_ply_points
-    ref, ref_normals = read_ply_points(args.ref_ply)
+    from nvfpcc_amd import ply_io
+    from nvfpcc_amd.pc_metrics import geometry_psnr
+    ref, ref_normals = ply_io.read_ply(args.ref_ply, device=dev, normals=True)      # ASCII or binary
     if lod:
         from nvfpcc_amd.recon import reduce_to_lattice
+        ref = ref.cpu().numpy() if isinstance(ref, torch.Tensor) else ref
         ref, ref_normals, bits = reduce_to_lattice(ref, lod), None, bits - lod
         print('[PCError] LoD %d: %d reference points on the %d-bit lattice, peak %d' % (lod, ref.shape[0], bits, (1 << bits) - 1))
         # the search index covers 10 to 12 bits per axis; a smaller domain fits the 10-bit one, the peak is the lattice's
@@ -608,7 +614,7 @@ def build_parser():
                         '(thh_pack) and decode uses it; decode --thh_mode fixed ignores it and uses --thh.')
     # opt-in switches: absent from the namespace unless given, so a command line without them parses as it always did
     p.add_argument('--from_ply', action='store_true', default=argparse.SUPPRESS,
-                   help='train / encode: the input is the cloud itself (ASCII PLY, 10-bit coordinates); it is '
+                   help='train / encode: the input is the cloud itself (ASCII or binary PLY, 10-bit coordinates); it is '
                         'pre-processed on the device and no *_l5_*.npy file is read or written.')
     p.add_argument('--bits', type=int, choices=[10, 11, 12], default=argparse.SUPPRESS,
                    help='train / encode with --from_ply: bits per axis of the cloud (10 when absent).  The leaf cubes '
@@ -640,8 +646,11 @@ def build_parser():
                    help='encode --lossless_lod: the contexts of the voxels.  field (the default): the decoder\'s field '
                         'alone.  nbr: also the exact 16^3 occupancy of the parent cell\'s neighbours, which the decoder '
                         'holds before the first voxel (fewer bits; decode tells the two apart by the pack).')
+    p.add_argument('--ply_format', choices=['ascii', 'binary'], default=argparse.SUPPRESS,
+                   help='encode / decode: format of the rc_*.ply files written.  ascii (also when absent): double x y z '
+                        'as text; binary: binary_little_endian with float x y z.')
     p.add_argument('--ref_ply', default=None,
-                   help='Original cloud (ASCII PLY): encode / decode also print its D1 / D2 geometry PSNR.')
+                   help='Original cloud (ASCII or binary PLY): encode / decode also print its D1 / D2 geometry PSNR.')
     return p
 
 

@@ -1038,6 +1038,37 @@ int nvf_pp_neighbours(const int32_t* origins, int bits, const uint32_t* rank_tab
                       int nblocks, void* stream);
 int nvf_pp_grids(const int32_t* d2, float* dist, float* gt, int64_t n, void* stream);
 
+/* ---- PLY text (nvfpcc_amd/ply_io.py, csrc/ply_io.hip) ---------------------------------------------------------------
+ * The body of an ASCII PLY, on the device in both directions.  `text` is uint8 [nbytes]; every offset is int64.  A line
+ * ends at '\n' or at the end of the text; line k is the k-th of them, blank lines included.  No call reads or writes
+ * at or beyond text + nbytes, whatever the bytes, `starts` or `offsets` hold.  Every call refuses null pointers and
+ * negative sizes with NVF_EINVAL before any HIP call and returns NVF_OK without a launch when there is nothing to do
+ * (nbytes == 0, n == 0, nlines == 0).
+ * nvf_ply_count_lines: counts int64 [ceil(nbytes / chunk)], the '\n' in each chunk of `chunk` >= 1 bytes.
+ * nvf_ply_line_starts: chunk_first int64 [as counts] = the exclusive prefix sum of counts; starts int64 [nlines]:
+ *   starts[k] = the byte offset of the start of line k, for every line k < nlines that the text has (the line after a
+ *   final '\n' starts at nbytes and is empty).  Entries of lines the text does not have are left as they were: the
+ *   caller fills starts with -1 first.
+ * nvf_ply_parse_xyz: one vertex per line first_line + i, i < n; starts holds at least first_line + n entries.  A token
+ *   is a maximal run of bytes other than space, tab, CR, LF.  The tokens of columns cx, cy, cz (distinct, < nprops)
+ *   must match [+-]?[0-9]{1,10}(\.0*)? with a magnitude <= 2147483647; xyz int32 [n, 3] receives their values (-0 is 0;
+ *   0 for a token outside the grammar).  Other tokens are skipped, never interpreted.
+ *   status int64 [4], written by the call: [0] lines with fewer than nprops tokens (a line with a negative start or one
+ *   >= nbytes has none), [1] lines with a coordinate token outside the grammar or with a byte a host reader may split
+ *   at where this one does not (below 0x20 other than tab, LF and a CR right before LF or the end; 0x7f and above),
+ *   [2] and [3] the lowest i of either kind, -1 when there is none.
+ * nvf_ply_format_sizes: sizes int32 [n] = strlen of "%d %d %d\n" for xyz int32 [n, 3] (INT32_MIN included).
+ * nvf_ply_format_xyz: offsets int64 [n + 1], offsets[0] = 0 and offsets[i + 1] = offsets[i] + sizes[i]; writes the
+ *   lines to text[offsets[i] ..).  A line that inconsistent offsets would put outside its workgroup's range or outside
+ *   [0, nbytes) is not written. */
+int nvf_ply_count_lines(const uint8_t* text, int64_t nbytes, int64_t chunk, int64_t* counts, void* stream);
+int nvf_ply_line_starts(const uint8_t* text, int64_t nbytes, int64_t chunk, const int64_t* chunk_first, int64_t* starts,
+                        int64_t nlines, void* stream);
+int nvf_ply_parse_xyz(const uint8_t* text, int64_t nbytes, const int64_t* starts, int64_t first_line, int64_t n, int nprops,
+                      int cx, int cy, int cz, int32_t* xyz, int64_t* status, void* stream);
+int nvf_ply_format_sizes(const int32_t* xyz, int64_t n, int32_t* sizes, void* stream);
+int nvf_ply_format_xyz(const int32_t* xyz, const int64_t* offsets, int64_t n, uint8_t* text, int64_t nbytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -153,6 +153,11 @@ PROTOTYPES = {
     "nvf_pp_blocks": (I, [P, I, I, P, P, P, P, P]),
     "nvf_pp_neighbours": (I, [P, I, P, P, P, I, P]),
     "nvf_pp_grids": (I, [P, P, P, L, P]),
+    "nvf_ply_count_lines": (I, [P, L, L, P, P]),
+    "nvf_ply_line_starts": (I, [P, L, L, P, P, L, P]),
+    "nvf_ply_parse_xyz": (I, [P, L, P, L, L, I, I, I, I, P, P, P]),
+    "nvf_ply_format_sizes": (I, [P, L, P, P]),
+    "nvf_ply_format_xyz": (I, [P, P, L, P, L, P]),
 }
 
 

@@ -1710,3 +1710,72 @@ def occ_nbr_decode(pyr, f1, states, words, nwords, group, level=0):
         above = occ_words
         counts, cells = occ_hier_cells(occ_words, fill=lv > level)
     return occ_words, counts, status, pos
+
+
+# ---------------------------------------------------------------- PLY text (csrc/ply_io.hip)
+PLY_CHUNK = 4096        # bytes of text per wave in the two line passes
+
+
+def _ply_text(text):
+    _chk(text)
+    if text.dtype != torch.uint8 or text.dim() != 1:
+        raise RuntimeError("PLY text must be a uint8 tensor [nbytes]")
+
+
+def ply_line_starts(text, nlines, chunk=PLY_CHUNK):
+    """text uint8 [nbytes] on the device -> int64 [nlines]: the byte offset of the start of each of the first `nlines`
+    lines (a line ends at '\\n' or at the end of the text; blank lines count), -1 for a line the text does not have.
+    The line after a final '\\n' starts at nbytes and is empty."""
+    _ply_text(text)
+    nbytes, nlines, chunk = text.numel(), int(nlines), int(chunk)
+    if chunk < 1 or nlines < 0:
+        raise RuntimeError(f"ply_line_starts: chunk {chunk} and nlines {nlines} must be positive")
+    starts = torch.full((nlines,), -1, dtype=torch.int64, device=text.device)
+    if nbytes == 0 or nlines == 0:
+        return starts
+    counts = torch.empty((nbytes + chunk - 1) // chunk, dtype=torch.int64, device=text.device)
+    check(lib().nvf_ply_count_lines(_ptr(text), nbytes, chunk, _ptr(counts), _stream()), "nvf_ply_count_lines")
+    first = (torch.cumsum(counts, 0) - counts).contiguous()
+    check(lib().nvf_ply_line_starts(_ptr(text), nbytes, chunk, _ptr(first), _ptr(starts), nlines, _stream()),
+          "nvf_ply_line_starts")
+    return starts
+
+
+def ply_parse_xyz(text, first_line, n, nprops, cols, chunk=PLY_CHUNK):
+    """The n vertex lines first_line .. first_line + n of an ASCII PLY body (text uint8 [nbytes] on the device), nprops
+    columns each, x y z in the columns `cols` -> (xyz int32 [n, 3], status int64 [4], both on the device): the contract
+    of nvf_ply_parse_xyz in include/nvf_hip.h.  xyz is good when status[0] == status[1] == 0."""
+    first_line, n = int(first_line), int(n)
+    starts = ply_line_starts(text, first_line + n, chunk)
+    xyz = torch.empty((n, 3), dtype=torch.int32, device=text.device)
+    status = torch.tensor([0, 0, -1, -1], dtype=torch.int64).to(text.device)
+    cx, cy, cz = (int(c) for c in cols)
+    if n == 0:
+        return xyz, status
+    if text.numel() == 0:                 # no text, no lines: every vertex is short (the entry takes no empty buffer)
+        return xyz.zero_(), torch.tensor([n, 0, 0, -1], dtype=torch.int64).to(text.device)
+    check(lib().nvf_ply_parse_xyz(_ptr(text), text.numel(), _ptr(starts), first_line, n, int(nprops), cx, cy, cz,
+                                  _ptr(xyz), _ptr(status), _stream()), "nvf_ply_parse_xyz")
+    return xyz, status
+
+
+def ply_format_xyz(xyz, guard=0):
+    """xyz int32 [n, 3] on the device -> uint8 [nbytes] on the device: "%d %d %d\\n" per point, in order.  guard > 0
+    (tests): the buffer is `guard` bytes longer, those bytes hold 0xAA, and the whole buffer is returned with nbytes:
+    (buffer, nbytes)."""
+    _chk(xyz)
+    if xyz.dtype != torch.int32 or xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise RuntimeError("ply_format_xyz: points must be int32 [n, 3]")
+    n, dev = xyz.shape[0], xyz.device
+    nbytes = 0
+    if n:
+        sizes = torch.empty(n, dtype=torch.int32, device=dev)
+        check(lib().nvf_ply_format_sizes(_ptr(xyz), n, _ptr(sizes), _stream()), "nvf_ply_format_sizes")
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(sizes, 0, dtype=torch.int64, out=offsets[1:])
+        nbytes = int(offsets[n].item())
+    text = torch.full((nbytes + guard,), 0xAA, dtype=torch.uint8, device=dev) if guard else \
+        torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    if nbytes:
+        check(lib().nvf_ply_format_xyz(_ptr(xyz), _ptr(offsets), n, _ptr(text), nbytes, _stream()), "nvf_ply_format_xyz")
+    return (text, nbytes) if guard else text

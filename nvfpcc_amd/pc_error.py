@@ -2,8 +2,9 @@
 
     python -m nvfpcc_amd.pc_error REF.ply TEST.ply [--bits 10] [--index dense|sparse] [--peak 1023] [--knn 12] [--no-d2]
 
-REF.ply is the original (A), TEST.ply the decoded cloud (B); both ASCII PLY with integer coordinates in [0, 2^bits),
-bits = 10, 11 or 12.  --peak defaults to 2^bits - 1; --index to the dense cell grid at 10 bits and the sparse one above.
+REF.ply is the original (A), TEST.ply the decoded cloud (B); each an ASCII or a binary PLY (nvfpcc_amd.ply_io) with
+integer coordinates in [0, 2^bits), bits = 10, 11 or 12.  --peak defaults to 2^bits - 1; --index to the dense cell grid
+at 10 bits and the sparse one above.
 The normals of A come from REF.ply's nx ny nz when it has them, otherwise from a k-NN PCA (nvfpcc_amd.pc_metrics).
 The exit status is 1 on bad input.
 """
@@ -32,8 +33,8 @@ def _lines(r, d2):
 
 def build_parser():
     p = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    p.add_argument("ref", help="reference cloud (A), ASCII PLY")
-    p.add_argument("test", help="test (decoded) cloud (B), ASCII PLY")
+    p.add_argument("ref", help="reference cloud (A), ASCII or binary PLY")
+    p.add_argument("test", help="test (decoded) cloud (B), ASCII or binary PLY")
     p.add_argument("--bits", type=int, choices=(10, 11, 12), default=10,
                    help="bits per axis: coordinates lie in [0, 2^bits)")
     p.add_argument("--index", choices=("dense", "sparse"), default=None,
@@ -48,10 +49,13 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.peak is None:
         args.peak = (1 << args.bits) - 1
-    from nvfpcc_amd.pc_metrics import geometry_psnr, read_ply_points
+    import torch
+    from nvfpcc_amd.pc_metrics import geometry_psnr
+    from nvfpcc_amd.ply_io import read_ply
+    dev = "cuda" if torch.cuda.is_available() else None     # the device geometry_psnr runs on; without one it says so
     try:
-        a, na = read_ply_points(args.ref)
-        b, _ = read_ply_points(args.test)
+        a, na = read_ply(args.ref, device=dev, normals=True)
+        b, _ = read_ply(args.test, device=dev)
         r = geometry_psnr(a, b, peak=args.peak, ref_normals=na, knn=args.knn, d2=not args.no_d2, bits=args.bits,
                           index=args.index)
     except (OSError, ValueError) as e:

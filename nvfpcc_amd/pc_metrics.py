@@ -256,7 +256,8 @@ def geometry_psnr(ref, test, peak=None, ref_normals=None, knn=12, d2=True, devic
 
 def read_ply_points(path):
     """(xyz int64 [n, 3], normals float64 [n, 3] or None) of an ASCII PLY, by the header's property names: x, y and z
-    need not be the first columns; nx ny nz are returned when all three are present.  Binary PLY raises ValueError."""
+    need not be the first columns; nx ny nz are returned when all three are present.  Binary PLY raises ValueError.
+    nvfpcc_amd.ply_io.read_ply reads both formats, and ASCII on the device."""
     with open(path, "rb") as f:
         raw = f.read()
     if not raw.startswith(b"ply"):
