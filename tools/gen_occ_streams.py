@@ -4,6 +4,10 @@ tests/occ_hier_ref.py) make of one seeded input -- tables, final states, every g
 the words a decoder consumes at each stop level.  tests/test_occ_ref_anchor_cpu.py holds the references to this file, so
 run it on the commit whose references are the yardstick, BEFORE changing them, never to make a failing test pass.
 
+This file pins the numpy coders to inputs they generate themselves; it does not pin the FIELD they code under.  That is
+tests/golden/conformance_{S,W}.npz (tools/make_conformance_fixture.py): the float32 bits of the eval forward on the two
+committed trained decoders, and the side packs encoded under them.
+
     python tools/gen_occ_streams.py       # rewrites tests/golden/occ_streams.npz
 """
 import os
