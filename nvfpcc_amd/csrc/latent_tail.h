@@ -27,7 +27,13 @@ struct RateTerm {
 
 // gsign: sign of the gradient arriving at `bits` (LowerBound passes when like >= 1e-8 OR the
 // incoming gradient on `like` is negative; that gradient is gsign * (-1/(like ln2))).
-__device__ __forceinline__ RateTerm rate_term(float v, float mu, float sabs, float half, float gsign) {
+// fused_pdf_diff (a constant at every call): how pu - pl, the factor of d/dv, is rounded.  Left to the compiler, the
+// product inside std_pdf(up) was fused into the subtraction (one fma) in the mini-batch path of latent_rate_body and not
+// in its loop path (which multiplies pu and pl as a packed pair), so d/dv of the same latent differed in its last bit
+// between a mini-batch and a larger batch.  Both forms are now spelled out, and each caller keeps the one its
+// mini-batch results have always had: the latent rate the fma, the weight rate the subtraction of the rounded densities.
+__device__ __forceinline__ RateTerm rate_term(float v, float mu, float sabs, float half, float gsign,
+                                              bool fused_pdf_diff = false) {
   const float inv_ln2 = 1.4426950408889634f;
   float up = (v - mu + half) / sabs, lo = (v - mu - half) / sabs;
   float like = std_cdf(up) - std_cdf(lo);
@@ -38,7 +44,14 @@ __device__ __forceinline__ RateTerm rate_term(float v, float mu, float sabs, flo
   bool pass = (like >= 1e-8f) || (gsign * dbits_dlike < 0.f);
   if (!pass) dbits_dlike = 0.f;
   float pu = std_pdf(up), pl = std_pdf(lo);
-  r.dv = dbits_dlike * (pu - pl) / sabs;
+  float dpdf;
+  if (fused_pdf_diff) {
+    dpdf = fmaf(0.3989422804014327f, expf(-0.5f * up * up), -pl);
+  } else {
+#pragma clang fp contract(off)
+    dpdf = pu - pl;
+  }
+  r.dv = dbits_dlike * dpdf / sabs;
   r.dmu = -r.dv;
   r.dsig = dbits_dlike * (-(pu * up - pl * lo) / sabs);
   return r;
@@ -90,7 +103,7 @@ __device__ __forceinline__ void latent_rate_body(const float* __restrict__ x, co
         }
         v = xv + (uu - 0.5f);
       }
-      RateTerm r = rate_term(v, m, sabs, 0.5f, gsign);
+      RateTerm r = rate_term(v, m, sabs, 0.5f, gsign, true);
       tb_[p] = r.bits;
       tb_[cn + p] = r.dsig;
       tb_[2 * cn + p] = r.dmu;
@@ -157,7 +170,7 @@ __device__ __forceinline__ void latent_rate_body(const float* __restrict__ x, co
           }
           v = xv + (uu - 0.5f);
         }
-        RateTerm r = rate_term(v, m, sabs, 0.5f, gsign);
+        RateTerm r = rate_term(v, m, sabs, 0.5f, gsign, true);
         sb += r.bits;
         ss += r.dsig;
         sm_ += r.dmu;

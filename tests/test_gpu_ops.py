@@ -282,11 +282,12 @@ def test_three_mfma_weight_gradients_in_one_launch(ops):
             assert torch.equal(got, ref)
 
 
-@pytest.mark.parametrize("mode,c", [("train", 3), ("eval", 8)])
-def test_latent_fwd_equals_the_three_kernels(ops, mode, c):
-    """nvf_latent_fwd = conv1x1 + GDN + quantiser/rate: every output bit-identical to the separate launches."""
+@pytest.mark.parametrize("mode,c,B", [pytest.param("train", 3, 5, id="train-3"), pytest.param("eval", 8, 5, id="eval-8"),
+                                      ("eval", 8, 17), ("train", 3, 47)])
+def test_latent_fwd_equals_the_three_kernels(ops, mode, c, B):
+    """nvf_latent_fwd = conv1x1 + GDN + quantiser/rate: every output bit-identical to the separate launches.  17 blocks
+    at c = 8 and 47 at c = 3 are one past the mini-batch (LDS) path of both the fused forward and nvf_latent_rate."""
     g = gen(7200 + c)
-    B = 5
     e = dev(1.0 + 0.5 * torch.randn(B, c, 2, 2, 2, generator=g))
     w = torch.randn(c, c, 1, 1, 1, generator=g) * 0.5
     b = dev(torch.randn(c, generator=g) * 0.1)
@@ -294,7 +295,7 @@ def test_latent_fwd_equals_the_three_kernels(ops, mode, c):
     gamma = dev(0.3 * torch.rand(c, c, generator=g))
     sigma, mu = dev(0.5 + torch.rand(c, generator=g)), dev(torch.randn(c, generator=g) * 0.1)
     wf, _ = ops.pack_conv_weight(dev(w))
-    ids = dev(torch.tensor([7, 3, 11, 0, 5]))
+    ids = dev(torch.tensor([7, 3, 11, 0, 5]) if B == 5 else 2 * torch.randperm(B, generator=g) + 1)
     h, lat, xr, bits = ops.latent_fwd(e, wf, b, beta, gamma, sigma, mu, mode, block_ids=ids, seed=9, step=4)
     h2 = ops.conv3d_gather(e, wf, b, c, 1, 1, 0, (2, 2, 2))
     lat2 = ops.gdn_fwd(h2, beta, gamma, False)
