@@ -22,8 +22,11 @@ engine (nvfpcc_amd/engine.py) instead of a DataLoader + autograd loop.
     python NVFPCC.py encode ... --lossless_lod                                 # the occupancy coarse to fine (lossless_lod_pack)
     python NVFPCC.py encode ... --lossless_lod --lossless_ctx nbr              # the voxels under their parents' neighbours
     python NVFPCC.py decode pack.pk --lossless_lod 0|1|2 ...                   # exact at 32^3, 16^3 or 8^3 per block
+    python NVFPCC.py train seq_%04d.ply --gof 8 --frame_start 1300 ...         # one decoder for frames 1300 .. 1307
+    python NVFPCC.py encode seq_%04d.ply --gof 8 --frame_start 1300 ...        # one pack: the weights once, a frame pack each
+    python NVFPCC.py decode pack.pk --frame 1303 ...                           # that frame alone; without --frame, all of them
 
-Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --ply_format, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --lossless_lod, --lossless_ctx, --thh_mode (count | block-count | d1:
+Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --ply_format, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --lossless_lod, --lossless_ctx, --gof, --frame_start, --frame, --thh_mode (count | block-count | d1:
 nvfpcc_amd/thh_select.py picks the occupancy threshold at encode time and a `thh_pack` key carries it); multi-GPU training when launched
 through torch.distributed.run (one process per GPU, leaf blocks sharded, one RCCL all-reduce per step).
 Headless: no GUI window, no IPython shell.
@@ -102,19 +105,48 @@ def _load_data(args, dev, shuffle=True):
     pre-processed on the device (nothing is read from or written to disk besides the PLY).  -> (dataset, the
     DevicePreprocess or None)."""
     from nvfpcc_amd.dataloader import LoadedVoxelDataset
-    if getattr(args, 'from_ply', False):
-        from nvfpcc_amd import ply_io, preprocess as pp
-        pre = pp.preprocess_device(ply_io.read_ply(args.input, device=dev)[0], dev, bits=getattr(args, 'bits', 10))
-        return LoadedVoxelDataset.from_device(pre, shuffle=shuffle), pre
-    fid = args.input[:-4]
-    return LoadedVoxelDataset(f'{fid}_l5_origins.npy', f'{fid}_l5_gt_grid.npy', f'{fid}_l5_dist.npy',
-                              shuffle=shuffle), None
+
+    def one(name):
+        if getattr(args, 'from_ply', False):
+            from nvfpcc_amd import ply_io, preprocess as pp
+            pre = pp.preprocess_device(ply_io.read_ply(name, device=dev)[0], dev, bits=getattr(args, 'bits', 10))
+            return LoadedVoxelDataset.from_device(pre, shuffle=shuffle), pre
+        fid = name[:-4]
+        return LoadedVoxelDataset(f'{fid}_l5_origins.npy', f'{fid}_l5_gt_grid.npy', f'{fid}_l5_dist.npy',
+                                  shuffle=shuffle), None
+    if hasattr(args, 'gof'):    # the frames' blocks, frame-major, as one dataset; its frame(k) carries frame k's `pre`
+        from nvfpcc_amd import gof
+        frames, pres = zip(*[gof.quiet(one, name) for name in _gof_names(args)])
+        return gof.GofDataset(frames, shuffle=shuffle, pres=pres), None
+    return one(args.input)
+
+
+def _gof_names(args):
+    """--gof F [--frame_start S] of train / encode: `input` is the pattern of the frames' names.  -> the F names, or None
+    without --gof.  Checked by nvfpcc_amd.gof.frame_names, and so is a --ref_ply pattern: what is wrong exits here, with
+    its reason, before any GPU work."""
+    if not hasattr(args, 'gof'):
+        if hasattr(args, 'frame_start'):
+            raise SystemExit(f"--frame_start {args.frame_start} numbers the frames of --gof; give --gof too")
+        return None
+    from nvfpcc_amd import gof
+    start = getattr(args, 'frame_start', 0)
+    try:
+        if args.input is None:
+            raise ValueError("no input: --gof takes the pattern of the frames' names, such as seq_%04d.ply")
+        names = gof.frame_names(args.input, start, args.gof, None if getattr(args, 'from_ply', False) else gof.npy_triple)
+        if args.ref_ply is not None:
+            gof.frame_names(args.ref_ply, start, args.gof)
+    except ValueError as e:
+        raise SystemExit(f"--gof {args.gof}: {e}")
+    return names
 
 
 def train(args):
     from nvfpcc_amd import dist as nd, ops
     from nvfpcc_amd.engine import TrainEngine, EpochDriver
     peak = (1 << _bits(args)) - 1
+    _gof_names(args)
     dev, rank, world = _device(args)
     say = print if rank == 0 else (lambda *a, **k: None)
     say(f'Rate loss = {args.w1} * b1 + b2 + {args.w2} * b3')
@@ -141,7 +173,7 @@ def train(args):
         nsteps = driver.run(order, q)
         # latent update on this rank's shard (every rank advances the noise counter), then re-synchronise the table
         if hi > lo:
-            eng.latent_step(q, lo, hi)
+            eng.latent_step_chunked(q, lo, hi)      # (a group of frames can hold more blocks than one pass should)
         else:
             eng.noise_step += 1
         nd.allgather_rows_(eng.emb, rank, world)
@@ -203,20 +235,73 @@ TEST_LINE = ('[Epoch %04d TEST %.1f seconds] Loss: %.4e PosiPenal: %.4f PosiGain
 
 def encode(args):
     """Pack everything the decoder needs (NVFPCC.py:395-554)."""
-    from nvfpcc_amd import ops, weight_codec, latent_codec
-    from nvfpcc_amd import ply_io
-    from nvfpcc_amd.recon import reconstruct_points
+    from nvfpcc_amd import weight_codec
     lossless_ctx_refusals(args)
     bits = _bits(args)
+    names = _gof_names(args)
     fmt = getattr(args, 'ply_format', 'ascii')
     dev, rank, world = _device(args)
     data, pre = _load_data(args, dev, shuffle=False)
     net = _build_net(args, dev)
     net_weight_pack = weight_codec.enc_dec_from_file(args.load_weights, qp=int(args.qp))
-    net_bits = len(net_weight_pack['bit_stream']) * 8
     d = torch.load(args.load_weights, map_location=dev)
     net.load_state_dict({k: v for k, v in d.items() if 'init_coords' not in k}, strict=False)
     emb = torch.load(args.load_emb, map_location=dev).to(dev).float().contiguous()
+    if names is not None:
+        return _encode_gof(args, net, net_weight_pack, emb, data, dev, bits, fmt)
+
+    def write(frame_pack):
+        with open(args.pack_fn, 'wb') as f:
+            pickle.dump({'net_weight_pack': net_weight_pack, **frame_pack}, f)
+    _encode_frame(args, net, net_weight_pack, emb, data, pre, dev, bits, fmt, 'rc_enc', write)
+
+
+def _encode_gof(args, net, net_weight_pack, emb, data, dev, bits, fmt):
+    """encode --gof: every frame through _encode_frame with its rows of --load_emb, into one pack
+    (nvfpcc_amd.gof: the weights once, gof_pack, a frame pack each)."""
+    import contextlib
+    import io
+    from nvfpcc_amd import gof
+    start = getattr(args, 'frame_start', 0)
+    if emb.shape[0] != data.N_leaf:
+        raise SystemExit(f"encode --gof {args.gof}: {args.load_emb} holds {emb.shape[0]} rows, the group's frames "
+                         f"{data.N_leaf} leaf blocks")
+    frames = []
+    for k in range(len(data.frame_points)):
+        number = start + k
+        lo, hi = int(data.frame_ranges[k]), int(data.frame_ranges[k + 1])
+        fargs = argparse.Namespace(**vars(args))
+        fargs.ref_ply = None if args.ref_ply is None else args.ref_ply % number
+        lines = io.StringIO()       # the frame's lines follow its [Frame] line, whose numbers they come before
+        try:
+            with contextlib.redirect_stdout(lines):
+                view = data.frame(k)
+                frame_pack, report = _encode_frame(fargs, net, net_weight_pack, emb[lo:hi].contiguous(), view, view.pre, dev,
+                                                   bits, fmt, 'rc_enc_%04d' % number, None)
+        except BaseException:
+            print(lines.getvalue(), end='')
+            raise
+        print(gof.frame_line(number, report['points'], report['blocks'], report['latent_bits'], report['side_bits']))
+        print(lines.getvalue(), end='')
+        frames.append(frame_pack)
+    total_pack = {'net_weight_pack': net_weight_pack,
+                  'gof_pack': gof.write_gof_pack(start, np.diff(data.frame_ranges), data.frame_points), 'frames': frames}
+    with open(args.pack_fn, 'wb') as f:
+        pickle.dump(total_pack, f)
+    for line in gof.gof_lines(total_pack):
+        print(line)
+
+
+def _encode_frame(args, net, net_weight_pack, emb, data, pre, dev, bits, fmt, stem, write_pack):
+    """Code one frame: the latents `emb` of its blocks under `net` (whose bytes are `net_weight_pack`), the side packs
+    the flags ask for, and its reconstruction into `stem`.ply (and `stem`_lod1.ply / _lod2.ply).  write_pack(frame_pack)
+    is called as soon as the pack is complete, before the reconstruction; None: the frame belongs to a group, nothing
+    is written and its Gross bpp line is the group's.  -> (frame_pack: the plain pack without net_weight_pack, report:
+    {'points', 'blocks', 'latent_bits', 'side_bits'})."""
+    from nvfpcc_amd import ops, latent_codec
+    from nvfpcc_amd import ply_io
+    from nvfpcc_amd.recon import reconstruct_points
+    net_bits = len(net_weight_pack['bit_stream']) * 8
     np_origins = np.array([data.origins[i] for i in range(len(data))], dtype=np.int16)
     with torch.no_grad():
         info = net.get_latent_code(emb)
@@ -246,8 +331,9 @@ def encode(args):
     if getattr(args, 'lossless_lod', None) is not None:     # the same occupancy coarse to fine: exact at 8^3, 16^3, 32^3
         lossless_lod = _encode_lossless_lod(args, total_pack, data, dev, batch)
         total_pack['lossless_lod_pack'] = lossless_lod['pack']
-    with open(args.pack_fn, 'wb') as f:
-        pickle.dump(total_pack, f)
+    frame_pack = {k: v for k, v in total_pack.items() if k != 'net_weight_pack'}
+    if write_pack is not None:
+        write_pack(frame_pack)
     print('Start to reconstruct')
     pts, counts = reconstruct_points(net, info['quantized_latent'].detach(), np_origins, thh, batch=batch)
     gt, dist = data.to_device(dev)
@@ -267,19 +353,21 @@ def encode(args):
     side_bits += 8 * len(total_pack.get('lossless_lod_pack', b''))
     if sel is not None:
         print(sel['line'])
-    print('[Latent code] Gross bpp: %.4f' % ((latent_bits + net_bits + side_bits) / data.N))
+    if write_pack is not None:
+        print('[Latent code] Gross bpp: %.4f' % ((latent_bits + net_bits + side_bits) / data.N))
     print('[Recon] Pacc: %.4f Nacc: %.4f MSE1: %.4f PSNR1: %.4f' % (
         m[0] / max(m[1], 1), m[2] / max(m[3], 1), *_psnr1(m[4], m[5], (1 << bits) - 1)))
-    ply_io.write_ply('rc_enc.ply', pts, fmt=fmt, device=dev)
+    ply_io.write_ply(stem + '.ply', pts, fmt=fmt, device=dev)
     _print_pc_error(args, pts, dev)
     if lod is not None:
         for level, (line, lod_pts) in enumerate(zip(lod['lines'], lod['points']), 1):
             print(line)
-            ply_io.write_ply('rc_enc_lod%d.ply' % level, lod_pts, fmt=fmt, device=dev)
+            ply_io.write_ply(stem + '_lod%d.ply' % level, lod_pts, fmt=fmt, device=dev)
     if lossless is not None:
         print(lossless['line'])
     if lossless_lod is not None:
         print(lossless_lod['line'])
+    return frame_pack, {'points': int(data.N), 'blocks': int(data.N_leaf), 'latent_bits': latent_bits, 'side_bits': side_bits}
 
 
 def _encode_lossless(args, total_pack, data, dev, batch):
@@ -395,9 +483,6 @@ def _select_threshold(mode, net, latents, data, origins, dev, batch):
 
 def decode(args):
     """Decode from a pack (NVFPCC.py:557-652)."""
-    from nvfpcc_amd import weight_codec, latent_codec
-    from nvfpcc_amd import ply_io
-    from nvfpcc_amd.recon import reconstruct_points
     lossless_refusals(args, None)
     lossless_lod_refusals(args, None)
     fmt = getattr(args, 'ply_format', 'ascii')
@@ -405,6 +490,58 @@ def decode(args):
     net = _build_net(args, torch.device('cpu'))
     with open(args.input, 'rb') as f:
         total_pack = pickle.load(f)
+    if 'gof_pack' in total_pack:            # a group of frames: --frame K alone, or every frame
+        return _decode_gof(args, total_pack, dev, fmt, net)
+    if hasattr(args, 'frame'):
+        raise SystemExit(f"decode --frame {args.frame}: {args.input} carries no gof_pack (it holds one cloud, encoded "
+                         f"without --gof)")
+    _decode_pack(args, total_pack, dev, fmt, net, 'rc_dec.ply')
+
+
+def _decode_gof(args, total_pack, dev, fmt, net):
+    """decode of a group (nvfpcc_amd.gof): frame K - start with --frame K into rc_dec.ply, else every frame into
+    rc_dec_%04d.ply, each as the plain pack gof.extract makes of it -- nothing of another frame is read or run.  --N is
+    ignored: a frame's own origins or octree give its count.  A frame that cannot be decoded is named; the others of a
+    whole-group decode are still written and the exit status is non-zero."""
+    from nvfpcc_amd import gof
+    try:
+        info = gof.read_gof_pack(total_pack['gof_pack'])
+        start, F = info['start'], len(info['n_leaf'])
+        if hasattr(args, 'frame'):
+            if not start <= args.frame < start + F:
+                raise ValueError(f"--frame {args.frame} is outside the group's frames {start} .. {start + F - 1}")
+            numbers = [args.frame]
+        else:
+            numbers = list(range(start, start + F))
+            if args.ref_ply is not None:
+                gof.frame_names(args.ref_ply, start, F)
+    except ValueError as e:
+        raise SystemExit(f"decode {args.input}: {e}")
+    failed = []
+    for number in numbers:
+        fargs = argparse.Namespace(**vars(args))
+        try:
+            pack = gof.extract(total_pack, number - start)
+            fargs.N = gof.frame_leaves(pack)
+            if args.ref_ply is not None and not hasattr(args, 'frame'):
+                fargs.ref_ply = args.ref_ply % number
+            if len(numbers) > 1:
+                print('[Frame %04d]' % number)
+            _decode_pack(fargs, pack, dev, fmt, net, 'rc_dec.ply' if hasattr(args, 'frame') else 'rc_dec_%04d.ply' % number)
+        except (SystemExit, ValueError, RuntimeError, IndexError, KeyError, EOFError) as e:
+            if hasattr(args, 'frame'):
+                raise SystemExit(f"decode {args.input}: frame {number:04d}: {e}")
+            failed.append('%04d' % number)
+            print(f"decode {args.input}: frame {number:04d}: {e}")
+        net = None                          # the next frame gets a decoder of its own
+    if failed:
+        raise SystemExit(f"decode {args.input}: {len(failed)} of {F} frames could not be decoded: {' '.join(failed)}")
+
+
+def _decode_pack(args, total_pack, dev, fmt, net, out_fn):
+    """One plain pack into the cloud `out_fn`.  net: a fresh Net on the host, or None to build one."""
+    from nvfpcc_amd import ply_io
+    from nvfpcc_amd.recon import reconstruct_points
     lossless_refusals(args, total_pack)
     lossless_lod_refusals(args, total_pack)
     lod, lod_side = getattr(args, 'lod', 0), None
@@ -434,7 +571,7 @@ def decode(args):
             raise SystemExit(f"decode --lossless: {e}")
         pts = lp.points_from_words(words, counts, origins)
         print('[Lossless] points: %d' % pts.shape[0])
-        ply_io.write_ply('rc_dec.ply', pts, fmt=fmt, device=dev)
+        ply_io.write_ply(out_fn, pts, fmt=fmt, device=dev)
         _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10)
         return
     if getattr(args, 'lossless_lod', None) is not None:     # the input's voxels, or their exact 2^3 / 4^3 max-pool
@@ -448,7 +585,7 @@ def decode(args):
             raise SystemExit(f"decode --lossless_lod {level}: {e}")
         pts = llp.points_from_words(words, counts, origins, level)
         print('[LosslessLoD] level: %d points: %d' % (level, pts.shape[0]))
-        ply_io.write_ply('rc_dec.ply', pts, fmt=fmt, device=dev)
+        ply_io.write_ply(out_fn, pts, fmt=fmt, device=dev)
         _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10, lod=level)
         return
     if lod_side is not None:                # a coarser level of detail: the trunk stops at the level's head
@@ -457,7 +594,7 @@ def decode(args):
         pts, counts = reconstruct_points_lod(net, latents[:n].contiguous(), origins, lod, t,
                                              batch=max(int(args.batchsize), 1))
         print(lp.lod_line(lod, t, pts.shape[0]))
-        ply_io.write_ply('rc_dec.ply', pts, fmt=fmt, device=dev)
+        ply_io.write_ply(out_fn, pts, fmt=fmt, device=dev)
         _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10, lod=lod)
         return
     thh, block_counts, used = args.thh, None, []
@@ -477,7 +614,7 @@ def decode(args):
                                      batch=max(int(args.batchsize), 1), block_counts=block_counts, thh_out=used)
     if block_counts is not None:
         print(ts.threshold_line('block-count', block_counts=block_counts, thresholds=torch.cat(used).cpu().numpy()))
-    ply_io.write_ply('rc_dec.ply', pts, fmt=fmt, device=dev)
+    ply_io.write_ply(out_fn, pts, fmt=fmt, device=dev)
     _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10)
 
 
@@ -646,6 +783,15 @@ def build_parser():
                    help='encode --lossless_lod: the contexts of the voxels.  field (the default): the decoder\'s field '
                         'alone.  nbr: also the exact 16^3 occupancy of the parent cell\'s neighbours, which the decoder '
                         'holds before the first voxel (fewer bits; decode tells the two apart by the pack).')
+    p.add_argument('--gof', type=int, default=argparse.SUPPRESS,
+                   help='train / encode: a group of F frames under one decoder.  `input` is then the pattern of their '
+                        'names with one %%d or %%0<n>d (seq_%%04d.ply); the frames are numbered from --frame_start.  encode '
+                        'writes one pack (the weights once, a frame pack each) and rc_enc_<number>.ply per frame.')
+    p.add_argument('--frame_start', type=int, default=argparse.SUPPRESS,
+                   help='train / encode --gof: number of the first frame (0 when absent).')
+    p.add_argument('--frame', type=int, default=argparse.SUPPRESS,
+                   help='decode of a group: the frame of that number alone, into rc_dec.ply; nothing of another frame is '
+                        'read.  Absent: every frame, into rc_dec_<number>.ply (--ref_ply is then a pattern too).')
     p.add_argument('--ply_format', choices=['ascii', 'binary'], default=argparse.SUPPRESS,
                    help='encode / decode: format of the rc_*.ply files written.  ascii (also when absent): double x y z '
                         'as text; binary: binary_little_endian with float x y z.')

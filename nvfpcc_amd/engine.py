@@ -44,6 +44,9 @@ _STEM_IN_TRUNK5 = True
 # derive their weights from the raw parameters, so the two latency-bound launches have nothing to wait for in each other
 _STEM_IN_HEAD = True
 _HEADS_IN_TRUNK5 = True     # heads' weight gradients as workgroups of the five-gradient launch (narrow decoder)
+# Most blocks one full-batch pass (latent step, evaluation) holds resident: the largest batch these passes have been
+# run and measured at (tools/latent4096.py).  A larger shard -- a group of frames -- is walked in chunks of this size.
+LATENT_CHUNK = 4096
 
 
 class StepPlan(NamedTuple):
@@ -879,18 +882,46 @@ class TrainEngine:
         """Full-batch latent update over blocks [lo, hi) (NVFPCC.py:225-251); no weight gradients."""
         hi = self.N_leaf if hi is None else hi
         self.noise_step += 1
+        self.prepare_weights(q)
+        a, de = self._latent_grad(lo, hi)
+        if update:
+            self._latent_update(lo, hi, de)
+        return a, de
+
+    def _latent_grad(self, lo, hi):
+        """Forward and latent gradient of blocks [lo, hi) at the noise counter and the effective weights as they stand.
+        The noise of a block is keyed by its absolute id (block_ids), not by its place in the batch, and every loss term
+        is a sum over blocks: the rows of `de` do not depend on which other blocks share the pass."""
         ids = torch.arange(lo, hi, device=self.dev)
         n_pts = float(self.counts.sum())          # the reference divides by the points of ALL blocks
-        self.prepare_weights(q)
-        e = self.emb[lo:hi]
-        a = self.forward(e, "train", ids)
+        a = self.forward(self.emb[lo:hi], "train", ids)
         de = self.backward(a, self.gt[lo:hi], self.dist[lo:hi], self.gt16[lo:hi], self.gt8[lo:hi], n_pts, "train",
                            ids, want_w=False, want_emb=True)
-        if update:
-            ops.adam_step(self.emb[lo:hi].view(-1), de.view(-1), self.emb_m[lo:hi].view(-1),
-                          self.emb_v[lo:hi].view(-1), self.lr_emb, self.emb_step + 1)
-            self.emb_step += 1
         return a, de
+
+    def _latent_update(self, lo, hi, de):
+        ops.adam_step(self.emb[lo:hi].view(-1), de.view(-1), self.emb_m[lo:hi].view(-1),
+                      self.emb_v[lo:hi].view(-1), self.lr_emb, self.emb_step + 1)
+        self.emb_step += 1
+
+    @_abandons_step
+    def latent_step_chunked(self, q, lo=0, hi=None, chunk=LATENT_CHUNK, update=True):
+        """latent_step(q, lo, hi) with at most `chunk` blocks resident at a time: ONE draw of the noise counter, ONE
+        prepare_weights and ONE Adam step number for all of [lo, hi), n_pts the points of ALL blocks, the forward and
+        backward chunk by chunk (a group of frames multiplies the block count; the activations of a pass grow with
+        it).  hi - lo <= chunk: latent_step itself.  Returns the latent gradient of [lo, hi)."""
+        hi = self.N_leaf if hi is None else hi
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError(f"latent_step_chunked: chunk = {chunk}")
+        if hi - lo <= chunk:
+            return self.latent_step(q, lo, hi, update)[1]
+        self.noise_step += 1
+        self.prepare_weights(q)
+        de = torch.cat([self._latent_grad(c, min(c + chunk, hi))[1] for c in range(lo, hi, chunk)], 0)
+        if update:
+            self._latent_update(lo, hi, de)     # after the last chunk: no chunk sees rows another one has moved
+        return de
 
     @_abandons_step
     def eval_forward(self, lo=0, hi=None, q=2):
@@ -905,6 +936,11 @@ class TrainEngine:
         SUM over blocks, so a rank evaluates its contiguous shard and ONE all-reduce of these 22 floats gives the
         full-batch numbers (eval shards contiguously; the reference evaluates on one device)."""
         hi = self.N_leaf if hi is None else hi
+        if hi - lo > LATENT_CHUNK:          # a shard beyond one resident pass: the 22 sums chunk by chunk, added in float64
+            tot = torch.zeros(22, device=self.dev, dtype=torch.float64)
+            for c in range(lo, hi, LATENT_CHUNK):
+                tot += self.eval_sums(c, min(c + LATENT_CHUNK, hi), q).double()
+            return tot.float()
         out = torch.zeros(22, device=self.dev)
         if hi <= lo:
             return out
