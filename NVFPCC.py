@@ -300,7 +300,7 @@ def _encode_frame(args, net, net_weight_pack, emb, data, pre, dev, bits, fmt, st
     {'points', 'blocks', 'latent_bits', 'side_bits'})."""
     from nvfpcc_amd import ops, latent_codec
     from nvfpcc_amd import ply_io
-    from nvfpcc_amd.recon import reconstruct_points
+    from nvfpcc_amd.recon import eval_batches, reconstruct_points
     net_bits = len(net_weight_pack['bit_stream']) * 8
     np_origins = np.array([data.origins[i] for i in range(len(data))], dtype=np.int16)
     with torch.no_grad():
@@ -338,8 +338,7 @@ def _encode_frame(args, net, net_weight_pack, emb, data, pre, dev, bits, fmt, st
     pts, counts = reconstruct_points(net, info['quantized_latent'].detach(), np_origins, thh, batch=batch)
     gt, dist = data.to_device(dev)
     with torch.no_grad():
-        out = torch.cat([net.reconstruct(info['quantized_latent'][i:i + 64].contiguous(), 2)
-                         for i in range(0, len(data), 64)], 0)
+        out = torch.cat([o for _, _, o in eval_batches(net, info['quantized_latent'], 64)], 0)
     if isinstance(thh, torch.Tensor):       # one threshold per block: the six sums block by block
         m = torch.zeros(6, device=dev)
         for b, t in enumerate(thh.tolist()):
@@ -425,7 +424,7 @@ def _encode_lod(args, net, latents, data, origins, dev, batch):
     threshold of each level chosen by count against the max-pooled ground truth, and the level's cloud through
     ops.head_points.  -> {'pack': lod_pack bytes, 'lines': the two [LoD l] lines, 'points': the two clouds}."""
     from nvfpcc_amd import lod_pack as lp, ops, thh_select as ts
-    from nvfpcc_amd.recon import reconstruct_points_lod
+    from nvfpcc_amd.recon import eval_batches, reconstruct_points_lod
     src = getattr(args, 'lod_heads', None) or args.load_weights
     try:
         heads = lp.head_tensors(torch.load(src, map_location='cpu'))
@@ -443,8 +442,7 @@ def _encode_lod(args, net, latents, data, origins, dev, batch):
         g = ops.maxpool2(g.contiguous())
         k = int((g != 0).sum().item())      # occupied coarse voxels of the input
         with torch.no_grad():
-            p = torch.cat([net.reconstruct_lod(latents[i:i + batch].contiguous(), level, 2, return_p=True)[1]
-                           for i in range(0, latents.shape[0], batch)], 0)
+            p = torch.cat([o[1] for _, _, o in eval_batches(net, latents, batch, level, return_p=True)], 0)
         t = float(ts.threshold_for_count(p, k).item())
         m = ops.metrics(p, g, None, t, t).cpu().numpy()
         pts, _ = reconstruct_points_lod(net, latents, origins, level, t, batch=batch)
@@ -459,10 +457,10 @@ def _select_threshold(mode, net, latents, data, origins, dev, batch):
     """--thh_mode count | block-count | d1 at the encoder: the eval forward of every block stays resident and
     nvfpcc_amd.thh_select picks the threshold(s).  -> {'t': float | tensor [N_leaf], 'pack': bytes, 'line': str}."""
     from nvfpcc_amd import thh_select as ts
+    from nvfpcc_amd.recon import eval_batches
     ts.check_resident(latents.shape[0])
     with torch.no_grad():
-        p_all = torch.cat([net.reconstruct(latents[i:i + batch].contiguous(), 2)
-                           for i in range(0, latents.shape[0], batch)], 0)
+        p_all = torch.cat([o for _, _, o in eval_batches(net, latents, batch)], 0)
     k_b = data.gt_grid.reshape(data.N_leaf, -1).astype(bool).sum(1)
     if mode == 'block-count':
         sel = ts.choose(mode, p_all, block_counts=k_b)
@@ -541,7 +539,7 @@ def _decode_gof(args, total_pack, dev, fmt, net):
 def _decode_pack(args, total_pack, dev, fmt, net, out_fn):
     """One plain pack into the cloud `out_fn`.  net: a fresh Net on the host, or None to build one."""
     from nvfpcc_amd import ply_io
-    from nvfpcc_amd.recon import reconstruct_points
+    from nvfpcc_amd.recon import reconstruct_points, reconstruct_points_lod
     lossless_refusals(args, total_pack)
     lossless_lod_refusals(args, total_pack)
     lod, lod_side = getattr(args, 'lod', 0), None
@@ -562,60 +560,49 @@ def _decode_pack(args, total_pack, dev, fmt, net, out_fn):
         n = int(args.N)
         origins = total_pack['origins'][:n]
     print('Start to reconstruct')
+    latents, batch, level = latents[:n].contiguous(), max(int(args.batchsize), 1), 0
     if getattr(args, 'lossless', False):    # the input's own voxels: the occupancy words decoded under the field
         from nvfpcc_amd import lossless_pack as lp
         try:
-            words, counts = lp.decode_occupancy(net, latents[:n].contiguous(), total_pack['lossless_pack'],
-                                                batch=max(int(args.batchsize), 1))
+            words, counts = lp.decode_occupancy(net, latents, total_pack['lossless_pack'], batch=batch)
         except ValueError as e:
             raise SystemExit(f"decode --lossless: {e}")
         pts = lp.points_from_words(words, counts, origins)
         print('[Lossless] points: %d' % pts.shape[0])
-        ply_io.write_ply(out_fn, pts, fmt=fmt, device=dev)
-        _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10)
-        return
-    if getattr(args, 'lossless_lod', None) is not None:     # the input's voxels, or their exact 2^3 / 4^3 max-pool
+    elif getattr(args, 'lossless_lod', None) is not None:   # the input's voxels, or their exact 2^3 / 4^3 max-pool
         from nvfpcc_amd import lossless_nbr_pack
         level = int(args.lossless_lod)
         try:
             llp = lossless_nbr_pack.module_of(total_pack['lossless_lod_pack'])     # byte 0: which contexts coded it
-            words, counts = llp.decode_occupancy(net, latents[:n].contiguous(), total_pack['lossless_lod_pack'], level=level,
-                                                 batch=max(int(args.batchsize), 1))
+            words, counts = llp.decode_occupancy(net, latents, total_pack['lossless_lod_pack'], level=level, batch=batch)
         except ValueError as e:
             raise SystemExit(f"decode --lossless_lod {level}: {e}")
         pts = llp.points_from_words(words, counts, origins, level)
         print('[LosslessLoD] level: %d points: %d' % (level, pts.shape[0]))
-        ply_io.write_ply(out_fn, pts, fmt=fmt, device=dev)
-        _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10, lod=level)
-        return
-    if lod_side is not None:                # a coarser level of detail: the trunk stops at the level's head
-        from nvfpcc_amd.recon import reconstruct_points_lod
-        t = lod_side['t'][lod - 1]
-        pts, counts = reconstruct_points_lod(net, latents[:n].contiguous(), origins, lod, t,
-                                             batch=max(int(args.batchsize), 1))
+    elif lod_side is not None:              # a coarser level of detail: the trunk stops at the level's head
+        level, t = lod, lod_side['t'][lod - 1]
+        pts, counts = reconstruct_points_lod(net, latents, origins, lod, t, batch=batch)
         print(lp.lod_line(lod, t, pts.shape[0]))
-        ply_io.write_ply(out_fn, pts, fmt=fmt, device=dev)
-        _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10, lod=lod)
-        return
-    thh, block_counts, used = args.thh, None, []
-    side = total_pack.get('thh_pack')
-    if side is None and args.thh_mode not in (None, 'fixed'):
-        raise SystemExit(f"decode --thh_mode {args.thh_mode}: {args.input} carries no thh_pack (it was encoded without "
-                         f"--thh_mode); decode it with --thh instead")
-    if side is not None and args.thh_mode != 'fixed':
-        from nvfpcc_amd import thh_select as ts
-        mode, value = ts.read_thh_pack(side)
-        if mode == 'block-count':
-            block_counts = value[:n]
-        else:
-            thh = value
-            print(ts.threshold_line(mode, t=thh))
-    pts, counts = reconstruct_points(net, latents[:n].contiguous(), origins, thh,
-                                     batch=max(int(args.batchsize), 1), block_counts=block_counts, thh_out=used)
-    if block_counts is not None:
-        print(ts.threshold_line('block-count', block_counts=block_counts, thresholds=torch.cat(used).cpu().numpy()))
+    else:
+        thh, block_counts, used = args.thh, None, []
+        side = total_pack.get('thh_pack')
+        if side is None and args.thh_mode not in (None, 'fixed'):
+            raise SystemExit(f"decode --thh_mode {args.thh_mode}: {args.input} carries no thh_pack (it was encoded "
+                             f"without --thh_mode); decode it with --thh instead")
+        if side is not None and args.thh_mode != 'fixed':
+            from nvfpcc_amd import thh_select as ts
+            mode, value = ts.read_thh_pack(side)
+            if mode == 'block-count':
+                block_counts = value[:n]
+            else:
+                thh = value
+                print(ts.threshold_line(mode, t=thh))
+        pts, counts = reconstruct_points(net, latents, origins, thh, batch=batch, block_counts=block_counts, thh_out=used)
+        if block_counts is not None:
+            print(ts.threshold_line('block-count', block_counts=block_counts, thresholds=torch.cat(used).cpu().numpy()))
     ply_io.write_ply(out_fn, pts, fmt=fmt, device=dev)
-    _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins) if args.ref_ply is not None else 10)
+    if args.ref_ply is not None:
+        _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins), lod=level)
 
 
 def _decoder_from_pack(args, total_pack, dev, net=None, lod_side=None):

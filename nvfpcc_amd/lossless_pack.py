@@ -196,12 +196,6 @@ def _span(batch, group, span_groups):
     return max(int(batch) // int(group), int(span_groups), 1) * int(group)
 
 
-def _forward(net, latents, lo, hi, batch):
-    """p of blocks lo..hi, the forward in calls of `batch` blocks (batch-invariant: the same bits at any batch)."""
-    parts = [net.reconstruct(latents[i:min(i + batch, hi)].contiguous(), 2) for i in range(lo, hi, batch)]
-    return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
-
-
 def span_args(kind, latents, gt, batch, group, span_groups):
     """What both encoders check first -> (N, batch, group, blocks per coder launch)."""
     N, batch, group = latents.shape[0], max(int(batch), 1), int(group)
@@ -213,10 +207,12 @@ def span_args(kind, latents, gt, batch, group, span_groups):
 
 
 def spans(net, latents, gt, batch, span):
-    """Span by span (p, the span's ground truth or None): one pass of the forward over the cloud."""
+    """Span by span (p, the span's ground truth or None): one pass of the forward over the cloud, `batch` blocks a call."""
+    from .recon import eval_batches
     for lo in range(0, latents.shape[0], span):
         hi = min(lo + span, latents.shape[0])
-        yield _forward(net, latents, lo, hi, batch), None if gt is None else gt[lo:hi].contiguous()
+        parts = [p for _, _, p in eval_batches(net, latents[lo:hi], batch)]
+        yield parts[0] if len(parts) == 1 else torch.cat(parts, 0), None if gt is None else gt[lo:hi].contiguous()
 
 
 def encode_spans(net, latents, gt, batch, span, code):

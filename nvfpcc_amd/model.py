@@ -24,8 +24,8 @@ class Net(nn.Module):
         return out, out_cls_list, net_bits, latent_likelihood
 
     def reconstruct(self, latent, q):
-        out, _, _ = self.reconstructor(latent, q)
-        return out
+        """The occupancy probabilities alone (CompDecoder.forward_out): no coarse head, no weight rate."""
+        return self.reconstructor.forward_out(latent, q)
 
     def reconstruct_lod(self, latent, lod, q=2, return_p=False):
         """What the level-`lod` head reads (CompDecoder.forward_lod): the trunk stops there."""

@@ -233,43 +233,50 @@ class CompDecoder(nn.Module):
         add("conv0_cls", IConv3d(c[1], 1, 3, 1, True, padding=1, SEED=_seed_tail()))
         self.likelihood_model = GaussianLikelihoodModel(step_size=1 / 16)
 
-    def forward(self, x, q, u_w=None):
-        """Returns (out, [cls0, cls1, out], net_bits[7]).  ``u_w``: optional {layer: uniform sample}
-        replacing the counter RNG for the q=1 weight noise (tests)."""
+    def _trunk(self, x, q, lod=0, u_w=None):
+        """up0 -> IGDN -> conv0 -> up1 -> conv1 -> up2 -> conv2, stopped at the activation the level-`lod` head reads.
+        -> what the heads read, as far as the walk went: [conv0's ([B, c1, 8^3], conv0_cls), from lod 1 down conv1's
+        ([B, c2, 16^3], conv1_cls), at lod 0 conv2's ([B, c3, 32^3], conv2_cls)].  q == 1 draws new weight noise."""
         u_w = u_w or {}
-        R, S = NF.ACT_RELU, NF.ACT_SIGMOID
+        R = NF.ACT_RELU
         if q == 1:
             NoiseState.step += 1
         t = self.activation(self.up0(x, q, u=u_w.get("up0")))
-        t = self.conv0(t, q, R, u_w.get("conv0"))
-        cls0 = self.conv0_cls(t, S)
-        t = self.up1(t, q, R, u_w.get("up1"))
-        t = self.conv1(t, q, R, u_w.get("conv1"))
-        cls1 = self.conv1_cls(t, S)
-        t = self.up2(t, q, R, u_w.get("up2"))
-        t = self.conv2(t, q, R, u_w.get("conv2"))
-        out = self.conv2_cls(t, q, S, u_w.get("conv2_cls"))
+        acts = [self.conv0(t, q, R, u_w.get("conv0"))]
+        if lod < 2:
+            t = self.up1(acts[-1], q, R, u_w.get("up1"))
+            acts.append(self.conv1(t, q, R, u_w.get("conv1")))
+        if lod < 1:
+            t = self.up2(acts[-1], q, R, u_w.get("up2"))
+            acts.append(self.conv2(t, q, R, u_w.get("conv2")))
+        return acts
+
+    def forward(self, x, q, u_w=None):
+        """Returns (out, [cls0, cls1, out], net_bits[7]).  ``u_w``: optional {layer: uniform sample}
+        replacing the counter RNG for the q=1 weight noise (tests)."""
+        S = NF.ACT_SIGMOID
+        t0, t1, t2 = self._trunk(x, q, 0, u_w)
+        cls0 = self.conv0_cls(t0, S)
+        cls1 = self.conv1_cls(t1, S)
+        out = self.conv2_cls(t2, q, S, (u_w or {}).get("conv2_cls"))
         net_bits = torch.stack([self.likelihood_model(p) for p in self.get_q_params()])
         return out, [cls0, cls1, out], net_bits
 
+    def forward_out(self, x, q):
+        """forward(x, q)[0] alone: the trunk and conv2_cls, the same calls and so the same bits; no coarse head, no rate."""
+        return self.conv2_cls(self._trunk(x, q)[-1], q, NF.ACT_SIGMOID)
+
     @torch.no_grad()
     def forward_lod(self, x, q, lod, return_p=False):
-        """The trunk up to the activation a coarse head reads, and no further: lod 1 stops after conv1 ([B, c2, 16^3],
-        read by conv1_cls), lod 2 after conv0 ([B, c1, 8^3], read by conv0_cls).  Same modules, same kernels and the
-        same bits as forward(x, q) computes on its way; an evaluation path (q = 0 or 2: no weight noise, no gradient).
-        return_p: also the head's probabilities [B, 1, D^3], equal to forward(x, q)[1][2 - lod]."""
+        """The trunk up to the activation a coarse head reads, and no further (lod 1 | 2).  Same modules, same kernels
+        and the same bits as forward(x, q) computes on its way; an evaluation path (q = 0 or 2: no weight noise, no
+        gradient).  return_p: also the head's probabilities [B, 1, D^3], equal to forward(x, q)[1][2 - lod]."""
         if lod not in (1, 2):
             raise ValueError(f"lod must be 1 or 2, got {lod!r}")
         if q not in (0, 2):
             raise ValueError("forward_lod is an evaluation path: q must be 0 or 2")
-        R = NF.ACT_RELU
-        t = self.activation(self.up0(x, q))
-        t = self.conv0(t, q, R)
-        if lod == 1:
-            t = self.conv1(self.up1(t, q, R), q, R)
-        if not return_p:
-            return t
-        return t, self.lod_head(lod)(t, NF.ACT_SIGMOID)
+        t = self._trunk(x, q, lod)[-1]
+        return (t, self.lod_head(lod)(t, NF.ACT_SIGMOID)) if return_p else t
 
     def lod_head(self, lod):
         return self.conv1_cls if lod == 1 else self.conv0_cls

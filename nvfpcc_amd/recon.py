@@ -10,6 +10,17 @@ import torch
 from . import ops
 
 
+def eval_batches(net, latents, batch, lod=0, q=2, return_p=False):
+    """The eval forward over latents [N,ch,2,2,2], at most max(batch, 1) blocks a call: yields (lo, hi, out) with out =
+    net.reconstruct(latents[lo:hi], q) at lod 0 and net.reconstruct_lod(latents[lo:hi], lod, q, return_p) at lod 1 | 2.
+    Nothing is gathered or moved, and gradients are the caller's business."""
+    batch = max(int(batch), 1)
+    for lo in range(0, latents.shape[0], batch):
+        hi = min(lo + batch, latents.shape[0])
+        x = latents[lo:hi].contiguous()
+        yield lo, hi, net.reconstruct_lod(x, lod, q, return_p) if lod else net.reconstruct(x, q)
+
+
 @torch.no_grad()
 def reconstruct_points(net, latents, origins, thh, batch=64, q=2, block_counts=None, thh_out=None):
     """latents [N,ch,2,2,2] (already rounded) on the device -> (int64 [n,3] points, per-block counts).
@@ -29,9 +40,7 @@ def reconstruct_points(net, latents, origins, thh, batch=64, q=2, block_counts=N
     elif isinstance(thh, torch.Tensor):
         thh = thh.to(device=dev, dtype=torch.float32)
     pts, counts = [], []
-    for lo in range(0, latents.shape[0], batch):
-        hi = min(lo + batch, latents.shape[0])
-        out = net.reconstruct(latents[lo:hi].contiguous(), q)
+    for lo, hi, out in eval_batches(net, latents, batch, q=q):
         t = thh
         if block_counts is not None:
             t = threshold_for_count(out, block_counts[lo:hi])
@@ -58,9 +67,7 @@ def reconstruct_points_lod(net, latents, origins, lod, thh, batch=64, q=2):
         thh = thh.to(device=dev, dtype=torch.float32)
     w_fwd, bias = net.lod_head_params(lod)
     pts, counts = [], []
-    for lo in range(0, latents.shape[0], batch):
-        hi = min(lo + batch, latents.shape[0])
-        x = net.reconstruct_lod(latents[lo:hi].contiguous(), lod, q)
+    for lo, hi, x in eval_batches(net, latents, batch, lod, q):
         t = thh[lo:hi].contiguous() if isinstance(thh, torch.Tensor) else thh
         p, c = ops.head_points(x, w_fwd, bias, t, origins[lo:hi].to(dev), lod)
         pts.append(p.cpu())

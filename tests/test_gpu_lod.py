@@ -90,6 +90,34 @@ def test_partial_forward_equals_the_full_forwards_coarse_heads(tag, B, gpu):
         net.reconstructor.forward_lod(lat.to(gpu), 1, 1)
 
 
+@pytest.mark.parametrize("ch,chanstr", [(3, "8,16,8,8"), (8, "16,32,16,16"), (4, "4,8,4,4")])
+def test_reconstruct_is_the_full_forwards_output_without_heads_or_rate(ch, chanstr, gpu, monkeypatch):
+    """Net.reconstruct gives the bits of forward(x, 2)[0] and runs neither coarse head nor the weight rate.  Two blocks:
+    the smallest batch at which a per-block indexing slip in the trunk walk can show."""
+    from nvfpcc_amd import network
+    from nvfpcc_amd.model import Net
+    network.reset_seed(synthetic_seed())
+    net = Net(None, "Gaussian", ch, chanstr, verbose=False)
+    sd = net.state_dict()
+    perturb_state_(sd, 500 + ch)
+    net.load_state_dict(sd)
+    net = net.to(gpu)
+    lat = torch.round(2.0 * torch.randn(2, ch, 2, 2, 2, generator=torch.Generator().manual_seed(ch))).to(gpu)
+    with torch.no_grad():
+        full = net.reconstructor(lat, 2)[0]
+        assert full.shape == (2, 1, 32, 32, 32)
+        assert torch.equal(net.reconstruct(lat, 2), full)
+
+        def unused(*a, **k):
+            raise AssertionError("a coarse head or the weight rate ran")
+        r = net.reconstructor
+        for mod in (r.conv0_cls, r.conv1_cls, r.likelihood_model):
+            monkeypatch.setattr(mod, "forward", unused)
+        assert torch.equal(net.reconstruct(lat, 2), full)
+        with pytest.raises(AssertionError, match="a coarse head"):
+            net.reconstructor(lat, 2)
+
+
 # ---------------------------------------------------------------- 2. nvf_head_occ_bits
 def head_case(C, D, B, gpu):
     """Activations with a few exact zeros and large magnitudes (a wrong halo or padding tap changes a logit by far more

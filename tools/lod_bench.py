@@ -5,7 +5,7 @@
 
 What is timed is a whole call, latents on the device in, points and counts on the device out:
 
-    lod 0            recon.reconstruct_points' loop body: Net.reconstruct + ops.threshold_points
+    lod 0            recon.reconstruct_points per slice of recon.eval_batches: Net.reconstruct + ops.threshold_points
     lod 1 / 2 fused  Net.reconstruct_lod + ops.head_points (nvf_head_occ_bits + nvf_points_from_bits)
     lod 1 / 2 plain  Net.reconstruct_lod(return_p=True) + ops.threshold_points: the head forward writes p, two more
                      kernels read it back

@@ -63,6 +63,7 @@ def main():
         raise SystemExit("lossless_bench.py needs a HIP device: nothing here can be timed on a CPU")
     from nvfpcc_amd import lossless_lod_pack as llp, lossless_nbr_pack as nlp, lossless_pack as lp, network, ops
     from nvfpcc_amd.model import Net
+    from nvfpcc_amd.recon import eval_batches
     from nvfpcc_amd.seeds import synthetic_seed
     dev = torch.device("cuda")
     network.reset_seed(synthetic_seed())
@@ -78,8 +79,7 @@ def main():
     gd = torch.Generator(device=dev).manual_seed(4)
     gts = []
     with torch.no_grad():
-        for lo in range(0, a.blocks, a.batch):
-            p = net.reconstruct(lat[lo:lo + a.batch].contiguous(), 2)
+        for _, _, p in eval_batches(net, lat, a.batch):
             # sharpened so that the cloud is sparse, as a leaf block is
             gts.append((torch.rand(p.shape, device=dev, generator=gd) < p ** 8).float())
     gt = torch.cat(gts, 0)
@@ -87,8 +87,8 @@ def main():
 
     def forward():
         with torch.no_grad():
-            for lo in range(0, a.blocks, a.batch):
-                net.reconstruct(lat[lo:lo + a.batch].contiguous(), 2)
+            for _ in eval_batches(net, lat, a.batch):
+                pass
         torch.cuda.synchronize()
 
     packs, info = {}, {}

@@ -43,8 +43,9 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 def record(tag, parent):
     import torch
     from nvfpcc_amd import lod_pack, lossless_lod_pack, lossless_nbr_pack, lossless_pack, thh_select as ts
-    from nvfpcc_amd.recon import reconstruct_points
+    from nvfpcc_amd.recon import eval_batches, reconstruct_points
     dev = torch.device("cuda")
+    torch.set_grad_enabled(False)
     heads = C.seed_heads(tag)
     net, lat, origins = C.build_decoder(GOLDEN, tag, dev, heads)
     gt = C.ground_truth()
@@ -54,11 +55,11 @@ def record(tag, parent):
     out.update({"heads/" + k: v for k, v in heads.items()})
 
     # the field, block by block at batch 1, and the two coarse heads
-    p_dev = C.batched(lambda x: net.reconstruct(x, 2), lat, 1)
+    p_dev = torch.cat([o for _, _, o in eval_batches(net, lat, 1)], 0)
     p = p_dev.reshape(C.N_BLOCKS, -1).cpu().numpy()
     fields = {"p": p}
     for lod, name in ((1, "cls1"), (2, "cls0")):
-        fields[name] = C.batched(lambda x: net.reconstruct_lod(x, lod, 2, return_p=True)[1], lat, 1) \
+        fields[name] = torch.cat([o[1] for _, _, o in eval_batches(net, lat, 1, lod, return_p=True)], 0) \
             .reshape(C.N_BLOCKS, -1).cpu().numpy()
     index = {"p": np.arange(0, C.VOX, C.SAMPLE_STRIDE), **C.HEAD_SAMPLES}
     for name, f in fields.items():
@@ -85,7 +86,7 @@ def record(tag, parent):
     out["lod_occ1"], out["lod_occ2"] = (np.packbits(o, axis=1) for o in sel["occ"])
 
     # encode --thh_mode count / block-count
-    p_all = C.batched(lambda x: net.reconstruct(x, 2), lat, C.ENCODE_BATCH)
+    p_all = torch.cat([o for _, _, o in eval_batches(net, lat, C.ENCODE_BATCH)], 0)
     n_points, k_b = int(gt.sum()), gt.sum(1)
     t = ts.choose("count", p_all, n_points=n_points)["t"]
     out["thh_count_pack"] = np.frombuffer(ts.write_thh_pack("count", t=t), np.uint8)

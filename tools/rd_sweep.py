@@ -51,6 +51,7 @@ def pick_threshold(ckpt, emb_fn, chanstr, ch, n_pts):
     import torch
     sys.argv = [sys.argv[0]]
     import NVFPCC as cli
+    from nvfpcc_amd.recon import eval_batches
     args = cli.build_parser().parse_args(["encode", "cloud.ply", "--chanstr", chanstr, "--ch", str(ch)])
     dev = torch.device("cuda")
     net = cli._build_net(args, dev)
@@ -61,8 +62,7 @@ def pick_threshold(ckpt, emb_fn, chanstr, ch, n_pts):
     counts = {t: 0 for t in cands}
     with torch.no_grad():
         lat = net.get_latent_code(emb)["quantized_latent"]
-        for i in range(0, lat.shape[0], 64):
-            out = net.reconstruct(lat[i:i + 64].contiguous(), 2)
+        for _, _, out in eval_batches(net, lat, 64):
             for t in cands:
                 counts[t] += int((out > t).sum().item())
     del net
