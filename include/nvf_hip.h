@@ -95,11 +95,23 @@ int nvf_effective_params(const float* kernel, const float* kernel_init, const fl
                          const float* b, const float* b_init, float* b_eff, int nb, int q, uint64_t seed,
                          uint64_t stream_id, void* stream);
 
-/* All layers of a decoder in one launch.  `table_dev` is a device array of `nlayers` records
- *   { const float *kernel, *kernel_init, *b, *b_init; float *w_fwd, *w_bwd, *b_eff;
- *     int32 dim0, dim1, k3, kind (0 conv / 1 convT), quantised, layer_id, nbias, pad; }
+/* All layers of a decoder in one launch.  `table_dev` is a device array of `nlayers` NvfLayerDesc records
  * (nvf_layer_desc_size() bytes each).  Writes w_eff = f_q(kernel) + kernel_init directly in the packed
  * layouts and b_eff = b + b_init.  Weight noise (q = 1): Philox(seed, ((step + *step_dev) << 8) | layer_id). */
+typedef struct NvfLayerDesc {
+  const float* kernel;
+  const float* kernel_init;
+  const float* b;
+  const float* b_init;
+  float* w_fwd;
+  float* w_bwd;
+  float* b_eff;
+  int32_t dim0, dim1, k3;   /* kernel is [dim0][dim1][k3] */
+  int32_t kind;             /* 0: conv [cout][cin][k] (w_bwd taps flipped); 1: convT [cin][cout][k] */
+  int32_t quantised;        /* 1: Q-layer (q applies); 0: I-layer (raw kernel) */
+  int32_t layer_id;         /* weight-noise stream id */
+  int32_t nbias, pad_;
+} NvfLayerDesc;
 size_t nvf_layer_desc_size(void);
 int nvf_prepare_weights(const void* table_dev, int nlayers, int q, uint64_t seed, uint64_t step,
                         const uint64_t* step_dev, void* stream);

@@ -61,21 +61,8 @@ extern "C" int nvf_effective_params(const float* kernel, const float* kernel_ini
 }
 
 // All layers of the decoder in ONE launch: w_eff = f_q(kernel) + kernel_init written straight into
-// the two scalar-load layouts (w_fwd[ci][k][co], w_bwd[co][k'][ci]) and b_eff = b + b_init.
-struct NvfLayerDesc {
-  const float* kernel;
-  const float* kernel_init;
-  const float* b;
-  const float* b_init;
-  float* w_fwd;
-  float* w_bwd;
-  float* b_eff;
-  int32_t dim0, dim1, k3;   // kernel is [dim0][dim1][k3]
-  int32_t kind;             // 0: conv [cout][cin][k] (w_bwd taps flipped); 1: convT [cin][cout][k]
-  int32_t quantised;        // 1: Q-layer (q applies); 0: I-layer (raw kernel)
-  int32_t layer_id;         // weight-noise stream id
-  int32_t nbias, pad_;
-};
+// the two scalar-load layouts (w_fwd[ci][k][co], w_bwd[co][k'][ci]) and b_eff = b + b_init.  One NvfLayerDesc
+// (nvf_hip.h) per layer.
 
 // w_eff of element i of a layer's kernel: f_q(kernel) + kernel_init (q = 1: uniform noise of one quantisation step,
 // q = 2: rounding to 1/16)

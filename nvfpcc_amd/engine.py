@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import ops, routes
-from ._lib import lib, check
+from ._lib import lib, check, NvfLayerDesc
 from .network import NoiseState
 
 R, S, NONE = ops.ACT_RELU, ops.ACT_SIGMOID, ops.ACT_NONE
@@ -111,9 +111,7 @@ def _abandons_step(fn):
 TRUNK = ("up0", "conv0", "up1", "conv1", "up2", "conv2", "conv2_cls")
 HEADS = ("conv1_cls", "conv0_cls")
 
-_DESC = np.dtype([("kernel", "<u8"), ("kernel_init", "<u8"), ("b", "<u8"), ("b_init", "<u8"), ("w_fwd", "<u8"),
-                  ("w_bwd", "<u8"), ("b_eff", "<u8"), ("dim0", "<i4"), ("dim1", "<i4"), ("k3", "<i4"),
-                  ("kind", "<i4"), ("quantised", "<i4"), ("layer_id", "<i4"), ("nbias", "<i4"), ("pad", "<i4")])
+_DESC = np.dtype(NvfLayerDesc)      # a row of the layer table (include/nvf_hip.h)
 
 
 class _Layer:

@@ -7,6 +7,8 @@ import os
 import numpy as np
 import torch
 
+from . import _cabi
+
 OFFSET = 512          # symbols = rounded latent + 512, mu + 512 (NVFPCC.py:447-458)
 _LIB = None
 
@@ -17,15 +19,7 @@ def lib():
         path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libnvf_codec.so")
         if not os.path.isfile(path):
             raise RuntimeError(f"{path} is missing: run python -m nvfpcc_amd.build")
-        h = C.CDLL(path)
-        h.nvf_ac_encode.restype = C.c_int64
-        h.nvf_ac_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p,
-                                    C.c_int64]
-        h.nvf_ac_decode.restype = C.c_int
-        h.nvf_ac_decode.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int,
-                                    C.c_void_p]
-        h.nvf_codec_version.restype = C.c_int
-        _LIB = h
+        _LIB = _cabi.bind(C.CDLL(path), _cabi.read_header("nvf_codec.h").prototypes)
     return _LIB
 
 

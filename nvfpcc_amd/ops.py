@@ -8,9 +8,9 @@ import math
 
 import torch
 
-from ._lib import lib, check, NvfTrunkWgrads
+from ._lib import lib, check, NvfTrunkWgrads, CONSTANTS as _K
 
-ACT_NONE, ACT_RELU, ACT_SIGMOID = 0, 1, 2
+ACT_NONE, ACT_RELU, ACT_SIGMOID = _K["NVF_ACT_NONE"], _K["NVF_ACT_RELU"], _K["NVF_ACT_SIGMOID"]
 # kernel variant passed to the conv / wgrad entry points: 0 = tuned LDS-tiled kernels, 1 = the
 # one-thread-per-output kernels (debug cross-check, bench.py --naive), >= 2 = alternates kept for tuning (tools/kbench.py)
 _NAIVE = 0
@@ -1412,8 +1412,9 @@ def occ_hist(p, shift=None, nbits=None, prefix=None, d2=None, gt=None, edges=Non
 
 # ---------------------------------------------------------------- lossless geometry (csrc/occ_rans.hip)
 OCC_CONTEXTS = 256
-OCC_RANS_MAX_GROUP = 1024
-OCC_RANS_PAST_END, OCC_RANS_BAD_STATE, OCC_RANS_WORDS_LEFT = 1, 2, 4
+OCC_RANS_MAX_GROUP = _K["NVF_OCC_RANS_MAX_GROUP"]
+OCC_RANS_PAST_END, OCC_RANS_BAD_STATE, OCC_RANS_WORDS_LEFT = (
+    _K["NVF_OCC_RANS_PAST_END"], _K["NVF_OCC_RANS_BAD_STATE"], _K["NVF_OCC_RANS_WORDS_LEFT"])
 
 
 def _occ_blocks(p, gt=None):
@@ -1517,9 +1518,9 @@ def occ_rans_decode(p, f1, states, words, nwords, group):
 
 
 # ---------------------------------------------------------------- scalable lossless geometry (csrc/occ_hier.hip)
-OCC_HIER_CONTEXTS = 3072
-OCC_HIER_BLOCK_WORDS = 512 + 4096 + 32768
-OCC_HIER_MAX_BATCH = 32768
+OCC_HIER_CONTEXTS = _K["NVF_OCC_HIER_CONTEXTS"]
+OCC_HIER_BLOCK_WORDS = _K["NVF_OCC_HIER_BLOCK_WORDS"]
+OCC_HIER_MAX_BATCH = _K["NVF_OCC_HIER_MAX_BATCH"]
 
 
 def occ_hier_cells(words, fill=True):
@@ -1639,7 +1640,7 @@ def occ_hier_decode(pyr, f1, states, words, nwords, group, level=0):
 
 
 # ---------------------------------------------------------------- neighbour contexts (csrc/occ_hier.hip, NBR)
-OCC_NBR_CONTEXTS = 3072 + 32 * 1024
+OCC_NBR_CONTEXTS = _K["NVF_OCC_NBR_CONTEXTS"]
 
 
 def _occ_nbr_table(f1, dev):

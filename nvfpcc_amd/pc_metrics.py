@@ -33,10 +33,10 @@ import math
 import numpy as np
 import torch
 
-from ._lib import lib, check, NvfPcSparseIndex
+from ._lib import lib, check, NvfPcSparseIndex, CONSTANTS
 
 ROOT = 1024                # the default domain: bits = 10
-CELLS = 128 ** 3           # NVF_PC_CELLS, the dense index
+CELLS = CONSTANTS["NVF_PC_CELLS"]           # the dense index
 BITS = (10, 11, 12)        # bits per axis the metrics reach
 
 

@@ -14,7 +14,7 @@
 import numpy as np
 import torch
 
-from ._lib import lib, check
+from ._lib import lib, check, CONSTANTS
 
 LEAF = 32
 ROOT = 1024
@@ -240,8 +240,8 @@ def octree_pack_from_origins(origins, bits=10):
 
 
 # ---------------------------------------------------------------- the whole pre-processing on the device
-META_INTS = 16                  # NVF_PP_META_INTS: [0] N, [1] rejected points, [2..9] bytes of level 0..7, [10] nb_off[N], [11] voxels
-WORK_WORDS = 11264              # NVF_PP_WORK_WORDS
+META_INTS = CONSTANTS["NVF_PP_META_INTS"]    # [0] N, [1] rejected points, [2..9] bytes of level 0..7, [10] nb_off[N], [11] voxels
+WORK_WORDS = CONSTANTS["NVF_PP_WORK_WORDS"]
 
 
 class DevicePreprocess:

@@ -49,6 +49,9 @@ def test_workspace_queries_need_no_gpu():
 def test_request_struct_layout_matches_the_library():
     """A mismatch between the ctypes Structure and the header would otherwise first show as a fault on a GPU."""
     assert ctypes.sizeof(_lib.NvfTrunkWgrads) == _lib.lib().nvf_trunk_wgrads_bytes() == 152
+    assert ctypes.sizeof(_lib.NvfLayerDesc) == _lib.lib().nvf_layer_desc_size() == 88
+    import numpy as np
+    assert np.dtype(_lib.NvfLayerDesc).itemsize == 88      # the layer table's row (engine._DESC)
 
 
 # ---- refusals of nvf_wgrad_trunk_partial: every one returns before any HIP call, so dummy addresses will do ----------
