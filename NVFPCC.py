@@ -25,8 +25,11 @@ engine (nvfpcc_amd/engine.py) instead of a DataLoader + autograd loop.
     python NVFPCC.py train seq_%04d.ply --gof 8 --frame_start 1300 ...         # one decoder for frames 1300 .. 1307
     python NVFPCC.py encode seq_%04d.ply --gof 8 --frame_start 1300 ...        # one pack: the weights once, a frame pack each
     python NVFPCC.py decode pack.pk --frame 1303 ...                           # that frame alone; without --frame, all of them
+    python NVFPCC.py train next.ply --freeze_decoder --load_weights q4.ckpt    # latents only, under a decoder that does not move
+    python NVFPCC.py encode next.ply --load_weights q4.ckpt --ref_pack ref.pk  # a latents-only pack: 33 bytes name ref.pk's decoder
+    python NVFPCC.py decode p.pk --ref_pack ref.pk ...                         # decoded under the reference's weights
 
-Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --ply_format, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --lossless_lod, --lossless_ctx, --gof, --frame_start, --frame, --thh_mode (count | block-count | d1:
+Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --ply_format, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --lossless_lod, --lossless_ctx, --gof, --frame_start, --frame, --freeze_decoder, --ref_pack, --thh_mode (count | block-count | d1:
 nvfpcc_amd/thh_select.py picks the occupancy threshold at encode time and a `thh_pack` key carries it); multi-GPU training when launched
 through torch.distributed.run (one process per GPU, leaf blocks sharded, one RCCL all-reduce per step).
 Headless: no GUI window, no IPython shell.
@@ -142,9 +145,77 @@ def _gof_names(args):
     return names
 
 
+def _load_ref_pack(args, what):
+    """--ref_pack: the reference pack, which must carry a decoder of its own."""
+    try:
+        with open(args.ref_pack, 'rb') as f:
+            ref = pickle.load(f)
+    except (OSError, pickle.UnpicklingError, EOFError) as e:
+        raise SystemExit(f"{what} --ref_pack {args.ref_pack}: {e}")
+    if not isinstance(ref, dict) or 'net_weight_pack' not in ref:
+        raise SystemExit(f"{what} --ref_pack {args.ref_pack}: it holds no net_weight_pack (a latents-only pack cannot be "
+                         f"a reference)")
+    return ref
+
+
+def fit_frozen(args):
+    """train --freeze_decoder: the latents of the input's blocks fitted under the decoder of --load_weights, which
+    does not move (TrainEngine.fit_latents; --epochs is the number of latent steps).  One [Fit] line per evaluation;
+    the table goes to <checkpoint_dir>/%04d_emb.ckpt under the number of the last step, counted from 0 as train counts
+    its epochs."""
+    from nvfpcc_amd import pframe
+    from nvfpcc_amd.engine import TrainEngine
+    if not args.load_weights:
+        raise SystemExit("train --freeze_decoder: no decoder to freeze; name the quantised checkpoint with --load_weights")
+    warm = hasattr(args, 'ref_pack')
+    if warm != bool(args.load_emb):
+        raise SystemExit("train --freeze_decoder: --ref_pack and --load_emb warm-start the table together (the reference's "
+                         "pack gives its blocks' origins, --load_emb their rows); give both or neither")
+    if args.epochs < 1:
+        raise SystemExit(f"train --freeze_decoder: --epochs {args.epochs} is the number of latent steps, at least 1")
+    _bits(args)
+    _gof_names(args)
+    ref = _load_ref_pack(args, 'train --freeze_decoder') if warm else None
+    dev, rank, world = _device(args)
+    if world > 1:
+        raise SystemExit("train --freeze_decoder runs on one GPU: the blocks of a frame are one pass")
+    data, _ = _load_data(args, dev, shuffle=False)
+    print('Using lambda: ', args.lmbda)
+    net = _build_net(args, dev)
+    d = torch.load(args.load_weights, map_location=dev)
+    net.load_state_dict({k: v for k, v in d.items() if 'init_coords' not in k}, strict=False)
+    emb = None
+    if warm:
+        ref_emb = torch.load(args.load_emb, map_location='cpu').float()
+        origins = np.array([data.origins[i] for i in range(len(data))], dtype=np.int64)
+        try:
+            emb = pframe.warm_start(ref_emb, pframe.pack_origins(ref), origins)
+        except ValueError as e:
+            raise SystemExit(f"train --freeze_decoder: {args.load_emb} / {args.ref_pack}: {e}")
+    gt, dist = data.to_device(dev)
+    eng = TrainEngine(net, gt, dist, n_points_total=float(data.N), lmbda=args.lmbda, w1=args.w1, w2=args.w2,
+                      lr=args.lr, wemb=args.wemb, emb=emb, seed=args.seed)
+    print('Embedding learning rate: %f x %f = %f' % (args.lr, args.wemb, args.lr * args.wemb))
+    t0, n_pts = time.time(), float(data.N)
+
+    def report(step, J, improved, bits):
+        torch.cuda.synchronize()
+        print(FIT_LINE % (step, time.time() - t0, J.sum().item(), int(improved.sum().item()), data.N_leaf,
+                          bits.sum().item() / n_pts))
+    eng.fit_latents(args.epochs, eval_every=10, report=report)
+    print('[INFO] Saving')
+    os.makedirs(args.checkpoint_dir, exist_ok=True)
+    torch.save(eng.emb.detach().clone(), './%s/%04d_emb.ckpt' % (args.checkpoint_dir, args.epochs - 1))
+
+
+FIT_LINE = '[Fit %04d %.1f seconds] J: %.9e improved: %d / %d b_latent: %.4f'
+
+
 def train(args):
     from nvfpcc_amd import dist as nd, ops
     from nvfpcc_amd.engine import TrainEngine, EpochDriver
+    if hasattr(args, 'freeze_decoder'):
+        return fit_frozen(args)
     peak = (1 << _bits(args)) - 1
     _gof_names(args)
     dev, rank, world = _device(args)
@@ -244,21 +315,31 @@ def encode(args):
     data, pre = _load_data(args, dev, shuffle=False)
     net = _build_net(args, dev)
     net_weight_pack = weight_codec.enc_dec_from_file(args.load_weights, qp=int(args.qp))
+    as_p = hasattr(args, 'ref_pack')
+    if as_p:    # a latents-only pack: the decoder of --load_weights must be the reference's, byte for byte
+        from nvfpcc_amd import pframe
+        ref = _load_ref_pack(args, 'encode')
+        if pframe.digest(net_weight_pack) != pframe.digest(ref['net_weight_pack']):
+            raise SystemExit(f"encode --ref_pack: the decoder of {args.load_weights} (at --qp {args.qp:g}) is not the one "
+                             f"{args.ref_pack} carries; a latents-only pack is coded under its reference's decoder")
     d = torch.load(args.load_weights, map_location=dev)
     net.load_state_dict({k: v for k, v in d.items() if 'init_coords' not in k}, strict=False)
     emb = torch.load(args.load_emb, map_location=dev).to(dev).float().contiguous()
     if names is not None:
-        return _encode_gof(args, net, net_weight_pack, emb, data, dev, bits, fmt)
+        return _encode_gof(args, net, net_weight_pack, emb, data, dev, bits, fmt, as_p)
 
     def write(frame_pack):
+        total_pack = {'net_weight_pack': net_weight_pack, **frame_pack}
         with open(args.pack_fn, 'wb') as f:
-            pickle.dump({'net_weight_pack': net_weight_pack, **frame_pack}, f)
-    _encode_frame(args, net, net_weight_pack, emb, data, pre, dev, bits, fmt, 'rc_enc', write)
+            pickle.dump(pframe.split(total_pack) if as_p else total_pack, f)
+    _encode_frame(args, net, net_weight_pack, emb, data, pre, dev, bits, fmt, 'rc_enc', write,
+                  decoder_bits=8 * pframe.REF_PACK_BYTES if as_p else None)
 
 
-def _encode_gof(args, net, net_weight_pack, emb, data, dev, bits, fmt):
+def _encode_gof(args, net, net_weight_pack, emb, data, dev, bits, fmt, as_p=False):
     """encode --gof: every frame through _encode_frame with its rows of --load_emb, into one pack
-    (nvfpcc_amd.gof: the weights once, gof_pack, a frame pack each)."""
+    (nvfpcc_amd.gof: the weights once, gof_pack, a frame pack each).  as_p: written as a latents-only pack
+    (nvfpcc_amd.pframe.split), whose closing lines count ref_pack in place of the weights."""
     import contextlib
     import io
     from nvfpcc_amd import gof
@@ -286,22 +367,26 @@ def _encode_gof(args, net, net_weight_pack, emb, data, dev, bits, fmt):
         frames.append(frame_pack)
     total_pack = {'net_weight_pack': net_weight_pack,
                   'gof_pack': gof.write_gof_pack(start, np.diff(data.frame_ranges), data.frame_points), 'frames': frames}
+    if as_p:
+        from nvfpcc_amd import pframe
+        total_pack = pframe.split(total_pack)
     with open(args.pack_fn, 'wb') as f:
         pickle.dump(total_pack, f)
     for line in gof.gof_lines(total_pack):
         print(line)
 
 
-def _encode_frame(args, net, net_weight_pack, emb, data, pre, dev, bits, fmt, stem, write_pack):
+def _encode_frame(args, net, net_weight_pack, emb, data, pre, dev, bits, fmt, stem, write_pack, decoder_bits=None):
     """Code one frame: the latents `emb` of its blocks under `net` (whose bytes are `net_weight_pack`), the side packs
     the flags ask for, and its reconstruction into `stem`.ply (and `stem`_lod1.ply / _lod2.ply).  write_pack(frame_pack)
     is called as soon as the pack is complete, before the reconstruction; None: the frame belongs to a group, nothing
-    is written and its Gross bpp line is the group's.  -> (frame_pack: the plain pack without net_weight_pack, report:
+    is written and its Gross bpp line is the group's.  decoder_bits: what the written pack pays for its decoder when that
+    is not the weights' stream (a latents-only pack: its ref_pack).  -> (frame_pack: the plain pack without net_weight_pack, report:
     {'points', 'blocks', 'latent_bits', 'side_bits'})."""
     from nvfpcc_amd import ops, latent_codec
     from nvfpcc_amd import ply_io
     from nvfpcc_amd.recon import eval_batches, reconstruct_points
-    net_bits = len(net_weight_pack['bit_stream']) * 8
+    net_bits = len(net_weight_pack['bit_stream']) * 8 if decoder_bits is None else int(decoder_bits)
     np_origins = np.array([data.origins[i] for i in range(len(data))], dtype=np.int16)
     with torch.no_grad():
         info = net.get_latent_code(emb)
@@ -488,6 +573,17 @@ def decode(args):
     net = _build_net(args, torch.device('cpu'))
     with open(args.input, 'rb') as f:
         total_pack = pickle.load(f)
+    if 'ref_pack' in total_pack:            # a latents-only pack: its decoder is the reference's (nvfpcc_amd.pframe)
+        from nvfpcc_amd import pframe
+        if not hasattr(args, 'ref_pack'):
+            raise SystemExit(f"decode {args.input}: a latents-only pack, coded under another pack's decoder; name that "
+                             f"pack with --ref_pack")
+        try:
+            total_pack = pframe.join(total_pack, _load_ref_pack(args, 'decode'))
+        except ValueError as e:
+            raise SystemExit(f"decode {args.input} --ref_pack {args.ref_pack}: {e}")
+    elif hasattr(args, 'ref_pack'):
+        print(f'[Info] {args.input} carries its own decoder; --ref_pack {args.ref_pack} is not read')
     if 'gof_pack' in total_pack:            # a group of frames: --frame K alone, or every frame
         return _decode_gof(args, total_pack, dev, fmt, net)
     if hasattr(args, 'frame'):
@@ -779,6 +875,15 @@ def build_parser():
     p.add_argument('--frame', type=int, default=argparse.SUPPRESS,
                    help='decode of a group: the frame of that number alone, into rc_dec.ply; nothing of another frame is '
                         'read.  Absent: every frame, into rc_dec_<number>.ply (--ref_ply is then a pattern too).')
+    p.add_argument('--freeze_decoder', action='store_true', default=argparse.SUPPRESS,
+                   help='train: fit the latents of the input under the decoder of --load_weights (a quantised checkpoint), '
+                        'which does not move; --epochs latent steps, every block keeps the best rounded latents seen.  '
+                        'Writes <checkpoint_dir>/<epochs - 1>_emb.ckpt.')
+    p.add_argument('--ref_pack', default=argparse.SUPPRESS,
+                   help='A pack that carries the decoder.  encode: write a latents-only pack (ref_pack, 33 bytes, in place '
+                        'of net_weight_pack) after checking that --load_weights is that decoder.  decode: the reference '
+                        'of a latents-only pack.  train --freeze_decoder with --load_emb: warm-start every block from '
+                        'the reference\'s row of the same or the nearest origin.')
     p.add_argument('--ply_format', choices=['ascii', 'binary'], default=argparse.SUPPRESS,
                    help='encode / decode: format of the rc_*.ply files written.  ascii (also when absent): double x y z '
                         'as text; binary: binary_little_endian with float x y z.')

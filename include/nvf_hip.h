@@ -586,6 +586,17 @@ int nvf_focal_loss_multi(const float* const* ps, const float* const* gts, const 
                          float* loss, int chain_sigmoid, void* workspace, size_t workspace_bytes, NvfStepCtx* ctx,
                          void* stream);
 
+/* ---- per-block costs of a frozen-decoder latent fit (engine.fit_latents) --------
+ * p, gt, dist [batch, voxels] (dist may be NULL), x_rounded [batch, c, spatial] (the eval-mode latents), sigma, mu [c].
+ * out [batch][2], float64: out[b][0] = the focal sum of block b (the terms of nvf_focal_loss without chain_sigmoid),
+ * out[b][1] = its eval-mode latent bits (the terms of nvf_latent_rate in mode 1).  Terms are float32; they are added in
+ * float64 in a fixed order by ONE workgroup per block: a row depends neither on batch nor on the block's place in it.
+ * NVF_EINVAL: a NULL required pointer, batch < 1, voxels not a multiple of 1024 (the workgroup's stride of 16-byte
+ * loads), c * spatial > 64 (the symbols are one wave's work), p / gt / dist not 16-byte aligned. */
+int nvf_block_costs(const float* p, const float* gt, const float* dist, float alpha, float beta,
+                    const float* x_rounded, const float* sigma, const float* mu, double* out, int batch, int voxels,
+                    int c, int spatial, void* stream);
+
 /* metrics (utils/loss.py:74-84, 113-121): out[0..5] (+)= tp, ap, tn, an at thh_acc; sse, denom at thh_sse */
 /* Exactness of the five counts: the per-workgroup partials are float32 and exact while a workgroup sees fewer than 2^24
  * elements, i.e. up to n = 2^34 per term (1024 workgroups); the final pass adds them in float64 and rounds once, so a

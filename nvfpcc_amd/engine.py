@@ -55,7 +55,8 @@ class StepPlan(NamedTuple):
     want_emb: bool              # latent gradients (the latent phase)
     stem_fwd: str               # "head": in the step head's launch / "latent": with the latent generator / "fused" / "layers"
     latent_fwd_fused: bool      # latent generator + quantiser in one launch (where the stem's forward did not take them)
-    heads: str                  # "deferred": forward too in the loss launch / "fused_loss" / "heads3" / "layers"
+    heads: str                  # "deferred": forward too in the loss launch / "fused_loss" / "heads3" / "layers" /
+                                # "main": conv2_cls alone, the coarse heads do not run (latent passes under a frozen decoder)
     head_bias_in_loss: bool     # the heads' bias gradients are partials of the loss launch
     heads_in_trunk5: bool       # the heads' weight gradients are workgroups of the five-gradient launch
     trunk5: bool                # the five trunk weight gradients in one launch (add_trunk5); else per layer
@@ -69,12 +70,16 @@ class StepPlan(NamedTuple):
 @functools.lru_cache(maxsize=None)
 def plan_step(narrow, wide, winograd, fused_stem, fused_latent_stem, heads3, ch, batch, want_w, want_emb, fuse, hook,
               naive, head_bias_in_loss, sums_in_trunk5, stem_in_trunk5, stem_in_head, heads_in_trunk5,
-              step_head=False, defer_heads=False):
+              step_head=False, defer_heads=False, main_only=False):
     """Which launches a step of ``batch`` blocks consists of, from the engine's class flags, the caller's request (``fuse``:
     it handed over the optimiser's coefficients; ``step_head``: batch_and_prepare(stem_mode=...) ran; ``defer_heads``:
     forward(defer_heads=True)), ops._NAIVE and the five module switches.  No tensors.  What launch_trunk_wgrads (wgrad.hip)
     answers with NVF_EINVAL is an implication between the fields (tests/test_step_plan.py).  ``winograd`` and the 64-block
-    switch point select kernel forms inside a launch (routes.py), never a launch."""
+    switch point select kernel forms inside a launch (routes.py), never a launch.  ``main_only``: a latent pass whose
+    objective holds the main output's focal term alone -- the coarse heads (conv0_cls, conv1_cls) run neither forward, loss
+    nor backward-data (a decoder rebuilt from a pack holds seed values there: the pack drops them)."""
+    if main_only and want_w:
+        raise ValueError("plan_step: main_only is a form of the latent pass (no weight gradients)")
     # the one-launch groupings bypass the variant switch of the per-layer entry points: only with the tuned kernels
     tuned = naive == 0
     small = batch <= 32         # the cooperative launches keep one arrival counter per block, 32 of them
@@ -82,7 +87,7 @@ def plan_step(narrow, wide, winograd, fused_stem, fused_latent_stem, heads3, ch,
                 "latent" if ch <= 8 and tuned and fused_stem and fused_latent_stem else
                 "fused" if fused_stem else "layers")
     fused_loss = heads3 and small and tuned
-    heads = (("deferred" if defer_heads and want_w else "fused_loss") if fused_loss else
+    heads = ("main" if main_only else ("deferred" if defer_heads and want_w else "fused_loss") if fused_loss else
              "heads3" if heads3 else "layers")
     trunk5 = want_w and narrow and tuned
     in_trunk5 = trunk5 and heads3 and heads_in_trunk5
@@ -288,12 +293,12 @@ class TrainEngine:
             self._rate = (job, add, key, dk, part)
         return self._rate
 
-    def _plan(self, batch, want_w=False, want_emb=False, fuse=False, step_head=False, defer_heads=False):
+    def _plan(self, batch, want_w=False, want_emb=False, fuse=False, step_head=False, defer_heads=False, main_only=False):
         """plan_step for this engine, with the module switches and ops._NAIVE as they are NOW (tests and bench.py assign them)."""
         return plan_step(self.narrow, self.wide, self.winograd, self.fused_stem, self.fused_latent_stem, self.heads3,
                          self.ch, batch, want_w, want_emb, fuse, self.grad_hook is not None, ops._NAIVE,
                          _HEAD_BIAS_IN_LOSS, _SUMS_IN_TRUNK5, _STEM_IN_TRUNK5, _STEM_IN_HEAD, _HEADS_IN_TRUNK5,
-                         step_head, defer_heads)
+                         step_head, defer_heads, main_only)
 
     def _noise(self):
         """(step, step_dev) of the counter RNG: the host's counter, or 0 and the device word a captured graph reads."""
@@ -383,15 +388,17 @@ class TrainEngine:
         osz = tuple(s + 2 * L.pad - L.k + 1 for s in x.shape[2:])
         return ops.conv3d_gather(x, L.w_fwd, L.b_eff, L.cout, L.k, 1, L.pad, osz, act)
 
-    def forward(self, e, mode, block_ids, defer_heads=False, stem=None):
+    def forward(self, e, mode, block_ids, defer_heads=False, stem=None, main_only=False):
         """e [B,ch,2,2,2] latents-before-latent_gen.  Returns the dict of saved activations.  ``defer_heads``: the caller
         runs backward() with weight gradients next -- at mini-batch sizes the heads' forward then rides in the launch of
         their loss and backward-data (a["p0"..] stay None until then).  ``stem``: the stem activations of this
-        mini-batch that batch_and_prepare(..., stem_mode=mode) returned (None: forward() runs the stem itself)."""
+        mini-batch that batch_and_prepare(..., stem_mode=mode) returned (None: forward() runs the stem itself).
+        ``main_only``: conv2_cls alone of the three heads (a["p0"] = a["p1"] = None); backward(main_only=True) follows."""
         net, Ls = self.net, self.layers
         a = {"e": e}
         # (defer_heads is the caller's promise of a weight-gradient backward pass; backward() holds it to that)
-        plan = self._plan(e.shape[0], want_w=defer_heads, step_head=stem is not None, defer_heads=defer_heads)
+        plan = self._plan(e.shape[0], want_w=defer_heads, step_head=stem is not None, defer_heads=defer_heads,
+                          main_only=main_only)
         g2 = net.latent_gen.gdn_2
         ig = net.reconstructor.activation
         step, sd = self._noise()
@@ -426,6 +433,9 @@ class TrainEngine:
         a["y5"] = self._conv(Ls["conv2"], a["y4"], R, train=(mode == "train"))
         if plan.heads == "deferred":
             a["p0"] = a["p1"] = a["p2"] = None      # nvf_heads3_fwd_loss_bwd_data (backward)
+        elif plan.heads == "main":
+            a["p0"] = a["p1"] = None
+            a["p2"] = self._conv(Ls["conv2_cls"], a["y5"], S)
         elif plan.heads != "layers":                # all three heads in one launch, after the trunk
             hl = [Ls["conv0_cls"], Ls["conv1_cls"], Ls["conv2_cls"]]
             a["p0"], a["p1"], a["p2"] = ops.heads3_fwd([a["y1"], a["y3"], a["y5"]], [L.w_fwd for L in hl],
@@ -504,18 +514,19 @@ class TrainEngine:
         self._rate_ready = self.tail_done = False
 
     @_abandons_step
-    def backward(self, a, gt, dist, gt16, gt8, n_pts, mode, block_ids, want_w, want_emb, fuse=None):
+    def backward(self, a, gt, dist, gt16, gt8, n_pts, mode, block_ids, want_w, want_emb, fuse=None, main_only=False):
         """Loss (NVFPCC.py:161-196) and its gradients.  Weight grads land in self.flat_g.  The phases run in launch order;
         what they return stays referenced here until the last launch has been enqueued (queued stages write it late)."""
         deferred = a.get("p2") is None
-        plan = self._plan(a["e"].shape[0], want_w, want_emb, fuse is not None, defer_heads=deferred)
+        plan = self._plan(a["e"].shape[0], want_w, want_emb, fuse is not None, defer_heads=deferred, main_only=main_only)
         if deferred and plan.heads != "deferred":
             raise ValueError("forward(defer_heads=True) must be followed by a backward pass with weight gradients "
                              "(want_w=True): the heads' forward runs in that pass's loss launch")
         if self._wg is None:
             # (wide decoder: 125 MiB of slabs at batch 16 -- a workspace that had to grow mid-step would be reallocated)
             self._wg = ops.WgradBatch(self.dev, nbytes=(256 if self.wide else 128) << 20, ctx=self.ctx)    # partial sums now, ONE reduction launch for all ten
-        loss = torch.empty(4, device=self.dev)   # [main, head0, head1, unused]
+        # [main, head0, head1, unused]; main-head-only: the coarse terms are not part of the objective and read 0
+        loss = torch.zeros(4, device=self.dev) if plan.heads == "main" else torch.empty(4, device=self.dev)
         nbits = torch.empty(7, device=self.dev)
         # the one-block final passes of the focal terms, the bias sums and the weight rate feed nothing inside the
         # step: queue them and run all three in one launch at the end
@@ -563,6 +574,10 @@ class TrainEngine:
                              out=self.step_counts, ctx=ctx)
         bias_outs = [L.gb for L in hl] if plan.head_bias_in_loss else None
         terms = ([gt8, gt16, gt], [None, None, dist], [0.85, 0.85, 0.9], [0.0, 0.0, 1.0], [1, 2, 0], loss, [L.w_bwd for L in hl])
+        if plan.heads == "main":
+            # the one focal term of p2 and conv2_cls's backward-data; nothing reaches y1 / y3 from a head (t0 = t1 = None)
+            dl2, = ops.focal_loss_multi([(a["p2"], gt, dist, 0.9, 1.0)], loss)
+            return None, None, self._dx_conv(Ls["conv2_cls"], dl2, a["y5"], mask=a["y5"]), None
         if plan.heads == "deferred":
             # the heads' forward, the three focal terms, their logit gradients and the heads' backward-data: ONE launch
             # (forward() left p0 / p1 / p2 to this call)
@@ -886,15 +901,16 @@ class TrainEngine:
             self._latent_update(lo, hi, de)
         return a, de
 
-    def _latent_grad(self, lo, hi):
+    def _latent_grad(self, lo, hi, main_only=False):
         """Forward and latent gradient of blocks [lo, hi) at the noise counter and the effective weights as they stand.
         The noise of a block is keyed by its absolute id (block_ids), not by its place in the batch, and every loss term
-        is a sum over blocks: the rows of `de` do not depend on which other blocks share the pass."""
+        is a sum over blocks: the rows of `de` do not depend on which other blocks share the pass.  ``main_only``: the
+        objective is the main output's focal term plus the latent rate (plan_step)."""
         ids = torch.arange(lo, hi, device=self.dev)
         n_pts = float(self.counts.sum())          # the reference divides by the points of ALL blocks
-        a = self.forward(self.emb[lo:hi], "train", ids)
+        a = self.forward(self.emb[lo:hi], "train", ids, main_only=main_only)
         de = self.backward(a, self.gt[lo:hi], self.dist[lo:hi], self.gt16[lo:hi], self.gt8[lo:hi], n_pts, "train",
-                           ids, want_w=False, want_emb=True)
+                           ids, want_w=False, want_emb=True, main_only=main_only)
         return a, de
 
     def _latent_update(self, lo, hi, de):
@@ -952,6 +968,73 @@ class TrainEngine:
         out[3:21] = c[0:18]
         out[21] = a["lbits"].reshape(-1)[0]
         return out
+
+    # ------------------------------------------------------------------ latents under a frozen decoder
+    def _block_sums(self, lo, hi):
+        """float64 [hi - lo, 2]: (main focal sum, eval-mode latent bits) of every block of [lo, hi), by the eval forward
+        at the effective weights as they stand, at most LATENT_CHUNK blocks resident at a time."""
+        outs = []
+        for c in range(lo, hi, LATENT_CHUNK):
+            e = min(c + LATENT_CHUNK, hi)
+            a = self.forward(self.emb[c:e], "eval", torch.arange(c, e, device=self.dev))
+            outs.append(ops.block_costs(a["p2"], self.gt[c:e], self.dist[c:e], 0.9, 1.0, a["x0"], *self._ec()))
+        return torch.cat(outs, 0) if outs else torch.zeros(0, 2, dtype=torch.float64, device=self.dev)
+
+    def _cost(self, sums):
+        """J_b = c_f * focal_b + c_r * bits_b in float64, with the coefficients the main-head-only latent gradient
+        differentiates: the focal term enters the objective as it is (_bwd_loss_heads: its gradient is unscaled) and the
+        latent bits times lambda * w1 / n_pts, n_pts the occupied voxels of ALL the engine's blocks (_latent_grad,
+        _bwd_latent).  The weight-rate term does not depend on the latents and is left out."""
+        c_f, c_r = 1.0, self.lmbda * self.w1 / float(self.counts.sum())
+        return c_f * sums[:, 0] + c_r * sums[:, 1]
+
+    @_abandons_step
+    def block_costs(self, lo=0, hi=None):
+        """Per-block cost J_b (float64 [hi - lo]) of the rounded latents of blocks [lo, hi) under the decoder at q = 2 --
+        the route eval_forward takes.  Under frozen weights the objective of the latent fit is the plain sum of these: a
+        block's cost depends on its own `emb` row only, and not on which blocks share the pass (nvf_block_costs)."""
+        hi = self.N_leaf if hi is None else hi
+        self.prepare_weights(2)
+        return self._cost(self._block_sums(lo, hi))
+
+    @_abandons_step
+    def fit_latents(self, steps, eval_every=10, lo=0, hi=None, report=None):
+        """Fit the latents of blocks [lo, hi) under the decoder as it stands, frozen at q = 2: ``steps`` main-head-only
+        latent steps in "train" mode (fresh latent noise per step), Adam on `emb` alone.  No net parameter, neither Adam
+        moment of the net and not opt_step moves; the weights carry no noise at q = 2 and are prepared once.
+
+        Before the first step, after every ``eval_every``-th and after the last one the per-block costs are evaluated
+        and every block keeps the `emb` row with the lowest J_b so far (strict <: the earlier row wins a tie).  This is
+        valid because the decoder is frozen -- the objective is a sum of per-block costs, each a function of its own row
+        -- so no block ends worse than it started.  At the end emb[lo:hi] holds the kept rows.  Returns (J_start,
+        J_final), float64 [hi - lo].  ``report(step, J_kept, improved, bits_kept)``: called after every evaluation with
+        device tensors (the kept costs, which blocks improved on the start, the kept rows' latent bits)."""
+        hi = self.N_leaf if hi is None else hi
+        steps, eval_every = int(steps), int(eval_every)
+        if steps < 0 or eval_every < 1 or not 0 <= lo < hi <= self.N_leaf:
+            raise ValueError(f"fit_latents: steps = {steps}, eval_every = {eval_every}, blocks [{lo}, {hi})")
+        self.prepare_weights(2)
+        kept = self.emb[lo:hi].clone()
+        sums = self._block_sums(lo, hi)
+        J0 = self._cost(sums)
+        J, bits = J0.clone(), sums[:, 1].clone()
+        if report is not None:
+            report(0, J, J < J0, bits)
+        for s in range(1, steps + 1):
+            self.noise_step += 1
+            de = torch.cat([self._latent_grad(c, min(c + LATENT_CHUNK, hi), main_only=True)[1]
+                            for c in range(lo, hi, LATENT_CHUNK)], 0)
+            self._latent_update(lo, hi, de)     # after the last chunk, as latent_step_chunked
+            if s % eval_every == 0 or s == steps:
+                sums = self._block_sums(lo, hi)
+                Js = self._cost(sums)
+                better = Js < J
+                kept = torch.where(better.view(-1, 1, 1, 1, 1), self.emb[lo:hi], kept)
+                J, bits = torch.where(better, Js, J), torch.where(better, sums[:, 1], bits)
+                if report is not None:
+                    report(s, J, J < J0, bits)
+        self.emb[lo:hi] = kept
+        return J0, J
 
     def weight_bits(self):
         """Sum of the 7 quantised kernels' rate terms (identical on every rank): host float, one sync."""

@@ -207,7 +207,8 @@ def account(total_pack):
     info = read_gof_pack(total_pack['gof_pack'])
     bits = [frame_bits(f) for f in total_pack['frames']]
     points = int(sum(info['n_points']))
-    w = 8 * len(total_pack['net_weight_pack']['bit_stream'])
+    # (a latents-only group, nvfpcc_amd.pframe: its 33-byte ref_pack stands where the weights' stream would)
+    w = 8 * (len(total_pack['net_weight_pack']['bit_stream']) if 'net_weight_pack' in total_pack else len(total_pack['ref_pack']))
     lat, side, g = sum(b[0] for b in bits), sum(b[1] for b in bits), 8 * len(total_pack['gof_pack'])
     return {'frames': len(bits), 'points': points, 'weight_bits': w, 'latent_bits': lat, 'side_bits': side, 'gof_bits': g,
             'own_bpp': [(b[0] + b[1]) / float(n) for b, n in zip(bits, info['n_points'])],

@@ -1078,6 +1078,18 @@ def focal_loss_multi(terms, loss_out, chain_sigmoid=True, ctx=None):
     return dps
 
 
+def block_costs(p, gt, dist, alpha, beta, x_rounded, sigma, mu):
+    """float64 [batch, 2]: per block its focal sum over (p, gt, dist-or-None) and its eval-mode latent bits
+    (nvf_block_costs: float32 terms added in float64, one workgroup per block, batch-invariant rows)."""
+    _f32(p, gt, dist, x_rounded, sigma, mu)
+    B = p.shape[0]
+    out = torch.empty(B, 2, dtype=torch.float64, device=p.device)
+    check(lib().nvf_block_costs(_ptr(p), _ptr(gt), _ptr(dist), float(alpha), float(beta), _ptr(x_rounded), _ptr(sigma),
+                                _ptr(mu), _ptr(out), B, p[0].numel(), x_rounded.shape[1], x_rounded[0, 0].numel(),
+                                _stream()), "nvf_block_costs")
+    return out
+
+
 def metrics(p, gt, dist, thh_acc, thh_sse, out=None, accumulate=False, ctx=None):
     """out[0..5] (+)= tp, ap, tn, an at thh_acc; sse, denom at thh_sse (utils/loss.py:74-84, 113-121).  With ``ctx``
     (an open StepCtx.begin) the final pass joins the deferred ones: ``out`` exists after ctx.flush()."""
