@@ -22,6 +22,8 @@ engine (nvfpcc_amd/engine.py) instead of a DataLoader + autograd loop.
     python NVFPCC.py encode ... --lossless_lod                                 # the occupancy coarse to fine (lossless_lod_pack)
     python NVFPCC.py encode ... --lossless_lod --lossless_ctx nbr              # the voxels under their parents' neighbours
     python NVFPCC.py decode pack.pk --lossless_lod 0|1|2 ...                   # exact at 32^3, 16^3 or 8^3 per block
+    python NVFPCC.py encode ... --lossless_lod --lossless_ctx inter --lossless_ref prev/rc_dec.ply   # the voxels under a cloud both sides hold
+    python NVFPCC.py decode pack.pk --lossless_lod 0|1|2 --lossless_ref prev/rc_dec.ply ...          # the same reference decodes it
     python NVFPCC.py train seq_%04d.ply --gof 8 --frame_start 1300 ...         # one decoder for frames 1300 .. 1307
     python NVFPCC.py encode seq_%04d.ply --gof 8 --frame_start 1300 ...        # one pack: the weights once, a frame pack each
     python NVFPCC.py decode pack.pk --frame 1303 ...                           # that frame alone; without --frame, all of them
@@ -29,7 +31,7 @@ engine (nvfpcc_amd/engine.py) instead of a DataLoader + autograd loop.
     python NVFPCC.py encode next.ply --load_weights q4.ckpt --ref_pack ref.pk  # a latents-only pack: 33 bytes name ref.pk's decoder
     python NVFPCC.py decode p.pk --ref_pack ref.pk ...                         # decoded under the reference's weights
 
-Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --ply_format, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --lossless_lod, --lossless_ctx, --gof, --frame_start, --frame, --freeze_decoder, --ref_pack, --thh_mode (count | block-count | d1:
+Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --ply_format, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --lossless_lod, --lossless_ctx, --lossless_ref, --gof, --frame_start, --frame, --freeze_decoder, --ref_pack, --thh_mode (count | block-count | d1:
 nvfpcc_amd/thh_select.py picks the occupancy threshold at encode time and a `thh_pack` key carries it); multi-GPU training when launched
 through torch.distributed.run (one process per GPU, leaf blocks sharded, one RCCL all-reduce per step).
 Headless: no GUI window, no IPython shell.
@@ -480,10 +482,15 @@ def _encode_lossless_lod(args, total_pack, data, dev, batch):
     """encode --lossless_lod: as _encode_lossless, with the coarse-to-fine coder (nvfpcc_amd.lossless_lod_pack).  The
     stream is decoded again at all three levels: a pack that does not reproduce the input's occupancy and its two
     max-pools is not written.  --lossless_ctx nbr: the voxels under their parents' neighbours
-    (nvfpcc_amd.lossless_nbr_pack), the same key.  -> {'pack': lossless_lod_pack bytes, 'line': the [LosslessLoD] line}."""
+    (nvfpcc_amd.lossless_nbr_pack), the same key.  --lossless_ctx inter: under the cloud of --lossless_ref as well
+    (nvfpcc_amd.lossless_inter_pack), rasterised onto this frame's blocks; the same key again.
+    -> {'pack': lossless_lod_pack bytes, 'line': the [LosslessLoD] line}."""
     import contextlib
     import io
-    if getattr(args, 'lossless_ctx', 'field') == 'nbr':
+    ctx = getattr(args, 'lossless_ctx', 'field')
+    if ctx == 'inter':
+        from nvfpcc_amd import lossless_inter_pack as lp
+    elif ctx == 'nbr':
         from nvfpcc_amd import lossless_nbr_pack as lp
     else:
         from nvfpcc_amd import lossless_lod_pack as lp
@@ -491,17 +498,32 @@ def _encode_lossless_lod(args, total_pack, data, dev, batch):
         net, latents = _decoder_from_pack(args, total_pack, dev)
     latents = latents[:data.N_leaf].contiguous()
     gt, _ = data.to_device(dev)
+    ref, ref_line = (), None
+    if ctx == 'inter':
+        ref, ref_line = _lossless_reference(args.lossless_ref, np.array([data.origins[i] for i in range(len(data))]), dev)
     try:
-        pack, info = lp.encode_occupancy(net, latents, gt, batch=batch, group=lp.GROUP)
+        pack, info = lp.encode_occupancy(net, latents, gt, *ref, batch=batch, group=lp.GROUP)
         for level in (2, 1, 0):
-            words, counts = lp.decode_occupancy(net, latents, pack, level=level, batch=batch)
+            words, counts = lp.decode_occupancy(net, latents, pack, *ref, level=level, batch=batch)
             if not torch.equal(words, info['gt_words'][level]) or (level == 0 and int(counts.sum().item()) != int(data.N)):
                 raise SystemExit(f"encode --lossless_lod: the stream does not decode to the input's occupancy at level "
                                  f"{level}; no pack written")
     except ValueError as e:
         raise SystemExit(f"encode --lossless_lod: {e}")
-    return {'pack': pack, 'line': lp.lossless_lod_line(len(pack), data.N, info['ideal_bits'], info['contexts'],
-                                                       info['symbols'], lp.GROUP)}
+    line = lp.lossless_lod_line(len(pack), data.N, info['ideal_bits'], info['contexts'], info['symbols'], lp.GROUP)
+    return {'pack': pack, 'line': line if ref_line is None else line + '\n' + ref_line}
+
+
+def _lossless_reference(fn, origins, dev):
+    """--lossless_ref: the cloud of `fn` (ASCII or binary PLY) rasterised onto the blocks at `origins`
+    -> ((the reference words on the device,), the [LosslessLoD] line that says what was read)."""
+    from nvfpcc_amd import lossless_inter_pack, ply_io
+    try:
+        pts = np.asarray(ply_io.read_ply(fn)[0])
+    except (OSError, ValueError) as e:
+        raise SystemExit(f"--lossless_ref {fn}: {e}")
+    words, dropped = lossless_inter_pack.reference_words(np.rint(pts).astype(np.int64), np.asarray(origins, np.int64), dev)
+    return (words,), '[LosslessLoD] reference: %s points: %d dropped: %d' % (fn, pts.shape[0], dropped)
 
 
 def _encode_lod(args, net, latents, data, origins, dev, batch):
@@ -666,11 +688,21 @@ def _decode_pack(args, total_pack, dev, fmt, net, out_fn):
         pts = lp.points_from_words(words, counts, origins)
         print('[Lossless] points: %d' % pts.shape[0])
     elif getattr(args, 'lossless_lod', None) is not None:   # the input's voxels, or their exact 2^3 / 4^3 max-pool
-        from nvfpcc_amd import lossless_nbr_pack
+        from nvfpcc_amd import lossless_inter_pack
         level = int(args.lossless_lod)
         try:
-            llp = lossless_nbr_pack.module_of(total_pack['lossless_lod_pack'])     # byte 0: which contexts coded it
-            words, counts = llp.decode_occupancy(net, latents, total_pack['lossless_lod_pack'], level=level, batch=batch)
+            llp = lossless_inter_pack.module_of(total_pack['lossless_lod_pack'])   # byte 0: which contexts coded it
+            ref = ()
+            if llp is lossless_inter_pack:
+                if not hasattr(args, 'lossless_ref'):
+                    raise SystemExit(f"decode --lossless_lod {level}: the lossless_lod_pack of {args.input} was coded under "
+                                     f"a reference cloud (--lossless_ctx inter); name that cloud with --lossless_ref")
+                ref, ref_line = _lossless_reference(args.lossless_ref, np.asarray(origins, np.int64), dev)
+                print(ref_line)
+            elif hasattr(args, 'lossless_ref'):
+                print(f'[Info] the lossless_lod_pack of {args.input} refers to no other cloud; --lossless_ref '
+                      f'{args.lossless_ref} is not read')
+            words, counts = llp.decode_occupancy(net, latents, total_pack['lossless_lod_pack'], *ref, level=level, batch=batch)
         except ValueError as e:
             raise SystemExit(f"decode --lossless_lod {level}: {e}")
         pts = llp.points_from_words(words, counts, origins, level)
@@ -735,10 +767,21 @@ def lossless_refusals(args, total_pack):
 
 
 def lossless_ctx_refusals(args):
-    """encode --lossless_ctx: it chooses the contexts of --lossless_lod and means nothing without it."""
+    """encode --lossless_ctx: it chooses the contexts of --lossless_lod and means nothing without it; the contexts
+    `inter` and the cloud of --lossless_ref come together, and not inside a group of frames."""
     if hasattr(args, 'lossless_ctx') and getattr(args, 'lossless_lod', None) is None:
         raise SystemExit(f"encode: --lossless_ctx {args.lossless_ctx} chooses the contexts of --lossless_lod; give "
                          f"--lossless_lod too")
+    inter = getattr(args, 'lossless_ctx', None) == 'inter'
+    if inter and not hasattr(args, 'lossless_ref'):
+        raise SystemExit("encode: --lossless_ctx inter codes the voxels under a reference cloud; name it with "
+                         "--lossless_ref (the previous frame's rc_dec.ply, say)")
+    if hasattr(args, 'lossless_ref') and not inter:
+        raise SystemExit(f"encode: --lossless_ref {args.lossless_ref} is the reference of --lossless_ctx inter; give "
+                         f"--lossless_lod --lossless_ctx inter too")
+    if inter and hasattr(args, 'gof'):
+        raise SystemExit("encode: --gof and --lossless_ctx inter exclude each other: a frame that refers to its "
+                         "predecessor inside a group is not coded; encode the frames one by one with --lossless_ref")
 
 
 def lossless_lod_refusals(args, total_pack):
@@ -862,10 +905,16 @@ def build_parser():
                         'Gross bpp).  decode --lossless_lod L: write exactly the input\'s voxels (0) or exactly their '
                         'reduction to bits - L bits per axis (1, 2) to rc_dec.ply, from a prefix of the same stream; '
                         'excludes --lod and --lossless.')
-    p.add_argument('--lossless_ctx', choices=['field', 'nbr'], default=argparse.SUPPRESS,
+    p.add_argument('--lossless_ctx', choices=['field', 'nbr', 'inter'], default=argparse.SUPPRESS,
                    help='encode --lossless_lod: the contexts of the voxels.  field (the default): the decoder\'s field '
                         'alone.  nbr: also the exact 16^3 occupancy of the parent cell\'s neighbours, which the decoder '
-                        'holds before the first voxel (fewer bits; decode tells the two apart by the pack).')
+                        'holds before the first voxel (fewer bits; decode tells the two apart by the pack).  inter: '
+                        'also the cloud of --lossless_ref, which both sides hold (far fewer bits where the scene stands '
+                        'still; decode needs the same cloud).')
+    p.add_argument('--lossless_ref', default=argparse.SUPPRESS,
+                   help='encode --lossless_lod --lossless_ctx inter / decode --lossless_lod of such a pack: the reference '
+                        'cloud (ASCII or binary PLY), normally the previous frame\'s rc_dec.ply.  The pack carries a '
+                        'digest of it on this frame\'s blocks: decode refuses any other cloud.')
     p.add_argument('--gof', type=int, default=argparse.SUPPRESS,
                    help='train / encode: a group of F frames under one decoder.  `input` is then the pattern of their '
                         'names with one %%d or %%0<n>d (seq_%%04d.ply); the frames are numbered from --frame_start.  encode '

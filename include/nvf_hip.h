@@ -1022,6 +1022,44 @@ int nvf_occ_nbr_decode(const float* p, const uint8_t* k1, const int32_t* cells1,
                        const uint32_t* nwords, int64_t total_words, int batch, int group, uint64_t* occ_words,
                        int32_t* status, void* stream);
 
+/* ---- scalable lossless geometry, inter contexts (nvfpcc_amd/lossless_inter_pack.py, csrc/occ_hier.hip) --------------
+ * A third context model for the same stream: a voxel is coded under a REFERENCE cloud that encoder and decoder both
+ * hold (the previous frame's decoded output, say) as well.  Everything but the context of a level-0 symbol is as above.
+ * R, the reference words: uint64 [batch, 512] in the format of gt_w0, the reference rasterised onto THIS frame's blocks.
+ * R(q) is the reference occupancy of voxel q of the SAME block, 0 outside [0, 32)^3.  For a voxel v = (z, y, x):
+ *   a = R(v), f = the sum of R over the six face neighbours of v, r = a ? 2 : (f > 0 ? 1 : 0)   the temporal class
+ *   F, E, C as for the neighbour contexts, s = (F * 2 + (E > 0)) * 2 + C in [0, 16)               the spatial class
+ *   t = r * 16 + s in [0, 48), ctx = 3072 + (t * 4 + k) * 256 + occ_ctx(p[v]), k = K1[parent]
+ * NVF_OCC_INTER_CONTEXTS = 3072 + 48 * 1024; contexts 0..1023 are never used.  f1 is int32 [NVF_OCC_INTER_CONTEXTS] on
+ * the device, 16-byte aligned, entries pulled into [1, 65535].
+ * nvf_occ_ref_words: points int32 [npts, 3] -> words uint64 [nblocks, 512], which the caller has cleared (bits are ORed
+ *   in, so calls accumulate).  A point q belongs to the block whose origin is q & ~31 and sets the bit of voxel
+ *   ((q[0] & 31) * 32 + (q[1] & 31)) * 32 + (q[2] & 31) there.  keys int64 [nblocks]: the blocks' origin keys
+ *   (o[0] >> 5) << 42 | (o[1] >> 5) << 21 | (o[2] >> 5), origins in [0, 2^NVF_OCC_REF_COORD_BITS), sorted ascending and
+ *   distinct; perm int32 [nblocks]: perm[i] = the block whose key is keys[i].  dropped[0] += the points under no block,
+ *   a point with a coordinate outside [0, 2^NVF_OCC_REF_COORD_BITS) among them (uint64, cleared by the caller).
+ *   Duplicate points are harmless; no content of points, keys or perm makes the kernel write outside words.
+ * nvf_occ_inter_hist: the level-0 symbols, as nvf_occ_nbr_hist with ref_words; cnt / occ uint64 [NVF_OCC_INTER_CONTEXTS].
+ * nvf_occ_inter_encode: the arguments and results of nvf_occ_nbr_encode, with ref_words and the longer f1.
+ * nvf_occ_inter_decode: section 0 of every group, as nvf_occ_nbr_decode with ref_words (every guarantee about damaged
+ *   streams holds).  Sections 2 and 1 are decoded by nvf_occ_hier_decode under the first NVF_OCC_HIER_CONTEXTS entries. */
+#define NVF_OCC_INTER_CONTEXTS 52224
+#define NVF_OCC_REF_COORD_BITS 26
+int nvf_occ_ref_words(const int32_t* points, int64_t npts, const int64_t* keys, const int32_t* perm, int nblocks,
+                      uint64_t* words, uint64_t* dropped, void* stream);
+int nvf_occ_inter_hist(const float* p, const uint8_t* k1, const uint64_t* gt_w0, const uint64_t* gt_w1,
+                       const uint64_t* ref_words, const int32_t* cells1, const int32_t* counts1, int batch, uint64_t* cnt,
+                       uint64_t* occ, void* stream);
+int nvf_occ_inter_encode(const float* p, const float* p1, const uint8_t* k1, const float* p2, const uint8_t* k2,
+                         const uint64_t* gt_w0, const uint64_t* gt_w1, const uint64_t* gt_w2, const uint64_t* ref_words,
+                         const int32_t* cells2, const int32_t* counts2, const int32_t* cells1, const int32_t* counts1,
+                         const int32_t* f1, int batch, int group, uint64_t* states, uint32_t* words, uint32_t* nwords,
+                         void* stream);
+int nvf_occ_inter_decode(const float* p, const uint8_t* k1, const int32_t* cells1, const int32_t* counts1, const uint64_t* w1,
+                         const uint64_t* ref_words, const int32_t* f1, uint64_t* states, int64_t* pos, const uint32_t* words,
+                         const int64_t* word_off, const uint32_t* nwords, int64_t total_words, int batch, int group,
+                         uint64_t* occ_words, int32_t* status, void* stream);
+
 /* ---- pre-processing on the device (nvfpcc_amd/preprocess.py: preprocess_device, csrc/pp_device.hip) ----------------
  * From int32 [P,3] points with coordinates of `bits` bits (10, 11 or 12; anything else is NVF_EINVAL) to everything
  * nvf_nearest_dist2 and the trainer take, without a host pass.  D = bits - 5 is the level of the 32^3 leaves.  A CELL

@@ -27,15 +27,32 @@
 // to the 3072 uint32 entries the other two sections use; the histogram counts a block in ONE uint32 per context, symbols
 // in the low half and occupied ones in the high half (128 KiB): a block codes at most 32768 voxels, so neither half
 // can carry.
+//
+//   nvf_occ_ref_words      a reference cloud rasterised onto this frame's blocks: one thread per point, a binary search
+//                          of its block among the sorted origin keys, an integer OR of one bit
+//   nvf_occ_inter_hist / _encode / _decode   the third context model (INTER below).  Sections 2 and 1 are the first model's
+//
+// INTER: the level-0 contexts are t = r * 16 + s in [0, 48): r in {0, 1, 2} from the reference words R of the SAME block
+// (2: the voxel itself is in the reference, 1: a face neighbour of it is, 0: neither), s in [0, 16) the neighbour class
+// with the edge count folded to a bit, (F * 2 + (E > 0)) * 2 + C.  R is read as uint32 rows of 32 voxels along x, five
+// per voxel: its own, z - 1, z + 1, y - 1, y + 1 (a row outside the block is empty), gathered with the probabilities
+// ahead of the chain.  The 48 x 1024 level-0 frequencies sit in LDS as uint16 (96 KiB) next to the 12 KiB of the other
+// sections; the histogram runs one workgroup per (block, r) over the block's symbols and counts those of its r in one
+// uint32 per context (16384 of them, 64 KiB), as NBR does.
 #include "occ_coder.h"
 
 #define HIER_CTX 3072                                  // 3 levels x 4 child counts x 256
 #define NBR_CTX0 32768                                 // 32 neighbour classes x 4 child counts x 256, from context 3072 on
+#define INTER_CTX0 49152                               // 3 temporal x 16 spatial classes x 4 child counts x 256
+#define INTER_CTX_R 16384                              // the level-0 contexts of one temporal class
 #define HIER_AHEAD 8
 #define HIER_BLOCK_WORDS NVF_OCC_HIER_BLOCK_WORDS      // 512 + 4096 + 32768: an all-full block
 #define HIER_THREADS 1024
 
 namespace {
+
+// the context model of a level-0 symbol: the field alone, with the parent's neighbours, with a reference cloud as well
+enum HierCtx { CTX_FIELD = 0, CTX_NBR = 1, CTX_INTER = 2 };
 
 __device__ __forceinline__ int hier_wave_sum(int v) {
 #pragma unroll
@@ -103,14 +120,47 @@ __device__ __forceinline__ int nbr_class(const NbrRows& r, int e, int j) {
   return (int)((F * 4u + E) * 2u + ((r.r11 >> xs) & in));
 }
 
+// the five rows of 32 reference voxels a voxel's temporal class is read from; a row outside the block is empty
+struct InterRows {
+  uint32_t own, zm, zp, ym, yp;
+};
+
+__device__ __forceinline__ uint32_t inter_row(const uint32_t* __restrict__ ref, int b, int z, int y) {
+  const bool in = (unsigned)z < 32u && (unsigned)y < 32u;
+  const uint32_t r = ref[(size_t)b * 1024 + (in ? z * 32 + y : 0)];
+  return in ? r : 0u;
+}
+
+// cell = block * 32768 + voxel (hier_where's cell at level 0)
+__device__ __forceinline__ InterRows inter_gather(const uint32_t* __restrict__ ref, int cell) {
+  const int b = cell >> 15, z = (cell >> 10) & 31, y = (cell >> 5) & 31;
+  return InterRows{inter_row(ref, b, z, y), inter_row(ref, b, z - 1, y), inter_row(ref, b, z + 1, y),
+                   inter_row(ref, b, z, y - 1), inter_row(ref, b, z, y + 1)};
+}
+
+// r = 2: the voxel is in the reference; 1: one of its six face neighbours is; 0: neither.  x = the voxel's x
+__device__ __forceinline__ int inter_temporal(const InterRows& q, int x) {
+  const unsigned long long o = q.own;                  // 64 bits: x - 1 = -1 and x + 1 = 32 read zeros
+  const unsigned long long faces = ((unsigned long long)(q.zm | q.zp | q.ym | q.yp) | (o >> 1) | (o << 1)) >> x;
+  return ((q.own >> x) & 1u) ? 2 : (int)(faces & 1ull);
+}
+
+// t = r * 16 + s, s = (F * 2 + (E > 0)) * 2 + C: the neighbour class n = F << 3 | E << 1 | C with E folded to a bit
+__device__ __forceinline__ int inter_class(const InterRows& q, const NbrRows& r, int e, int j, int x) {
+  const int n = nbr_class(r, e, j);
+  return inter_temporal(q, x) * 16 + ((n >> 3) * 2 + ((n & 6) ? 1 : 0)) * 2 + (n & 1);
+}
+
 // index into the level-0 frequencies: context - 3072
 __device__ __forceinline__ int nbr_ctx0(int n, int k, float v) { return (n * 4 + (k & 3)) * OCC_CTX + occ_ctx(v); }
 
-// the NBR_CTX0 level-0 frequencies f0 (16-byte aligned) as uint16 in LDS, pulled into [1, 65535].  One wave.
+// the N (NBR_CTX0 or INTER_CTX0) level-0 frequencies f0 (16-byte aligned) as uint16 in LDS, pulled into [1, 65535].
+// One wave.
+template <int N = NBR_CTX0>
 __device__ __forceinline__ void nbr_load_table(const int32_t* __restrict__ f0, uint16_t* tab0, int lane) {
   const auto pull = [](int v) { return (uint32_t)(v < 1 ? 1 : (v > 65535 ? 65535 : v)); };
 #pragma unroll 8
-  for (int i = lane * 4; i < NBR_CTX0; i += 256) {
+  for (int i = lane * 4; i < N; i += 256) {
     const int4 v = *(const int4*)(f0 + i);
     *(uint2*)(tab0 + i) = make_uint2(pull(v.x) | (pull(v.y) << 16), pull(v.z) | (pull(v.w) << 16));
   }
@@ -286,16 +336,19 @@ __global__ __launch_bounds__(HIER_THREADS) void nbr_hist_kernel(const float* __r
   }
 }
 
-// one section of a group, backwards.  The words written so far are wg[ptr .. region).  NBR (level 0 only): the
-// frequency comes from tab0 under the neighbour class read from `rows`, the ground truth's level-1 words.
-template <int LEVEL, bool NBR = false>
+// one section of a group, backwards.  The words written so far are wg[ptr .. region).  CTX_NBR (level 0 only): the
+// frequency comes from tab0 under the neighbour class read from `rows`, the ground truth's level-1 words.  CTX_INTER:
+// under the temporal class read from `ref`, the reference words, as well.
+template <int LEVEL, HierCtx CTX = CTX_FIELD>
 __device__ __forceinline__ void hier_encode_section(int n, const int32_t* __restrict__ parents, int b0,
                                                     const float* __restrict__ pv, const uint8_t* __restrict__ kv,
                                                     const unsigned long long* __restrict__ gw, const uint32_t* tab,
                                                     int lane, unsigned long long& x, int& ptr, uint32_t* __restrict__ wg,
                                                     const uint16_t* __restrict__ rows = nullptr,
-                                                    const uint16_t* tab0 = nullptr) {
-  static_assert(!NBR || LEVEL == 0, "only voxels have neighbour contexts");
+                                                    const uint16_t* tab0 = nullptr,
+                                                    const uint32_t* __restrict__ ref = nullptr) {
+  static_assert(CTX == CTX_FIELD || LEVEL == 0, "only voxels have neighbour contexts");
+  constexpr bool NBR = CTX != CTX_FIELD, INTER = CTX == CTX_INTER;
   const int steps = (n + 63) >> 6;
   for (int t0 = (steps + HIER_AHEAD - 1) / HIER_AHEAD * HIER_AHEAD - HIER_AHEAD; t0 >= 0; t0 -= HIER_AHEAD) {
     float val[HIER_AHEAD];
@@ -303,6 +356,7 @@ __device__ __forceinline__ void hier_encode_section(int n, const int32_t* __rest
     unsigned long long gword[HIER_AHEAD];
     NbrRows nr[NBR ? HIER_AHEAD : 1];
     int ee[NBR ? HIER_AHEAD : 1];
+    InterRows ir[INTER ? HIER_AHEAD : 1];
 #pragma unroll
     for (int k = 0; k < HIER_AHEAD; ++k) {
       const int i = (t0 + k) * 64 + lane;
@@ -316,12 +370,14 @@ __device__ __forceinline__ void hier_encode_section(int n, const int32_t* __rest
         nr[k] = nbr_gather(rows, kcell, lane & 7);     // i & 7: a step is 64 symbols
         ee[k] = kcell;
       }
+      if constexpr (INTER) ir[k] = inter_gather(ref, cell);
     }
     uint32_t fr[HIER_AHEAD], st[HIER_AHEAD];           // fr = 0: an idle lane
 #pragma unroll
     for (int k = 0; k < HIER_AHEAD; ++k) {
       uint32_t one;
-      if constexpr (NBR) one = tab0[nbr_ctx0(nbr_class(nr[k], ee[k], lane & 7), kk[k], val[k])];
+      if constexpr (INTER) one = tab0[nbr_ctx0(inter_class(ir[k], nr[k], ee[k], lane & 7, bit[k] & 31), kk[k], val[k])];
+      else if constexpr (NBR) one = tab0[nbr_ctx0(nbr_class(nr[k], ee[k], lane & 7), kk[k], val[k])];
       else one = tab[hier_ctx(LEVEL, kk[k], val[k])];
       const bool s = (gword[k] >> bit[k]) & 1ull;
       const bool live = (t0 + k) * 64 + lane < n;
@@ -334,8 +390,9 @@ __device__ __forceinline__ void hier_encode_section(int n, const int32_t* __rest
   }
 }
 
-// one wave per group.  NBR: section 0 under the neighbour contexts, f1 holds NVF_OCC_NBR_CONTEXTS entries
-template <bool NBR>
+// one wave per group.  CTX_NBR: section 0 under the neighbour contexts, f1 holds NVF_OCC_NBR_CONTEXTS entries;
+// CTX_INTER: under the inter contexts, f1 holds NVF_OCC_INTER_CONTEXTS entries and ref the reference words
+template <HierCtx CTX>
 __global__ __launch_bounds__(64) void hier_encode_kernel(const float* __restrict__ p, const float* __restrict__ p1,
                                                          const uint8_t* __restrict__ k1, const float* __restrict__ p2,
                                                          const uint8_t* __restrict__ k2,
@@ -346,14 +403,16 @@ __global__ __launch_bounds__(64) void hier_encode_kernel(const float* __restrict
                                                          const int32_t* __restrict__ cells1, const int32_t* __restrict__ counts1,
                                                          const int32_t* __restrict__ f1, int batch, int G,
                                                          unsigned long long* __restrict__ states, uint32_t* __restrict__ words,
-                                                         uint32_t* __restrict__ nwords) {
+                                                         uint32_t* __restrict__ nwords,
+                                                         const uint32_t* __restrict__ ref = nullptr) {
   __shared__ uint32_t tab[HIER_CTX];
   const int lane = threadIdx.x, g = blockIdx.x;
   occ_load_table<HIER_CTX>(f1, tab, lane);
   const uint16_t* tab0 = nullptr;
-  if constexpr (NBR) {
-    __shared__ __attribute__((aligned(16))) uint16_t t0[NBR_CTX0];
-    nbr_load_table(f1 + HIER_CTX, t0, lane);
+  if constexpr (CTX != CTX_FIELD) {
+    constexpr int N0 = CTX == CTX_INTER ? INTER_CTX0 : NBR_CTX0;
+    __shared__ __attribute__((aligned(16))) uint16_t t0[N0];
+    nbr_load_table<N0>(f1 + HIER_CTX, t0, lane);
     tab0 = t0;
   }
   const int b0 = g * G, nb = min(G, batch - b0);
@@ -361,8 +420,8 @@ __global__ __launch_bounds__(64) void hier_encode_kernel(const float* __restrict
   uint32_t* wg = words + (size_t)g * G * HIER_BLOCK_WORDS;
   unsigned long long x = OCC_RANS_L;
   int ptr = region;
-  hier_encode_section<0, NBR>(8 * hier_sum(counts1, b0, b0 + nb, lane), cells1 + hier_sum(counts1, 0, b0, lane), b0, p, k1,
-                              w0, tab, lane, x, ptr, wg, (const uint16_t*)w1, tab0);
+  hier_encode_section<0, CTX>(8 * hier_sum(counts1, b0, b0 + nb, lane), cells1 + hier_sum(counts1, 0, b0, lane), b0, p, k1,
+                              w0, tab, lane, x, ptr, wg, (const uint16_t*)w1, tab0, ref);
   hier_encode_section<1>(8 * hier_sum(counts2, b0, b0 + nb, lane), cells2 + hier_sum(counts2, 0, b0, lane), b0, p1, k1, w1,
                          tab, lane, x, ptr, wg);
   hier_encode_section<2>(nb * 512, nullptr, b0, p2, k2, w2, tab, lane, x, ptr, wg);
@@ -370,9 +429,10 @@ __global__ __launch_bounds__(64) void hier_encode_kernel(const float* __restrict
   if (lane == 0) nwords[g] = (uint32_t)(region - ptr);
 }
 
-// one section of a group, forwards: what the decoder kernels below share.  NBR (level 0 only): the frequency comes
-// from tab0 under the neighbour class read from `rows`, the level-1 words section 1 decoded.
-template <int LEVEL, bool NBR>
+// one section of a group, forwards: what the decoder kernels below share.  CTX_NBR (level 0 only): the frequency comes
+// from tab0 under the neighbour class read from `rows`, the level-1 words section 1 decoded.  CTX_INTER: under the
+// temporal class read from `ref`, the reference words, as well.
+template <int LEVEL, HierCtx CTX>
 __device__ __forceinline__ void hier_decode_group(const float* __restrict__ pv, const uint8_t* __restrict__ kv,
                                                   const int32_t* __restrict__ cells, const int32_t* __restrict__ counts,
                                                   const uint32_t* tab, const uint16_t* tab0,
@@ -382,8 +442,10 @@ __device__ __forceinline__ void hier_decode_group(const float* __restrict__ pv, 
                                                   const long long* __restrict__ word_off,
                                                   const uint32_t* __restrict__ nwords, long long total_words,
                                                   int batch, int G, unsigned long long* __restrict__ occ_words,
-                                                  int32_t* __restrict__ status) {
-  static_assert(!NBR || LEVEL == 0, "only voxels have neighbour contexts");
+                                                  int32_t* __restrict__ status,
+                                                  const uint32_t* __restrict__ ref = nullptr) {
+  static_assert(CTX == CTX_FIELD || LEVEL == 0, "only voxels have neighbour contexts");
+  constexpr bool NBR = CTX != CTX_FIELD, INTER = CTX == CTX_INTER;
   const int lane = threadIdx.x, g = blockIdx.x;
   const int b0 = g * G, nb = min(G, batch - b0);
   // a stop before level 0 needs only a prefix of the group's words: there the cut alone is no damage
@@ -402,6 +464,7 @@ __device__ __forceinline__ void hier_decode_group(const float* __restrict__ pv, 
     int kk[HIER_AHEAD], where[HIER_AHEAD];
     NbrRows nr[NBR ? HIER_AHEAD : 1];
     int ee[NBR ? HIER_AHEAD : 1];
+    InterRows ir[INTER ? HIER_AHEAD : 1];
 #pragma unroll
     for (int k = 0; k < HIER_AHEAD; ++k) {
       const int i = (t0 + k) * 64 + lane;
@@ -414,11 +477,13 @@ __device__ __forceinline__ void hier_decode_group(const float* __restrict__ pv, 
         nr[k] = nbr_gather(rows, kcell, lane & 7);     // i & 7: a step is 64 symbols
         ee[k] = kcell;
       }
+      if constexpr (INTER) ir[k] = inter_gather(ref, cell);
     }
     uint32_t one[HIER_AHEAD];
 #pragma unroll
     for (int k = 0; k < HIER_AHEAD; ++k) {
-      if constexpr (NBR) one[k] = tab0[nbr_ctx0(nbr_class(nr[k], ee[k], lane & 7), kk[k], val[k])];
+      if constexpr (INTER) one[k] = tab0[nbr_ctx0(inter_class(ir[k], nr[k], ee[k], lane & 7, where[k] & 31), kk[k], val[k])];
+      else if constexpr (NBR) one[k] = tab0[nbr_ctx0(nbr_class(nr[k], ee[k], lane & 7), kk[k], val[k])];
       else one[k] = tab[hier_ctx(LEVEL, kk[k], val[k])];
     }
 #pragma unroll
@@ -454,7 +519,7 @@ __global__ __launch_bounds__(64) void hier_decode_kernel(const float* __restrict
                                                          int32_t* __restrict__ status) {
   __shared__ uint32_t tab[HIER_CTX];
   occ_load_table<HIER_CTX>(f1, tab, threadIdx.x);
-  hier_decode_group<LEVEL, false>(pv, kv, cells, counts, tab, nullptr, nullptr, states, pos_io, words, word_off, nwords,
+  hier_decode_group<LEVEL, CTX_FIELD>(pv, kv, cells, counts, tab, nullptr, nullptr, states, pos_io, words, word_off, nwords,
                                   total_words, batch, G, occ_words, status);
 }
 
@@ -470,8 +535,95 @@ __global__ __launch_bounds__(64) void nbr_decode_kernel(const float* __restrict_
                                                         int32_t* __restrict__ status) {
   __shared__ __attribute__((aligned(16))) uint16_t tab0[NBR_CTX0];
   nbr_load_table(f0, tab0, threadIdx.x);
-  hier_decode_group<0, true>(p, k1, cells1, counts1, nullptr, tab0, rows, states, pos_io, words, word_off, nwords,
-                             total_words, batch, G, occ_words, status);
+  hier_decode_group<0, CTX_NBR>(p, k1, cells1, counts1, nullptr, tab0, rows, states, pos_io, words, word_off, nwords,
+                                total_words, batch, G, occ_words, status);
+}
+
+// section 0 of every group under the inter contexts: nbr_decode_kernel with the reference words
+__global__ __launch_bounds__(64) void inter_decode_kernel(const float* __restrict__ p, const uint8_t* __restrict__ k1,
+                                                          const int32_t* __restrict__ cells1, const int32_t* __restrict__ counts1,
+                                                          const uint16_t* __restrict__ rows, const uint32_t* __restrict__ ref,
+                                                          const int32_t* __restrict__ f0,
+                                                          unsigned long long* __restrict__ states, long long* __restrict__ pos_io,
+                                                          const uint32_t* __restrict__ words,
+                                                          const long long* __restrict__ word_off,
+                                                          const uint32_t* __restrict__ nwords, long long total_words,
+                                                          int batch, int G, unsigned long long* __restrict__ occ_words,
+                                                          int32_t* __restrict__ status) {
+  __shared__ __attribute__((aligned(16))) uint16_t tab0[INTER_CTX0];
+  nbr_load_table<INTER_CTX0>(f0, tab0, threadIdx.x);
+  hier_decode_group<0, CTX_INTER>(p, k1, cells1, counts1, nullptr, tab0, rows, states, pos_io, words, word_off, nwords,
+                                  total_words, batch, G, occ_words, status, ref);
+}
+
+// a reference cloud onto the blocks: one thread per point.  keys: the blocks' origin keys ascending, perm[i] the block
+// whose key is keys[i].  A point under no block (or outside the key's range) is counted in dropped[0].
+__device__ __forceinline__ long long ref_key(int q0, int q1, int q2) {
+  return ((long long)(q0 >> 5) << 42) | ((long long)(q1 >> 5) << 21) | (long long)(q2 >> 5);
+}
+
+__global__ __launch_bounds__(256) void ref_words_kernel(const int32_t* __restrict__ pts, long long npts,
+                                                        const long long* __restrict__ keys, const int32_t* __restrict__ perm,
+                                                        int nblocks, unsigned long long* __restrict__ words,
+                                                        unsigned long long* __restrict__ dropped) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  bool drop = false;
+  if (i < npts) {
+    const int q0 = pts[3 * i], q1 = pts[3 * i + 1], q2 = pts[3 * i + 2];
+    drop = true;
+    if ((unsigned)q0 < (1u << NVF_OCC_REF_COORD_BITS) && (unsigned)q1 < (1u << NVF_OCC_REF_COORD_BITS) &&
+        (unsigned)q2 < (1u << NVF_OCC_REF_COORD_BITS)) {
+      const long long key = ref_key(q0, q1, q2);
+      int lo = 0, hi = nblocks;                        // the first entry >= key
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (keys[mid] < key) lo = mid + 1; else hi = mid;
+      }
+      if (lo < nblocks && keys[lo] == key) {
+        const int b = perm[lo];
+        if ((unsigned)b < (unsigned)nblocks) {         // a permutation cannot fail this; no content of perm writes outside
+          const int v = ((q0 & 31) * 32 + (q1 & 31)) * 32 + (q2 & 31);
+          atomicOr(&words[(size_t)b * 512 + (v >> 6)], 1ull << (v & 63));   // integer OR: any order, the same words
+          drop = false;
+        }
+      }
+    }
+  }
+  const unsigned long long m = __ballot(drop);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(dropped, (unsigned long long)__popcll(m));
+}
+
+// the level-0 symbols of one block under the inter contexts: one workgroup per (block, temporal class r = blockIdx.y),
+// which counts the symbols of its r alone, one uint32 per context as nbr_hist_kernel
+__global__ __launch_bounds__(HIER_THREADS) void inter_hist_kernel(const float* __restrict__ p, const uint8_t* __restrict__ k1,
+                                                                  const unsigned long long* __restrict__ w0,
+                                                                  const uint16_t* __restrict__ rows,
+                                                                  const uint32_t* __restrict__ ref,
+                                                                  const int32_t* __restrict__ cells1,
+                                                                  const int32_t* __restrict__ counts1,
+                                                                  unsigned long long* __restrict__ cnt,
+                                                                  unsigned long long* __restrict__ occ) {
+  __shared__ uint32_t h[INTER_CTX_R];                  // occupied << 16 | symbols, each <= 32768
+  const int tid = threadIdx.x, b = blockIdx.x, r = blockIdx.y;
+  for (int c = tid; c < INTER_CTX_R; c += HIER_THREADS) h[c] = 0;
+  __syncthreads();
+  const int32_t* parents = cells1 + hier_sum(counts1, 0, b, tid & 63);
+  const int n = 8 * counts1[b];
+  for (int i = tid; i < n; i += HIER_THREADS) {
+    int cell, e;
+    hier_where<0>(i, parents, b, cell, e);
+    const int t = inter_class(inter_gather(ref, cell), nbr_gather(rows, e, i & 7), e, i & 7, cell & 31);
+    if ((t >> 4) != r) continue;
+    const int c = nbr_ctx0(t & 15, k1[e], p[cell]);
+    atomicAdd(&h[c], 1u + ((uint32_t)((w0[cell >> 6] >> (cell & 63)) & 1ull) << 16));
+  }
+  __syncthreads();
+  // integers: any order of these adds gives the same totals
+  for (int c = tid; c < INTER_CTX_R; c += HIER_THREADS) {
+    const uint32_t v = h[c];
+    if (v & 0xFFFFu) atomicAdd(cnt + HIER_CTX + r * INTER_CTX_R + c, (unsigned long long)(v & 0xFFFFu));
+    if (v >> 16) atomicAdd(occ + HIER_CTX + r * INTER_CTX_R + c, (unsigned long long)(v >> 16));
+  }
 }
 
 }  // namespace
@@ -529,7 +681,7 @@ extern "C" int nvf_occ_hier_encode(const float* p, const float* p1, const uint8_
       group > NVF_OCC_RANS_MAX_GROUP)
     return NVF_EINVAL;
   const int groups = (batch + group - 1) / group;
-  hier_encode_kernel<false><<<groups, 64, 0, nvf_stream(stream)>>>(
+  hier_encode_kernel<CTX_FIELD><<<groups, 64, 0, nvf_stream(stream)>>>(
       p, p1, k1, p2, k2, (const unsigned long long*)gt_w0, (const unsigned long long*)gt_w1,
       (const unsigned long long*)gt_w2, cells2, counts2, cells1, counts1, f1, batch, group, (unsigned long long*)states,
       words, nwords);
@@ -584,7 +736,7 @@ extern "C" int nvf_occ_nbr_encode(const float* p, const float* p1, const uint8_t
       group > NVF_OCC_RANS_MAX_GROUP)
     return NVF_EINVAL;
   const int groups = (batch + group - 1) / group;
-  hier_encode_kernel<true><<<groups, 64, 0, nvf_stream(stream)>>>(
+  hier_encode_kernel<CTX_NBR><<<groups, 64, 0, nvf_stream(stream)>>>(
       p, p1, k1, p2, k2, (const unsigned long long*)gt_w0, (const unsigned long long*)gt_w1,
       (const unsigned long long*)gt_w2, cells2, counts2, cells1, counts1, f1, batch, group, (unsigned long long*)states,
       words, nwords);
@@ -605,6 +757,68 @@ extern "C" int nvf_occ_nbr_decode(const float* p, const uint8_t* k1, const int32
   nbr_decode_kernel<<<groups, 64, 0, nvf_stream(stream)>>>(
       p, k1, cells1, counts1, (const uint16_t*)w1, f1 + HIER_CTX, (unsigned long long*)states, (long long*)pos, words,
       (const long long*)word_off, nwords, (long long)total_words, batch, group, (unsigned long long*)occ_words, status);
+  NVF_LAUNCH_CHECK();
+  return NVF_OK;
+}
+
+extern "C" int nvf_occ_ref_words(const int32_t* points, int64_t npts, const int64_t* keys, const int32_t* perm, int nblocks,
+                                 uint64_t* words, uint64_t* dropped, void* stream) {
+  if (!keys || !perm || !words || !dropped || npts < 0 || (npts > 0 && !points) || nblocks <= 0 ||
+      nblocks > NVF_OCC_HIER_MAX_BATCH || npts > ((int64_t)1 << 31) * 256)
+    return NVF_EINVAL;
+  if (npts == 0) return NVF_OK;
+  ref_words_kernel<<<(unsigned)((npts + 255) / 256), 256, 0, nvf_stream(stream)>>>(
+      points, (long long)npts, (const long long*)keys, perm, nblocks, (unsigned long long*)words,
+      (unsigned long long*)dropped);
+  NVF_LAUNCH_CHECK();
+  return NVF_OK;
+}
+
+extern "C" int nvf_occ_inter_hist(const float* p, const uint8_t* k1, const uint64_t* gt_w0, const uint64_t* gt_w1,
+                                  const uint64_t* ref_words, const int32_t* cells1, const int32_t* counts1, int batch,
+                                  uint64_t* cnt, uint64_t* occ, void* stream) {
+  if (!p || !k1 || !gt_w0 || !gt_w1 || !ref_words || !cells1 || !counts1 || !cnt || !occ || batch <= 0 ||
+      batch > NVF_OCC_HIER_MAX_BATCH)
+    return NVF_EINVAL;
+  inter_hist_kernel<<<dim3(batch, 3), HIER_THREADS, 0, nvf_stream(stream)>>>(
+      p, k1, (const unsigned long long*)gt_w0, (const uint16_t*)gt_w1, (const uint32_t*)ref_words, cells1, counts1,
+      (unsigned long long*)cnt, (unsigned long long*)occ);
+  NVF_LAUNCH_CHECK();
+  return NVF_OK;
+}
+
+extern "C" int nvf_occ_inter_encode(const float* p, const float* p1, const uint8_t* k1, const float* p2, const uint8_t* k2,
+                                    const uint64_t* gt_w0, const uint64_t* gt_w1, const uint64_t* gt_w2,
+                                    const uint64_t* ref_words, const int32_t* cells2, const int32_t* counts2,
+                                    const int32_t* cells1, const int32_t* counts1, const int32_t* f1, int batch, int group,
+                                    uint64_t* states, uint32_t* words, uint32_t* nwords, void* stream) {
+  if (!p || !p1 || !k1 || !p2 || !k2 || !gt_w0 || !gt_w1 || !gt_w2 || !ref_words || !cells2 || !counts2 || !cells1 ||
+      !counts1 || !f1 || ((uintptr_t)f1 & 15) || !states || !words || !nwords || batch <= 0 ||
+      batch > NVF_OCC_HIER_MAX_BATCH || group < 1 || group > NVF_OCC_RANS_MAX_GROUP)
+    return NVF_EINVAL;
+  const int groups = (batch + group - 1) / group;
+  hier_encode_kernel<CTX_INTER><<<groups, 64, 0, nvf_stream(stream)>>>(
+      p, p1, k1, p2, k2, (const unsigned long long*)gt_w0, (const unsigned long long*)gt_w1,
+      (const unsigned long long*)gt_w2, cells2, counts2, cells1, counts1, f1, batch, group, (unsigned long long*)states,
+      words, nwords, (const uint32_t*)ref_words);
+  NVF_LAUNCH_CHECK();
+  return NVF_OK;
+}
+
+extern "C" int nvf_occ_inter_decode(const float* p, const uint8_t* k1, const int32_t* cells1, const int32_t* counts1,
+                                    const uint64_t* w1, const uint64_t* ref_words, const int32_t* f1, uint64_t* states,
+                                    int64_t* pos, const uint32_t* words, const int64_t* word_off, const uint32_t* nwords,
+                                    int64_t total_words, int batch, int group, uint64_t* occ_words, int32_t* status,
+                                    void* stream) {
+  if (!p || !k1 || !cells1 || !counts1 || !w1 || !ref_words || !f1 || ((uintptr_t)f1 & 15) || !states || !pos || !words ||
+      !word_off || !nwords || !occ_words || !status || total_words < 0 || batch <= 0 || batch > NVF_OCC_HIER_MAX_BATCH ||
+      group < 1 || group > NVF_OCC_RANS_MAX_GROUP)
+    return NVF_EINVAL;
+  const int groups = (batch + group - 1) / group;
+  inter_decode_kernel<<<groups, 64, 0, nvf_stream(stream)>>>(
+      p, k1, cells1, counts1, (const uint16_t*)w1, (const uint32_t*)ref_words, f1 + HIER_CTX, (unsigned long long*)states,
+      (long long*)pos, words, (const long long*)word_off, nwords, (long long)total_words, batch, group,
+      (unsigned long long*)occ_words, status);
   NVF_LAUNCH_CHECK();
   return NVF_OK;
 }

@@ -1725,6 +1725,117 @@ def occ_nbr_decode(pyr, f1, states, words, nwords, group, level=0):
     return occ_words, counts, status, pos
 
 
+# ---------------------------------------------------------------- inter contexts (csrc/occ_hier.hip, INTER)
+OCC_INTER_CONTEXTS = _K["NVF_OCC_INTER_CONTEXTS"]
+OCC_REF_COORD_BITS = _K["NVF_OCC_REF_COORD_BITS"]
+
+
+def occ_ref_words(points, origins):
+    """A reference cloud rasterised onto the blocks at `origins` (include/nvf_hip.h, "inter contexts"): points int32
+    [M, 3] and origins int32 [N, 3] (multiples of 32 in [0, 2^26), distinct, in any order) on one device -> (words int64
+    [N, 512] in the format of gt_words[0], dropped int64 [1]: the points under no block).  The keys and their sort
+    are torch; the search and the OR are the kernel's."""
+    _chk(points, origins)
+    if points.dtype != torch.int32 or points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError("occ_ref_words: points must be int32 [M, 3]")
+    N = origins.shape[0]
+    if origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 3 or not 1 <= N <= OCC_HIER_MAX_BATCH or \
+            origins.device != points.device:
+        raise RuntimeError(f"occ_ref_words: origins must be int32 [N, 3] on the device of points, 1 <= N <= {OCC_HIER_MAX_BATCH}")
+    o = origins.long()
+    if bool(((o & 31) != 0).any()) or bool((o < 0).any()) or bool((o >= 1 << OCC_REF_COORD_BITS).any()):
+        raise RuntimeError(f"occ_ref_words: origins are multiples of 32 in [0, 2^{OCC_REF_COORD_BITS})")
+    keys, perm = torch.sort(((o[:, 0] >> 5) << 42) | ((o[:, 1] >> 5) << 21) | (o[:, 2] >> 5))
+    if N > 1 and bool((keys[1:] == keys[:-1]).any()):
+        raise RuntimeError("occ_ref_words: two blocks share an origin")
+    perm = perm.to(torch.int32).contiguous()
+    words = torch.zeros((N, 512), dtype=torch.int64, device=points.device)
+    dropped = torch.zeros(1, dtype=torch.int64, device=points.device)
+    check(lib().nvf_occ_ref_words(_ptr(points), points.shape[0], _ptr(keys), _ptr(perm), N, _ptr(words), _ptr(dropped),
+                                  _stream()), "nvf_occ_ref_words")
+    return words, dropped
+
+
+def _occ_inter_table(f1, dev):
+    _chk(f1)
+    if f1.dtype != torch.int32 or f1.shape != (OCC_INTER_CONTEXTS,) or f1.device != dev or f1.data_ptr() % 16:
+        raise RuntimeError(f"f1 must be int32 [{OCC_INTER_CONTEXTS}] on the device of p, 16-byte aligned")
+
+
+def _occ_inter_ref(ref_words, B, dev):
+    _chk(ref_words)
+    if ref_words.dtype != torch.int64 or ref_words.shape != (B, 512) or ref_words.device != dev:
+        raise RuntimeError(f"ref_words must be int64 [{B}, 512] on the device of p: the reference words of the same blocks")
+
+
+def occ_inter_hist(pyr, ref_words, cnt=None, occ=None):
+    """occ_nbr_hist under the inter contexts (include/nvf_hip.h, "inter contexts"): ref_words int64 [B, 512], cnt and
+    occ int64 [52224]; levels 2 and 1 land in 1024..3071 through nvf_occ_hier_hist, the voxels in 3072.. -> (cnt, occ)."""
+    B, dev = pyr["p"].shape[0], pyr["p"].device
+    _occ_inter_ref(ref_words, B, dev)
+    if cnt is None:
+        cnt, occ = (torch.zeros(OCC_INTER_CONTEXTS, dtype=torch.int64, device=dev) for _ in range(2))
+    _chk(cnt, occ)
+    if any(t.dtype != torch.int64 or t.shape != (OCC_INTER_CONTEXTS,) for t in (cnt, occ)):
+        raise RuntimeError(f"occ_inter_hist: cnt and occ are int64 [{OCC_INTER_CONTEXTS}]")
+    cells2, counts2, cells1, counts1 = pyr["lists"]
+    w0, w1, _ = pyr["gt_words"]
+    for level, cells, counts in ((2, None, None), (1, cells2, counts2)):
+        pv, kv = _occ_hier_level(pyr, level)
+        check(lib().nvf_occ_hier_hist(level, _ptr(pv), _ptr(kv), _ptr(pyr["gt_words"][level]), _ptr(cells), _ptr(counts), B,
+                                      _ptr(cnt), _ptr(occ), _stream()), "nvf_occ_hier_hist")
+    check(lib().nvf_occ_inter_hist(_ptr(pyr["p"]), _ptr(pyr["k1"]), _ptr(w0), _ptr(w1), _ptr(ref_words), _ptr(cells1),
+                                   _ptr(counts1), B, _ptr(cnt), _ptr(occ), _stream()), "nvf_occ_inter_hist")
+    return cnt, occ
+
+
+def occ_inter_encode(pyr, ref_words, f1, group):
+    """occ_hier_encode with the voxels under the inter contexts: ref_words int64 [B, 512], f1 int32 [52224] ->
+    (states, words)."""
+    B, dev = pyr["p"].shape[0], pyr["p"].device
+    _occ_inter_table(f1, dev)
+    _occ_inter_ref(ref_words, B, dev)
+    G, ng = _occ_groups(B, group)
+    w0, w1, w2 = pyr["gt_words"]
+    cells2, counts2, cells1, counts1 = pyr["lists"]
+    return _occ_coded(B, G, ng, OCC_HIER_BLOCK_WORDS, dev, lambda states, region, nwords: check(
+        lib().nvf_occ_inter_encode(_ptr(pyr["p"]), _ptr(pyr["p1"]), _ptr(pyr["k1"]), _ptr(pyr["p2"]), _ptr(pyr["k2"]),
+                                   _ptr(w0), _ptr(w1), _ptr(w2), _ptr(ref_words), _ptr(cells2), _ptr(counts2), _ptr(cells1),
+                                   _ptr(counts1), _ptr(f1), B, G, _ptr(states), _ptr(region), _ptr(nwords), _stream()),
+        "nvf_occ_inter_encode"))
+
+
+def occ_inter_decode(pyr, ref_words, f1, states, words, nwords, group, level=0):
+    """occ_hier_decode of a stream occ_inter_encode wrote (ref_words int64 [B, 512], f1 int32 [52224]): sections 2 and
+    1 through nvf_occ_hier_decode under f1's first 3072 entries, section 0 through nvf_occ_inter_decode with the level-1
+    words just decoded and the reference words.  The same results, status bits and guarantees."""
+    B, dev = pyr["p"].shape[0], pyr["p"].device
+    _occ_inter_table(f1, dev)
+    _occ_inter_ref(ref_words, B, dev)
+    G, ng = _occ_groups(B, group)
+    if level not in (0, 1, 2):
+        raise RuntimeError(f"level must be 0, 1 or 2, got {level!r}")
+    words, word_off, total = _occ_stream("occ_inter_decode", B, G, ng, states, words, nwords)
+    x = states.clone()
+    pos = torch.zeros(ng, dtype=torch.int64, device=dev)
+    status = torch.zeros(ng, dtype=torch.int32, device=dev)
+    cells = counts = above = None
+    for lv in (2, 1, 0)[:3 - level]:
+        pv, kv = _occ_hier_level(pyr, lv)
+        occ_words = torch.zeros((B, 512 >> 3 * lv), dtype=torch.int64, device=dev)
+        if lv:
+            check(lib().nvf_occ_hier_decode(lv, _ptr(pv), _ptr(kv), _ptr(cells), _ptr(counts), _ptr(f1), _ptr(x), _ptr(pos),
+                                            _ptr(words), _ptr(word_off), _ptr(nwords), total, B, G, _ptr(occ_words),
+                                            _ptr(status), _stream()), "nvf_occ_hier_decode")
+        else:
+            check(lib().nvf_occ_inter_decode(_ptr(pv), _ptr(kv), _ptr(cells), _ptr(counts), _ptr(above), _ptr(ref_words),
+                                             _ptr(f1), _ptr(x), _ptr(pos), _ptr(words), _ptr(word_off), _ptr(nwords), total,
+                                             B, G, _ptr(occ_words), _ptr(status), _stream()), "nvf_occ_inter_decode")
+        above = occ_words
+        counts, cells = occ_hier_cells(occ_words, fill=lv > level)
+    return occ_words, counts, status, pos
+
+
 # ---------------------------------------------------------------- PLY text (csrc/ply_io.hip)
 PLY_CHUNK = 4096        # bytes of text per wave in the two line passes
 

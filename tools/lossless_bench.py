@@ -26,6 +26,10 @@ same run, its routes alternating with v1's inside every repetition:
 --lod --ctx nbr adds the neighbour contexts (lossless_nbr_pack, nvf_occ_nbr_*) as a third coder, its routes nbr_encode,
 nbr_decodeL, nbr_coder_encode and nbr_coder_decodeL alternating with the other two's in the same repetitions, and the
 bytes and bpp of its packs ("nbr_packs") next to the scalable coder's ("lod_packs") on the same cloud.
+--lod --ctx inter adds the inter contexts (lossless_inter_pack, nvf_occ_inter_*) as a fourth, next to the neighbour
+contexts in the same repetitions: inter_encode, inter_decodeL, inter_coder_encode, inter_coder_decodeL, "inter_packs",
+and ref_words: nvf_occ_ref_words with its key sort over the whole reference cloud, which is the benchmark's cloud moved
+by one voxel along x on the lattice of synth.make_origins.
   Every whole call ends in a synchronise (its result is on the host or its
 status was read); the routes alternate inside every repetition, the first --warmup repetitions are dropped and the
 median, minimum and maximum of the rest are reported in milliseconds.  Each pack is decoded and compared with the
@@ -54,14 +58,16 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--lod", action="store_true", help="time the scalable coder (lossless_lod_pack) next to v1")
-    ap.add_argument("--ctx", choices=["field", "nbr"], default="field",
-                    help="nbr (with --lod): time the neighbour contexts (lossless_nbr_pack) next to the scalable coder")
+    ap.add_argument("--ctx", choices=["field", "nbr", "inter"], default="field",
+                    help="nbr (with --lod): time the neighbour contexts (lossless_nbr_pack) next to the scalable coder; "
+                         "inter: the inter contexts (lossless_inter_pack) next to both")
     a = ap.parse_args()
-    if a.ctx == "nbr" and not a.lod:
-        raise SystemExit("lossless_bench.py: --ctx nbr is a route of the scalable coder; give --lod too")
+    if a.ctx != "field" and not a.lod:
+        raise SystemExit(f"lossless_bench.py: --ctx {a.ctx} is a route of the scalable coder; give --lod too")
     if not torch.cuda.is_available():
         raise SystemExit("lossless_bench.py needs a HIP device: nothing here can be timed on a CPU")
-    from nvfpcc_amd import lossless_lod_pack as llp, lossless_nbr_pack as nlp, lossless_pack as lp, network, ops
+    from nvfpcc_amd import lossless_inter_pack as ilp, lossless_lod_pack as llp, lossless_nbr_pack as nlp
+    from nvfpcc_amd import lossless_pack as lp, network, ops
     from nvfpcc_amd.model import Net
     from nvfpcc_amd.recon import eval_batches
     from nvfpcc_amd.seeds import synthetic_seed
@@ -99,30 +105,42 @@ def main():
             raise SystemExit(f"group {G}: the pack does not decode to the ground truth")
         info[G] = {"bytes": len(packs[G]), "bpp": round(8 * len(packs[G]) / n_points, 4),
                    "ideal_bpp": round(side["ideal_bits"] / n_points, 4)}
-    lod_packs, lod_info, nbr_packs, nbr_info = {}, {}, {}, {}
-    coders = ([("scalable", llp, lod_packs, lod_info)] if a.lod else []) + \
-             ([("neighbour", nlp, nbr_packs, nbr_info)] if a.ctx == "nbr" else [])
-    for what, mod, out_packs, out_info in coders:
+    ref, ref_pts, ref_org, ref_dropped = (), None, None, 0
+    if a.ctx == "inter":                    # the cloud itself, one voxel along x, as a decoder would hold it: as points
+        from nvfpcc_amd.synth import make_origins
+        ref_org = torch.from_numpy(make_origins(a.blocks)).to(torch.int32).to(dev)
+        nz = gt.reshape(a.blocks, 32, 32, 32).nonzero()
+        ref_pts = (ref_org[nz[:, 0]] + nz[:, 1:].to(torch.int32) + torch.tensor([0, 0, 1], dtype=torch.int32, device=dev)).contiguous()
+        words, dropped = ops.occ_ref_words(ref_pts, ref_org)
+        ref, ref_dropped = (words,), int(dropped.item())
+    lod_packs, lod_info, nbr_packs, nbr_info, inter_packs, inter_info = {}, {}, {}, {}, {}, {}
+    coders = ([("scalable", llp, lod_packs, lod_info, ())] if a.lod else []) + \
+             ([("neighbour", nlp, nbr_packs, nbr_info, ())] if a.ctx in ("nbr", "inter") else []) + \
+             ([("inter", ilp, inter_packs, inter_info, ref)] if a.ctx == "inter" else [])
+    for what, mod, out_packs, out_info, extra in coders:
         for G in groups:
-            out_packs[G], side = mod.encode_occupancy(net, lat, gt, batch=a.batch, group=G)
+            out_packs[G], side = mod.encode_occupancy(net, lat, gt, *extra, batch=a.batch, group=G)
             for level in (0, 1, 2):
-                words, counts = mod.decode_occupancy(net, lat, out_packs[G], level=level, batch=a.batch)
+                words, counts = mod.decode_occupancy(net, lat, out_packs[G], *extra, level=level, batch=a.batch)
                 if not torch.equal(words, side["gt_words"][level]) or (level == 0 and int(counts.sum().item()) != n_points):
                     raise SystemExit(f"group {G}: the {what} pack does not decode to the ground truth at level {level}")
             out_info[G] = {"bytes": len(out_packs[G]), "bpp": round(8 * len(out_packs[G]) / n_points, 4),
                            "ideal_bpp": round(side["ideal_bits"] / n_points, 4), "contexts": side["contexts"],
                            "symbols": side["symbols"], "v1_symbols": a.blocks * 32768}
     routes = {"forward": forward}
+    if a.ctx == "inter":
+        routes["ref_words"] = lambda: ops.occ_ref_words(ref_pts, ref_org)
     for G in groups:
         routes[f"encode_G{G}"] = lambda G=G: lp.encode_occupancy(net, lat, gt, batch=a.batch, group=G)
         routes[f"decode_G{G}"] = lambda G=G: lp.decode_occupancy(net, lat, packs[G], batch=a.batch)
-        for tag, mod, its_packs in (("lod", llp, lod_packs), ("nbr", nlp, nbr_packs)):
+        for tag, mod, its_packs, extra in (("lod", llp, lod_packs, ()), ("nbr", nlp, nbr_packs, ()), ("inter", ilp, inter_packs, ref)):
             if G not in its_packs:
                 continue
-            routes[f"{tag}_encode_G{G}"] = lambda G=G, mod=mod: mod.encode_occupancy(net, lat, gt, batch=a.batch, group=G)
+            routes[f"{tag}_encode_G{G}"] = lambda G=G, mod=mod, extra=extra: \
+                mod.encode_occupancy(net, lat, gt, *extra, batch=a.batch, group=G)
             for level in (0, 1, 2):
-                routes[f"{tag}_decode{level}_G{G}"] = lambda G=G, level=level, mod=mod, its_packs=its_packs: \
-                    mod.decode_occupancy(net, lat, its_packs[G], level=level, batch=a.batch)
+                routes[f"{tag}_decode{level}_G{G}"] = lambda G=G, level=level, mod=mod, its_packs=its_packs, extra=extra: \
+                    mod.decode_occupancy(net, lat, its_packs[G], *extra, level=level, batch=a.batch)
     times = {k: [] for k in routes}
     for rep in range(a.warmup + a.reps):
         for name, fn in routes.items():
@@ -153,13 +171,21 @@ def main():
                 span[G] += (pyr, hf1, hs, torch.cat(hw), torch.tensor([w.numel() for w in hw], dtype=torch.int32, device=dev))
                 for name in ("pyramid", "coder_encode", "coder_decode0", "coder_decode1", "coder_decode2"):
                     times[f"lod_{name}_G{G}"] = []
-                if a.ctx == "nbr":
+                if a.ctx in ("nbr", "inter"):
                     nf1, _ = nlp.table_from_counts(*(t.tolist() for t in ops.occ_nbr_hist(pyr)))
                     nf1 = torch.tensor(nf1, dtype=torch.int32, device=dev)
                     ns, nw = ops.occ_nbr_encode(pyr, nf1, G)
                     span[G] += (nf1, ns, torch.cat(nw), torch.tensor([w.numel() for w in nw], dtype=torch.int32, device=dev))
                     for name in ("coder_encode", "coder_decode0", "coder_decode1", "coder_decode2"):
                         times[f"nbr_{name}_G{G}"] = []
+                if a.ctx == "inter":
+                    rw = ref[0][:nb].contiguous()
+                    if1, _ = ilp.table_from_counts(*(t.tolist() for t in ops.occ_inter_hist(pyr, rw)))
+                    if1 = torch.tensor(if1, dtype=torch.int32, device=dev)
+                    is_, iw = ops.occ_inter_encode(pyr, rw, if1, G)
+                    span[G] += (rw, if1, is_, torch.cat(iw), torch.tensor([w.numel() for w in iw], dtype=torch.int32, device=dev))
+                    for name in ("coder_encode", "coder_decode0", "coder_decode1", "coder_decode2"):
+                        times[f"inter_{name}_G{G}"] = []
         for rep in range(a.warmup + a.reps):
             for G in groups:
                 nb, p, gg, f1, states, flat, nwords = span[G][:7]
@@ -171,10 +197,15 @@ def main():
                               (f"lod_coder_encode_G{G}", lambda: ops.occ_hier_encode(pyr, hf1, G))]
                     timed += [(f"lod_coder_decode{level}_G{G}", lambda level=level: ops.occ_hier_decode(pyr, hf1, hs, hflat, hn, G, level))
                               for level in (0, 1, 2)]
-                if a.ctx == "nbr":
-                    nf1, ns, nflat, nn = span[G][12:]
+                if a.ctx in ("nbr", "inter"):
+                    nf1, ns, nflat, nn = span[G][12:16]
                     timed += [(f"nbr_coder_encode_G{G}", lambda: ops.occ_nbr_encode(pyr, nf1, G))]
                     timed += [(f"nbr_coder_decode{level}_G{G}", lambda level=level: ops.occ_nbr_decode(pyr, nf1, ns, nflat, nn, G, level))
+                              for level in (0, 1, 2)]
+                if a.ctx == "inter":
+                    rw, if1, is_, iflat, inn = span[G][16:]
+                    timed += [(f"inter_coder_encode_G{G}", lambda: ops.occ_inter_encode(pyr, rw, if1, G))]
+                    timed += [(f"inter_coder_decode{level}_G{G}", lambda level=level: ops.occ_inter_decode(pyr, rw, if1, is_, iflat, inn, G, level))
                               for level in (0, 1, 2)]
                 for name, fn in timed:
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -189,6 +220,8 @@ def main():
            "chanstr": a.chanstr, "reps": a.reps, "warmup": a.warmup, "points": n_points,
            "span_blocks": {str(G): span[G][0] for G in groups}, "packs": {str(G): v for G, v in info.items()},
            "lod_packs": {str(G): v for G, v in lod_info.items()}, "nbr_packs": {str(G): v for G, v in nbr_info.items()},
+           "inter_packs": {str(G): v for G, v in inter_info.items()},
+           "reference": {"points": 0 if ref_pts is None else int(ref_pts.shape[0]), "dropped": ref_dropped},
            "ms": {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
                   for k, v in times.items()}}
     print(json.dumps(out))
