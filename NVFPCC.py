@@ -24,6 +24,7 @@ engine (nvfpcc_amd/engine.py) instead of a DataLoader + autograd loop.
     python NVFPCC.py decode pack.pk --lossless_lod 0|1|2 ...                   # exact at 32^3, 16^3 or 8^3 per block
     python NVFPCC.py encode ... --lossless_lod --lossless_ctx inter --lossless_ref prev/rc_dec.ply   # the voxels under a cloud both sides hold
     python NVFPCC.py decode pack.pk --lossless_lod 0|1|2 --lossless_ref prev/rc_dec.ply ...          # the same reference decodes it
+    python NVFPCC.py encode ... --lossless_lod --lossless_ctx inter --lossless_ref prev/rc_dec.ply --lossless_mv 4   # each block under the reference moved by its own vector (lossless_mv_pack); decode needs no flag
     python NVFPCC.py train seq_%04d.ply --gof 8 --frame_start 1300 ...         # one decoder for frames 1300 .. 1307
     python NVFPCC.py encode seq_%04d.ply --gof 8 --frame_start 1300 ...        # one pack: the weights once, a frame pack each
     python NVFPCC.py decode pack.pk --frame 1303 ...                           # that frame alone; without --frame, all of them
@@ -31,7 +32,7 @@ engine (nvfpcc_amd/engine.py) instead of a DataLoader + autograd loop.
     python NVFPCC.py encode next.ply --load_weights q4.ckpt --ref_pack ref.pk  # a latents-only pack: 33 bytes name ref.pk's decoder
     python NVFPCC.py decode p.pk --ref_pack ref.pk ...                         # decoded under the reference's weights
 
-Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --ply_format, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --lossless_lod, --lossless_ctx, --lossless_ref, --gof, --frame_start, --frame, --freeze_decoder, --ref_pack, --thh_mode (count | block-count | d1:
+Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --ply_format, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --lossless_lod, --lossless_ctx, --lossless_ref, --lossless_mv, --gof, --frame_start, --frame, --freeze_decoder, --ref_pack, --thh_mode (count | block-count | d1:
 nvfpcc_amd/thh_select.py picks the occupancy threshold at encode time and a `thh_pack` key carries it); multi-GPU training when launched
 through torch.distributed.run (one process per GPU, leaf blocks sharded, one RCCL all-reduce per step).
 Headless: no GUI window, no IPython shell.
@@ -418,6 +419,8 @@ def _encode_frame(args, net, net_weight_pack, emb, data, pre, dev, bits, fmt, st
     if getattr(args, 'lossless_lod', None) is not None:     # the same occupancy coarse to fine: exact at 8^3, 16^3, 32^3
         lossless_lod = _encode_lossless_lod(args, total_pack, data, dev, batch)
         total_pack['lossless_lod_pack'] = lossless_lod['pack']
+        if 'mv_pack' in lossless_lod:       # --lossless_mv: the vectors the reference words were fetched under
+            total_pack['lossless_mv_pack'] = lossless_lod['mv_pack']
     frame_pack = {k: v for k, v in total_pack.items() if k != 'net_weight_pack'}
     if write_pack is not None:
         write_pack(frame_pack)
@@ -436,7 +439,7 @@ def _encode_frame(args, net, net_weight_pack, emb, data, pre, dev, bits, fmt, st
     latent_bits = len(latent_pack['latent_byte_stream']) * 8
     side_bits = (0 if sel is None else 8 * len(sel['pack'])) + 8 * len(total_pack.get('octree_pack', b''))
     side_bits += 8 * len(total_pack.get('lod_pack', b'')) + 8 * len(total_pack.get('lossless_pack', b''))
-    side_bits += 8 * len(total_pack.get('lossless_lod_pack', b''))
+    side_bits += 8 * len(total_pack.get('lossless_lod_pack', b'')) + 8 * len(total_pack.get('lossless_mv_pack', b''))
     if sel is not None:
         print(sel['line'])
     if write_pack is not None:
@@ -483,8 +486,11 @@ def _encode_lossless_lod(args, total_pack, data, dev, batch):
     stream is decoded again at all three levels: a pack that does not reproduce the input's occupancy and its two
     max-pools is not written.  --lossless_ctx nbr: the voxels under their parents' neighbours
     (nvfpcc_amd.lossless_nbr_pack), the same key.  --lossless_ctx inter: under the cloud of --lossless_ref as well
-    (nvfpcc_amd.lossless_inter_pack), rasterised onto this frame's blocks; the same key again.
-    -> {'pack': lossless_lod_pack bytes, 'line': the [LosslessLoD] line}."""
+    (nvfpcc_amd.lossless_inter_pack), rasterised onto this frame's blocks; the same key again.  --lossless_mv R: the
+    reference words are fetched block by block under the vectors of a search of radius R (nvfpcc_amd.lossless_mv_pack);
+    the coder sees only those words.
+    -> {'pack': lossless_lod_pack bytes, 'line': the [LosslessLoD] lines, 'mv_pack': lossless_mv_pack bytes with
+    --lossless_mv}."""
     import contextlib
     import io
     ctx = getattr(args, 'lossless_ctx', 'field')
@@ -498,9 +504,10 @@ def _encode_lossless_lod(args, total_pack, data, dev, batch):
         net, latents = _decoder_from_pack(args, total_pack, dev)
     latents = latents[:data.N_leaf].contiguous()
     gt, _ = data.to_device(dev)
-    ref, ref_line = (), None
+    ref, ref_line, mv_pack = (), None, None
     if ctx == 'inter':
-        ref, ref_line = _lossless_reference(args.lossless_ref, np.array([data.origins[i] for i in range(len(data))]), dev)
+        ref, ref_line, mv_pack = _lossless_reference(args.lossless_ref, np.array([data.origins[i] for i in range(len(data))]),
+                                                     dev, search=(gt, args.lossless_mv) if hasattr(args, 'lossless_mv') else None)
     try:
         pack, info = lp.encode_occupancy(net, latents, gt, *ref, batch=batch, group=lp.GROUP)
         for level in (2, 1, 0):
@@ -511,19 +518,38 @@ def _encode_lossless_lod(args, total_pack, data, dev, batch):
     except ValueError as e:
         raise SystemExit(f"encode --lossless_lod: {e}")
     line = lp.lossless_lod_line(len(pack), data.N, info['ideal_bits'], info['contexts'], info['symbols'], lp.GROUP)
-    return {'pack': pack, 'line': line if ref_line is None else line + '\n' + ref_line}
+    out = {'pack': pack, 'line': line if ref_line is None else line + '\n' + ref_line}
+    if mv_pack is not None:
+        out['mv_pack'] = mv_pack
+    return out
 
 
-def _lossless_reference(fn, origins, dev):
+def _lossless_reference(fn, origins, dev, search=None, mv_pack=None):
     """--lossless_ref: the cloud of `fn` (ASCII or binary PLY) rasterised onto the blocks at `origins`
-    -> ((the reference words on the device,), the [LosslessLoD] line that says what was read)."""
-    from nvfpcc_amd import lossless_inter_pack, ply_io
+    -> ((the reference words on the device,), the [LosslessLoD] lines that say what was read, the lossless_mv_pack bytes
+    or None).  search = (gt float [N, 32768] on the device, radius): encode --lossless_mv, the vectors are searched and
+    packed; mv_pack: the bytes a pack carries, decode.  Either way the words are fetched under the vectors."""
+    from nvfpcc_amd import lossless_inter_pack, lossless_mv_pack, ply_io
     try:
         pts = np.asarray(ply_io.read_ply(fn)[0])
     except (OSError, ValueError) as e:
         raise SystemExit(f"--lossless_ref {fn}: {e}")
-    words, dropped = lossless_inter_pack.reference_words(np.rint(pts).astype(np.int64), np.asarray(origins, np.int64), dev)
-    return (words,), '[LosslessLoD] reference: %s points: %d dropped: %d' % (fn, pts.shape[0], dropped)
+    pts, origins = np.rint(pts).astype(np.int64), np.asarray(origins, np.int64)
+    if search is None and mv_pack is None:
+        words, dropped = lossless_inter_pack.reference_words(pts, origins, dev)
+        return (words,), '[LosslessLoD] reference: %s points: %d dropped: %d' % (fn, pts.shape[0], dropped), None
+    own = lossless_mv_pack.reference_blocks(pts, dev)
+    if search is not None:
+        gt, radius = search
+        mv = lossless_mv_pack.search(lossless_mv_pack.frame_words(gt), own, origins, radius)[0].cpu().numpy()
+        mv_pack = lossless_mv_pack.write(radius, mv)
+    else:
+        info = lossless_mv_pack.read(mv_pack, origins.shape[0])
+        mv, radius = info['mv'], info['radius']
+    words = lossless_mv_pack.compensated_words(own, origins, mv)
+    lines = '[LosslessLoD] reference: %s points: %d blocks: %d\n' % (fn, pts.shape[0], own[1].shape[0]) + \
+        lossless_mv_pack.mv_line(radius, mv, len(mv_pack))
+    return (words,), lines, mv_pack
 
 
 def _encode_lod(args, net, latents, data, origins, dev, batch):
@@ -588,6 +614,9 @@ def _select_threshold(mode, net, latents, data, origins, dev, batch):
 
 def decode(args):
     """Decode from a pack (NVFPCC.py:557-652)."""
+    if hasattr(args, 'lossless_mv'):
+        raise SystemExit(f"decode: --lossless_mv {args.lossless_mv} is the search radius of encode; decode reads the "
+                         f"vectors from the pack's lossless_mv_pack")
     lossless_refusals(args, None)
     lossless_lod_refusals(args, None)
     fmt = getattr(args, 'ply_format', 'ascii')
@@ -697,7 +726,8 @@ def _decode_pack(args, total_pack, dev, fmt, net, out_fn):
                 if not hasattr(args, 'lossless_ref'):
                     raise SystemExit(f"decode --lossless_lod {level}: the lossless_lod_pack of {args.input} was coded under "
                                      f"a reference cloud (--lossless_ctx inter); name that cloud with --lossless_ref")
-                ref, ref_line = _lossless_reference(args.lossless_ref, np.asarray(origins, np.int64), dev)
+                ref, ref_line, _ = _lossless_reference(args.lossless_ref, np.asarray(origins, np.int64), dev,
+                                                       mv_pack=total_pack.get('lossless_mv_pack'))
                 print(ref_line)
             elif hasattr(args, 'lossless_ref'):
                 print(f'[Info] the lossless_lod_pack of {args.input} refers to no other cloud; --lossless_ref '
@@ -782,6 +812,12 @@ def lossless_ctx_refusals(args):
     if inter and hasattr(args, 'gof'):
         raise SystemExit("encode: --gof and --lossless_ctx inter exclude each other: a frame that refers to its "
                          "predecessor inside a group is not coded; encode the frames one by one with --lossless_ref")
+    if hasattr(args, 'lossless_mv'):
+        if not inter:
+            raise SystemExit(f"encode: --lossless_mv {args.lossless_mv} moves the reference of --lossless_ctx inter; give "
+                             f"--lossless_lod --lossless_ctx inter --lossless_ref too")
+        if not 1 <= args.lossless_mv <= 8:
+            raise SystemExit(f"encode: --lossless_mv {args.lossless_mv}: the search radius is 1..8 voxels")
 
 
 def lossless_lod_refusals(args, total_pack):
@@ -798,6 +834,9 @@ def lossless_lod_refusals(args, total_pack):
     if total_pack is not None and 'lossless_lod_pack' not in total_pack:
         raise SystemExit(f"decode --lossless_lod {level}: {args.input} carries no lossless_lod_pack (it was encoded "
                          f"without --lossless_lod)")
+    if total_pack is not None and 'lossless_mv_pack' in total_pack and bytes(total_pack['lossless_lod_pack'][:1]) != b'\x04':
+        raise SystemExit(f"decode --lossless_lod {level}: {args.input} carries a lossless_mv_pack, the vectors of a "
+                         f"reference cloud, but its lossless_lod_pack is not version 4 and refers to none")
 
 
 def _pack_bits(total_pack, origins):
@@ -915,6 +954,11 @@ def build_parser():
                    help='encode --lossless_lod --lossless_ctx inter / decode --lossless_lod of such a pack: the reference '
                         'cloud (ASCII or binary PLY), normally the previous frame\'s rc_dec.ply.  The pack carries a '
                         'digest of it on this frame\'s blocks: decode refuses any other cloud.')
+    p.add_argument('--lossless_mv', type=int, metavar='R', default=argparse.SUPPRESS,
+                   help='encode --lossless_lod --lossless_ctx inter: block motion compensation.  Each block is coded under '
+                        'the reference cloud moved by its own integer vector, found by an exhaustive search of radius R '
+                        '(1..8 voxels); the vectors travel in lossless_mv_pack (counted in Gross bpp).  decode needs no '
+                        'flag.')
     p.add_argument('--gof', type=int, default=argparse.SUPPRESS,
                    help='train / encode: a group of F frames under one decoder.  `input` is then the pattern of their '
                         'names with one %%d or %%0<n>d (seq_%%04d.ply); the frames are numbered from --frame_start.  encode '

@@ -1060,6 +1060,37 @@ int nvf_occ_inter_decode(const float* p, const uint8_t* k1, const int32_t* cells
                          const int64_t* word_off, const uint32_t* nwords, int64_t total_words, int batch, int group,
                          uint64_t* occ_words, int32_t* status, void* stream);
 
+/* ---- scalable lossless geometry, motion-compensated reference (nvfpcc_amd/lossless_mv_pack.py, csrc/occ_motion.hip) --
+ * A layer in FRONT of the inter contexts: the coder above only ever sees R, so R may be built block by block from the
+ * reference displaced by that block's own integer vector.  Nothing in the version-4 stream changes.
+ * Ref(q) = 1 when the reference cloud holds the point q, q in [0, 2^NVF_OCC_REF_COORD_BITS)^3, and 0 everywhere else.
+ * A block with origin o_b and vector d_b = (d0, d1, d2), every |component| <= r <= NVF_OCC_MV_MAX_RADIUS, has the
+ *   compensated reference R'_b(v) = Ref(o_b + v - d_b), v in [0, 32)^3, axes in the order of the points' columns, in the
+ *   word format of gt_w0 and nvf_occ_ref_words: one uint32 per (v0, v1) row with bit v2, two rows to a uint64 word.
+ *   With every d_b = 0, R' is what nvf_occ_ref_words writes whenever the reference's points all lie under the blocks.
+ * The reference is held on its OWN blocks: ref_keys int64 [nref] = the distinct keys (as in nvf_occ_ref_words) of q & ~31
+ *   over its in-range points, sorted ascending; ref_own uint64 [nref, 512] = their words, filled by nvf_occ_ref_words
+ *   (in chunks of at most NVF_OCC_HIER_MAX_BATCH blocks when there are more; nref itself is not bounded).  A block's
+ *   window reaches at most 2 x 2 x 2 reference blocks; a block that is absent reads as 0, and so does a window coordinate
+ *   outside [0, 2^NVF_OCC_REF_COORD_BITS).  nref == 0 is valid (ref_own and ref_keys are then not read and may be NULL):
+ *   words are all 0 and vectors are all 0.
+ * nvf_occ_mv_words: origins int32 [nblocks, 3], mv int32 [nblocks, 3] -> words uint64 [nblocks, 512], EVERY word
+ *   written.  A vector with a component outside +-NVF_OCC_MV_MAX_RADIUS zeroes that block's words and adds 1 to
+ *   status[0] (int32, cleared by the caller).  No content of mv, origins or ref_keys makes the kernel read or write
+ *   outside its arrays (origins need not be multiples of 32 for that; the window arithmetic is 64-bit).
+ * nvf_occ_mv_search: gt_w0 uint64 [nblocks, 512], the blocks' own words.  For each block the exact Hamming distance
+ *   sum popcount(G_b ^ R'_{b,d}) over all (2 radius + 1)^3 vectors d; mv int32 [nblocks, 3] = the vector of the smallest
+ *   distance, ties broken by the smaller d0^2 + d1^2 + d2^2, then by the lexicographically smaller (d0, d1, d2): the zero
+ *   vector wins every tie it takes part in, and a block whose window is empty gets 0.  cost uint32 [nblocks, 2] = (the
+ *   winner's distance, the distance at d = 0).  All sums are integer: every call gives the same bits.
+ * Both return NVF_EINVAL on a null pointer, nblocks <= 0 or > NVF_OCC_HIER_MAX_BATCH, nref < 0, and the search on a
+ *   radius outside [1, NVF_OCC_MV_MAX_RADIUS]. */
+#define NVF_OCC_MV_MAX_RADIUS 8
+int nvf_occ_mv_words(const uint64_t* ref_own, const int64_t* ref_keys, int nref, const int32_t* origins, const int32_t* mv,
+                     int nblocks, uint64_t* words, int32_t* status, void* stream);
+int nvf_occ_mv_search(const uint64_t* gt_w0, const uint64_t* ref_own, const int64_t* ref_keys, int nref,
+                      const int32_t* origins, int nblocks, int radius, int32_t* mv, uint32_t* cost, void* stream);
+
 /* ---- pre-processing on the device (nvfpcc_amd/preprocess.py: preprocess_device, csrc/pp_device.hip) ----------------
  * From int32 [P,3] points with coordinates of `bits` bits (10, 11 or 12; anything else is NVF_EINVAL) to everything
  * nvf_nearest_dist2 and the trainer take, without a host pass.  D = bits - 5 is the level of the 32^3 leaves.  A CELL

@@ -1836,6 +1836,84 @@ def occ_inter_decode(pyr, ref_words, f1, states, words, nwords, group, level=0):
     return occ_words, counts, status, pos
 
 
+# ---------------------------------------------------------------- motion-compensated reference (csrc/occ_motion.hip)
+OCC_MV_MAX_RADIUS = _K["NVF_OCC_MV_MAX_RADIUS"]
+
+
+def occ_ref_blocks(points):
+    """A reference cloud on its OWN blocks (include/nvf_hip.h, "motion-compensated reference"): points int32 [M, 3] on
+    the device -> (ref_own int64 [Nref, 512], ref_keys int64 [Nref]): the distinct blocks q & ~31 of the points inside
+    [0, 2^26)^3, keys sorted ascending, and their words.  The keys, unique and sort are torch; the words are
+    nvf_occ_ref_words', in chunks of at most OCC_HIER_MAX_BATCH blocks (a chunk drops the other chunks' points)."""
+    _chk(points)
+    if points.dtype != torch.int32 or points.dim() != 2 or points.shape[1] != 3:
+        raise RuntimeError("occ_ref_blocks: points must be int32 [M, 3]")
+    dev = points.device
+    q = points.long()
+    q = q[((q >= 0) & (q < 1 << OCC_REF_COORD_BITS)).all(1)]
+    keys = torch.unique(((q[:, 0] >> 5) << 42) | ((q[:, 1] >> 5) << 21) | (q[:, 2] >> 5))      # sorted ascending
+    nref = keys.shape[0]
+    ref_own = torch.zeros((nref, 512), dtype=torch.int64, device=dev)
+    dropped = torch.zeros(1, dtype=torch.int64, device=dev)
+    for lo in range(0, nref, OCC_HIER_MAX_BATCH):
+        n = min(OCC_HIER_MAX_BATCH, nref - lo)
+        perm = torch.arange(n, dtype=torch.int32, device=dev)
+        check(lib().nvf_occ_ref_words(_ptr(points), points.shape[0], _ptr(keys[lo:lo + n]), _ptr(perm), n,
+                                      _ptr(ref_own[lo:lo + n]), _ptr(dropped), _stream()), "nvf_occ_ref_words")
+    return ref_own, keys
+
+
+def _occ_mv_ref(name, ref_own, ref_keys, origins):
+    _chk(ref_own, ref_keys, origins)
+    N, dev = origins.shape[0], origins.device
+    if origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 3 or not 1 <= N <= OCC_HIER_MAX_BATCH:
+        raise RuntimeError(f"{name}: origins must be int32 [N, 3], 1 <= N <= {OCC_HIER_MAX_BATCH}")
+    nref = ref_keys.shape[0]
+    if ref_keys.dtype != torch.int64 or ref_keys.dim() != 1 or ref_own.dtype != torch.int64 or \
+            ref_own.shape != (nref, 512) or ref_own.device != dev or ref_keys.device != dev:
+        raise RuntimeError(f"{name}: the reference is ref_own int64 [Nref, 512] and ref_keys int64 [Nref] on the device of "
+                           f"origins (occ_ref_blocks)")
+    if nref > 1 and bool((ref_keys[1:] <= ref_keys[:-1]).any()):
+        raise RuntimeError(f"{name}: ref_keys are distinct and sorted ascending")
+    return N, nref, dev
+
+
+def occ_mv_words(ref_own, ref_keys, origins, mv, guard=0):
+    """The compensated reference words R' (include/nvf_hip.h, "motion-compensated reference"): (ref_own, ref_keys) of
+    occ_ref_blocks, origins int32 [N, 3], mv int32 [N, 3] on one device -> (words int64 [N, 512], status int32 [1]: the
+    blocks whose vector has a component outside +-8; their words are 0).  guard > 0 (tests): the buffer has `guard` rows
+    of 0x55.. before and after the N blocks and is returned whole."""
+    N, nref, dev = _occ_mv_ref("occ_mv_words", ref_own, ref_keys, origins)
+    _chk(mv)
+    if mv.dtype != torch.int32 or mv.shape != (N, 3) or mv.device != dev:
+        raise RuntimeError(f"occ_mv_words: mv must be int32 [{N}, 3] on the device of origins")
+    buf = torch.full((N + 2 * guard, 512), 0x5555555555555555, dtype=torch.int64, device=dev) if guard else \
+        torch.empty((N, 512), dtype=torch.int64, device=dev)
+    words = buf[guard:guard + N]
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    check(lib().nvf_occ_mv_words(_ptr(ref_own), _ptr(ref_keys), nref, _ptr(origins), _ptr(mv), N, _ptr(words), _ptr(status),
+                                 _stream()), "nvf_occ_mv_words")
+    return (buf if guard else words), status
+
+
+def occ_mv_search(gt_words0, ref_own, ref_keys, origins, radius):
+    """The exhaustive Hamming search of radius `radius` in 1..8: gt_words0 int64 [N, 512] (the blocks' own words), the
+    reference and origins as occ_mv_words -> (mv int32 [N, 3], cost int32 [N, 2] = the winner's distance and the
+    distance at 0).  Ties: smaller |d|^2, then lexicographically smaller d."""
+    N, nref, dev = _occ_mv_ref("occ_mv_search", ref_own, ref_keys, origins)
+    _chk(gt_words0)
+    if gt_words0.dtype != torch.int64 or gt_words0.shape != (N, 512) or gt_words0.device != dev:
+        raise RuntimeError(f"occ_mv_search: gt_words0 must be int64 [{N}, 512] on the device of origins")
+    radius = int(radius)
+    if not 1 <= radius <= OCC_MV_MAX_RADIUS:
+        raise RuntimeError(f"occ_mv_search: radius {radius} outside 1..{OCC_MV_MAX_RADIUS}")
+    mv = torch.empty((N, 3), dtype=torch.int32, device=dev)
+    cost = torch.empty((N, 2), dtype=torch.int32, device=dev)
+    check(lib().nvf_occ_mv_search(_ptr(gt_words0), _ptr(ref_own), _ptr(ref_keys), nref, _ptr(origins), N, radius, _ptr(mv),
+                                  _ptr(cost), _stream()), "nvf_occ_mv_search")
+    return mv, cost
+
+
 # ---------------------------------------------------------------- PLY text (csrc/ply_io.hip)
 PLY_CHUNK = 4096        # bytes of text per wave in the two line passes
 

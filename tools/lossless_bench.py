@@ -30,6 +30,13 @@ bytes and bpp of its packs ("nbr_packs") next to the scalable coder's ("lod_pack
 contexts in the same repetitions: inter_encode, inter_decodeL, inter_coder_encode, inter_coder_decodeL, "inter_packs",
 and ref_words: nvf_occ_ref_words with its key sort over the whole reference cloud, which is the benchmark's cloud moved
 by one voxel along x on the lattice of synth.make_origins.
+--lod --ctx inter --mv R adds block motion compensation (lossless_mv_pack, csrc/occ_motion.hip) in the same repetitions:
+mv_ref_blocks (the reference on its own blocks: keys, unique and nvf_occ_ref_words), mv_search (nvf_occ_mv_search at radius
+R over all blocks, with the copy of nothing: vectors stay on the device), mv_words (nvf_occ_mv_words over all blocks) and
+inter_mv_encode G: the whole compensated encode from the reference's points -- its own blocks, the frame's words, the
+search, the vectors' pack, the compensated words and lossless_inter_pack.encode_occupancy under them -- next to
+inter_encode G, which is handed finished reference words (ref_words is its share of that work); "inter_mv_packs" and
+"motion" (the vectors' bytes and how many blocks moved) say what it buys on this cloud.
   Every whole call ends in a synchronise (its result is on the host or its
 status was read); the routes alternate inside every repetition, the first --warmup repetitions are dropped and the
 median, minimum and maximum of the rest are reported in milliseconds.  Each pack is decoded and compared with the
@@ -61,13 +68,18 @@ def main():
     ap.add_argument("--ctx", choices=["field", "nbr", "inter"], default="field",
                     help="nbr (with --lod): time the neighbour contexts (lossless_nbr_pack) next to the scalable coder; "
                          "inter: the inter contexts (lossless_inter_pack) next to both")
+    ap.add_argument("--mv", type=int, default=0, metavar="R",
+                    help="with --lod --ctx inter: time the motion search of radius R (1..8), the compensated words and the "
+                         "whole compensated encode next to the inter contexts'")
     a = ap.parse_args()
     if a.ctx != "field" and not a.lod:
         raise SystemExit(f"lossless_bench.py: --ctx {a.ctx} is a route of the scalable coder; give --lod too")
+    if a.mv and (a.ctx != "inter" or not 1 <= a.mv <= 8):
+        raise SystemExit(f"lossless_bench.py: --mv {a.mv} is a search radius in 1..8 for the reference of --ctx inter")
     if not torch.cuda.is_available():
         raise SystemExit("lossless_bench.py needs a HIP device: nothing here can be timed on a CPU")
     from nvfpcc_amd import lossless_inter_pack as ilp, lossless_lod_pack as llp, lossless_nbr_pack as nlp
-    from nvfpcc_amd import lossless_pack as lp, network, ops
+    from nvfpcc_amd import lossless_mv_pack as mp, lossless_pack as lp, network, ops
     from nvfpcc_amd.model import Net
     from nvfpcc_amd.recon import eval_batches
     from nvfpcc_amd.seeds import synthetic_seed
@@ -114,9 +126,27 @@ def main():
         words, dropped = ops.occ_ref_words(ref_pts, ref_org)
         ref, ref_dropped = (words,), int(dropped.item())
     lod_packs, lod_info, nbr_packs, nbr_info, inter_packs, inter_info = {}, {}, {}, {}, {}, {}
+    mv_packs, mv_info, motion, ref_mv = {}, {}, {}, ()
+
+    def compensated():
+        """From the reference's points to (the vectors' pack, R'): everything --lossless_mv adds to an inter encode."""
+        own = mp.reference_blocks(ref_pts, dev)
+        mv = mp.search(mp.frame_words(gt), own, ref_org, a.mv)[0]
+        return mp.write(a.mv, mv), mp.compensated_words(own, ref_org, mv)
+    if a.mv:
+        own = mp.reference_blocks(ref_pts, dev)
+        gt_w0 = mp.frame_words(gt)
+        mv_dev, cost = mp.search(gt_w0, own, ref_org, a.mv)
+        vec_pack, rprime = compensated()
+        ref_mv = (rprime,)
+        moved = int((mv_dev != 0).any(1).sum().item())
+        motion = {"radius": a.mv, "bytes": len(vec_pack), "moved": moved, "ref_blocks": int(own[1].shape[0]),
+                  "distance": int(cost[:, 0].sum().item()), "distance_at_0": int(cost[:, 1].sum().item()),
+                  "words_equal_frame": bool(torch.equal(rprime, gt_w0))}
     coders = ([("scalable", llp, lod_packs, lod_info, ())] if a.lod else []) + \
              ([("neighbour", nlp, nbr_packs, nbr_info, ())] if a.ctx in ("nbr", "inter") else []) + \
-             ([("inter", ilp, inter_packs, inter_info, ref)] if a.ctx == "inter" else [])
+             ([("inter", ilp, inter_packs, inter_info, ref)] if a.ctx == "inter" else []) + \
+             ([("compensated inter", ilp, mv_packs, mv_info, ref_mv)] if a.mv else [])
     for what, mod, out_packs, out_info, extra in coders:
         for G in groups:
             out_packs[G], side = mod.encode_occupancy(net, lat, gt, *extra, batch=a.batch, group=G)
@@ -130,6 +160,10 @@ def main():
     routes = {"forward": forward}
     if a.ctx == "inter":
         routes["ref_words"] = lambda: ops.occ_ref_words(ref_pts, ref_org)
+    if a.mv:
+        routes["mv_ref_blocks"] = lambda: mp.reference_blocks(ref_pts, dev)
+        routes["mv_search"] = lambda: mp.search(gt_w0, own, ref_org, a.mv)
+        routes["mv_words"] = lambda: mp.compensated_words(own, ref_org, mv_dev)
     for G in groups:
         routes[f"encode_G{G}"] = lambda G=G: lp.encode_occupancy(net, lat, gt, batch=a.batch, group=G)
         routes[f"decode_G{G}"] = lambda G=G: lp.decode_occupancy(net, lat, packs[G], batch=a.batch)
@@ -138,6 +172,9 @@ def main():
                 continue
             routes[f"{tag}_encode_G{G}"] = lambda G=G, mod=mod, extra=extra: \
                 mod.encode_occupancy(net, lat, gt, *extra, batch=a.batch, group=G)
+            if tag == "inter" and a.mv:
+                routes[f"inter_mv_encode_G{G}"] = lambda G=G: \
+                    ilp.encode_occupancy(net, lat, gt, compensated()[1], batch=a.batch, group=G)
             for level in (0, 1, 2):
                 routes[f"{tag}_decode{level}_G{G}"] = lambda G=G, level=level, mod=mod, its_packs=its_packs, extra=extra: \
                     mod.decode_occupancy(net, lat, its_packs[G], *extra, level=level, batch=a.batch)
@@ -221,6 +258,7 @@ def main():
            "span_blocks": {str(G): span[G][0] for G in groups}, "packs": {str(G): v for G, v in info.items()},
            "lod_packs": {str(G): v for G, v in lod_info.items()}, "nbr_packs": {str(G): v for G, v in nbr_info.items()},
            "inter_packs": {str(G): v for G, v in inter_info.items()},
+           "inter_mv_packs": {str(G): v for G, v in mv_info.items()}, "motion": motion,
            "reference": {"points": 0 if ref_pts is None else int(ref_pts.shape[0]), "dropped": ref_dropped},
            "ms": {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
                   for k, v in times.items()}}
