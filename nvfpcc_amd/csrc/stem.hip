@@ -123,20 +123,11 @@ __global__ __launch_bounds__(C0 * 64) void stem_bwd_kernel(const float* __restri
                                         want_w, blockIdx.x, gridDim.x, lds, StemCoop{});
 }
 
-// Both finals of the stem backward in one launch: the last workgroup turns the IGDN slabs into parameter gradients
-// (fixed-order sum, re-parametrisation chain rule, LowerBound rule), the others add up0's weight-gradient slabs.
-__global__ __launch_bounds__(256) void stem_finals(StemGdnFinal f, const float* __restrict__ slab_w,
-                                                   float* __restrict__ dw, int nslab, int jtotal) {
-  if (blockIdx.x == gridDim.x - 1) {
-    stem_gdn_final_body(f, threadIdx.x, 256);
-    return;
-  }
-  const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= jtotal) return;
-  float s = 0.f;
-  for (int g = 0; g < nslab; ++g) s += slab_w[(size_t)g * jtotal + j];
-  dw[j] = s;
-}
+// The IGDN final of nvf_stem_bwd: one workgroup turns the slabs into parameter gradients (fixed-order sum,
+// re-parametrisation chain rule, LowerBound rule).  up0's weight-gradient slabs go through nvf_wgrad_reduce_multi, the
+// reduction nvf_stem_bwd_partial's callers run: one summation order for both entry points at any number of slabs (a
+// slab loop of its own here added them one after the other, which is that reduction's order up to 16 slabs only).
+__global__ __launch_bounds__(256) void stem_finals(StemGdnFinal f) { stem_gdn_final_body(f, threadIdx.x, 256); }
 
 // workspace of nvf_stem_bwd / nvf_stem_bwd_partial: IGDN slabs, up0 weight-gradient slabs, conv0 backward-data partials
 static size_t stem_ws_floats(int batch, int ch, int c0, int c1) {
@@ -189,12 +180,15 @@ extern "C" int nvf_stem_bwd(const float* g1, const float* x0, const float* a0, c
     launch_stem_bwd<16, 32>(g1, x0, a0, conv0_w_bwd, up0_w_bwd, beta_hat, gamma_hat, da0, dx0, workspace, batch, ch,
                             want_w, &slab_gdn, &slab_w, &nslab, s);
   if (want_w) {
-    const int jtotal = ch * c0 * 125;
     StemGdnFinal f{slab_gdn, beta_hat, gamma_hat, dbeta_hat, dgamma_hat, nslab, c0};
-    stem_finals<<<(jtotal + 255) / 256 + 1, 256, 0, s>>>(f, slab_w, dw_up0, nslab, jtotal);
+    stem_finals<<<1, 256, 0, s>>>(f);
   }
   NVF_LAUNCH_CHECK();
-  return NVF_OK;
+  if (!want_w) return NVF_OK;
+  const float* slabs[1] = {slab_w};
+  float* dws[1] = {dw_up0};
+  const int jtotal = ch * c0 * 125;
+  return nvf_wgrad_reduce_multi(slabs, dws, &nslab, &jtotal, 1, stream);
 }
 
 // nvf_stem_bwd without its final launch: up0's weight-gradient slabs are left to the caller's slab reduction

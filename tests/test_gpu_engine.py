@@ -906,19 +906,27 @@ def test_graph_replay_hands_over_wide_schedule_rows(gpu, collective):
     assert torch.isfinite(eng.flat_p).all()
 
 
-@pytest.mark.parametrize("batch", [16, 5, 32])
-def test_stem_backward_inside_the_five_gradient_launch(gpu, monkeypatch, batch):
-    """Round 5: the stem's backward (conv0^T -> IGDN' -> up0^T and up0's gradients) has no launch of its own -- queued in the
-    step context (nvf_stem_bwd_queue), it runs as the first workgroups of the five-gradient launch and hands dx0 to the
-    latent tail of the same launch through device-scope stores and arrival counters (csrc/stem_bwd.h).  Same arithmetic in
-    the same order: against the two-launch form every gradient is the same BITS, except up0's bias gradient, which is now a
-    per-block wave sum added over the blocks (another summation order: to rounding).  Repeated steps must leave the arrival
-    counters at zero."""
+def make_cfg(gpu, ch, channels, nblk, **seeds):
+    """An engine for any (ch, channels): the make() of tests/test_gpu_measured_path.py without its oracle copies."""
+    from tests.test_gpu_measured_path import make as make_any
+    net, eng, _, gt, dist, emb = make_any(gpu, ch, channels, nblk, **seeds)
+    return net, eng, gt, dist, emb
+
+
+def _cfg(tag):
+    """(ch, channels, seeds) of one of the two decoders of BASELINE.json, as make(tag, ...) builds them."""
+    c = CONFIGS[tag]
+    return c["ch"], c["channels"], dict(param_seed=c["param_seed"], emb_seed=c["emb_seed"])
+
+
+def _stem_backward_in_the_five_gradient_launch(gpu, monkeypatch, ch, channels, batch, **seeds):
+    """The queued stem backward against the two-launch form at (ch, channels): every gradient the same bits, except up0's
+    bias gradient (a per-block wave sum added over the blocks: to rounding); arrival counters left at zero."""
     from nvfpcc_amd import engine as E
     got = {}
     for coop in (True, False):
         monkeypatch.setattr(E, "_STEM_IN_TRUNK5", coop)
-        net, eng, gt, dist, emb = make("S", gpu, nblk=40)
+        net, eng, gt, dist, emb = make_cfg(gpu, ch, channels, 40, **seeds)
         ids = np.random.default_rng(2).permutation(40)[:batch]
         for rep in range(3):
             eng.noise_step = 0
@@ -941,19 +949,34 @@ def test_stem_backward_inside_the_five_gradient_launch(gpu, monkeypatch, batch):
             assert torch.equal(g1[o:o + m], g0[o:o + m]), name
 
 
-@pytest.mark.parametrize("q", [1, 2])
-@pytest.mark.parametrize("tag,batch", [("S", 16), ("S", 5), ("W", 16), ("W", 3)])
-def test_stem_forward_inside_the_step_head_launch(gpu, monkeypatch, tag, batch, q):
-    """Round 5: the step head (effective weights, MFMA packings, row gather, weight-rate partials) and the stem's forward
-    (latent generator + quantiser + up0 / IGDN / conv0) are ONE launch (nvf_step_head_stem): the stem's workgroups derive
-    their weights from the raw parameters with the arithmetic of the weight preparation and fetch their latents through
-    the index vector, so they wait for nothing.  Against the two-launch form: every saved activation, the latent bits, the
-    loss and every gradient are the same BITS (q = 1: the same counter-RNG draws).  Both decoders of BASELINE.json."""
+@pytest.mark.parametrize("batch", [16, 5, 32])
+def test_stem_backward_inside_the_five_gradient_launch(gpu, monkeypatch, batch):
+    """Round 5: the stem's backward (conv0^T -> IGDN' -> up0^T and up0's gradients) has no launch of its own -- queued in the
+    step context (nvf_stem_bwd_queue), it runs as the first workgroups of the five-gradient launch and hands dx0 to the
+    latent tail of the same launch through device-scope stores and arrival counters (csrc/stem_bwd.h).  Same arithmetic in
+    the same order: against the two-launch form every gradient is the same BITS, except up0's bias gradient, which is now a
+    per-block wave sum added over the blocks (another summation order: to rounding).  Repeated steps must leave the arrival
+    counters at zero."""
+    ch, channels, seeds = _cfg("S")
+    _stem_backward_in_the_five_gradient_launch(gpu, monkeypatch, ch, channels, batch, **seeds)
+
+
+@pytest.mark.parametrize("batch", [5, 32])
+@pytest.mark.parametrize("ch", [1, 5, 8])
+def test_stem_backward_inside_the_five_gradient_launch_at_other_widths(gpu, monkeypatch, ch, batch):
+    """The same at the narrow decoder's other latent widths: ch is a run-time bound of the cooperative stem backward (its
+    LDS copies, guards, shuffle groups and weight strides), and 3 was the only value it had run under a test with."""
+    _stem_backward_in_the_five_gradient_launch(gpu, monkeypatch, ch, (8, 16, 8, 8), batch)
+
+
+def _stem_forward_in_the_step_head_launch(gpu, monkeypatch, ch, channels, batch, q, **seeds):
+    """nvf_step_head_stem against the two-launch form at (ch, channels): every saved activation, the latent bits, the loss
+    and every gradient are the same bits."""
     from nvfpcc_amd import engine as E
     got = {}
     for merged in (True, False):
         monkeypatch.setattr(E, "_STEM_IN_HEAD", merged)
-        net, eng, gt, dist, emb = make(tag, gpu, nblk=40)
+        net, eng, gt, dist, emb = make_cfg(gpu, ch, channels, 40, **seeds)
         ids = np.random.default_rng(7).permutation(40)[:batch]
         a = eng.train_step(ids, q, update=False)
         torch.cuda.synchronize()
@@ -963,6 +986,29 @@ def test_stem_forward_inside_the_step_head_launch(gpu, monkeypatch, tag, batch, 
     for k in a1:
         assert torch.equal(a1[k], a0[k]), k
     assert l1 == l0 and torch.equal(g1, g0)
+
+
+@pytest.mark.parametrize("q", [1, 2])
+@pytest.mark.parametrize("tag,batch", [("S", 16), ("S", 5), ("W", 16), ("W", 3)])
+def test_stem_forward_inside_the_step_head_launch(gpu, monkeypatch, tag, batch, q):
+    """Round 5: the step head (effective weights, MFMA packings, row gather, weight-rate partials) and the stem's forward
+    (latent generator + quantiser + up0 / IGDN / conv0) are ONE launch (nvf_step_head_stem): the stem's workgroups derive
+    their weights from the raw parameters with the arithmetic of the weight preparation and fetch their latents through
+    the index vector, so they wait for nothing.  Against the two-launch form: every saved activation, the latent bits, the
+    loss and every gradient are the same BITS (q = 1: the same counter-RNG draws).  Both decoders of BASELINE.json."""
+    ch, channels, seeds = _cfg(tag)
+    _stem_forward_in_the_step_head_launch(gpu, monkeypatch, ch, channels, batch, q, **seeds)
+
+
+OTHER_WIDTHS = [(ch, (8, 16, 8, 8), batch) for ch in (1, 5, 8) for batch in (5, 32)] + [(3, (16, 32, 16, 16), 5)]
+
+
+@pytest.mark.parametrize("q", [1, 2])
+@pytest.mark.parametrize("ch,channels,batch", OTHER_WIDTHS)
+def test_stem_forward_inside_the_step_head_launch_at_other_widths(gpu, monkeypatch, ch, channels, batch, q):
+    """The same at other latent widths of the narrow decoder, and at ch = 3 on the wide one (whose up0 the route table
+    sends to the generic kernels while the stem stays fused)."""
+    _stem_forward_in_the_step_head_launch(gpu, monkeypatch, ch, channels, batch, q)
 
 
 def test_stem_jobs_survive_a_growing_five_gradient_launch(gpu):

@@ -212,7 +212,11 @@ def test_batch16_train_step_matches_the_oracle(dec, q, gpu):
 # agree with the oracle, or refuse with a message naming these
 CONFIGS3 = [(8, (8, 16, 8, 8)),       # the reference's argparse default: --ch 8 --chanstr 8,16,8,8 (NVFPCC.py:723-735)
             (4, (4, 8, 4, 4)),        # off-grid: no instantiation of the fused stem / one-launch heads / trunk5
-            (3, (8, 8, 8, 8))]        # narrow trunk, other stem
+            (3, (8, 8, 8, 8)),        # narrow trunk, other stem
+            # the fused stem at other latent widths than the two of BASELINE.json (ch is the codec's rate knob) ...
+            (1, (8, 16, 8, 8)), (5, (8, 16, 8, 8)),
+            (9, (8, 16, 8, 8)),       # ... one past its limit: per-layer stem kernels, un-queued latent tail
+            (3, (16, 32, 16, 16)), (5, (16, 32, 16, 16))]     # wide: up0 on the generic kernels under a fused stem
 
 
 @pytest.mark.parametrize("ch,channels", CONFIGS3)
