@@ -31,9 +31,13 @@ engine (nvfpcc_amd/engine.py) instead of a DataLoader + autograd loop.
     python NVFPCC.py train next.ply --freeze_decoder --load_weights q4.ckpt    # latents only, under a decoder that does not move
     python NVFPCC.py encode next.ply --load_weights q4.ckpt --ref_pack ref.pk  # a latents-only pack: 33 bytes name ref.pk's decoder
     python NVFPCC.py decode p.pk --ref_pack ref.pk ...                         # decoded under the reference's weights
+    python NVFPCC.py train scan.ply --from_ply --voxelize [--vox_step S --vox_origin X Y Z] ...    # float coordinates, repeated points
+    python NVFPCC.py encode scan.ply --from_ply --voxelize ...                 # the same flags; the lattice travels (vox_pack)
+    python NVFPCC.py decode pack.pk --source_frame ...                         # also rc_dec_src.ply, in the input's frame
 
 Additions over the reference (all optional): --device, --epochs, --seed, --ref_ply, --from_ply, --ply_format, --bits, --pack_octree, --pack_lod, --lod_heads, --lod, --lossless, --lossless_lod, --lossless_ctx, --lossless_ref, --lossless_mv, --gof, --frame_start, --frame, --freeze_decoder, --ref_pack, --thh_mode (count | block-count | d1:
-nvfpcc_amd/thh_select.py picks the occupancy threshold at encode time and a `thh_pack` key carries it); multi-GPU training when launched
+nvfpcc_amd/thh_select.py picks the occupancy threshold at encode time and a `thh_pack` key carries it), --voxelize, --vox_step,
+--vox_origin, --source_frame (nvfpcc_amd/voxelize.py: float clouds are voxelised on the device and a `vox_pack` key carries the lattice); multi-GPU training when launched
 through torch.distributed.run (one process per GPU, leaf blocks sharded, one RCCL all-reduce per step).
 Headless: no GUI window, no IPython shell.
 """
@@ -106,6 +110,33 @@ def _bits(args):
     return bits
 
 
+def _voxelize_refusals(args):
+    """--voxelize / --vox_step / --vox_origin / --source_frame after the checks that need no device and no file: what
+    does not fit together exits here, each with its own reason.  With --voxelize, args.vox_lattice becomes the lattice
+    of --vox_step / --vox_origin (nvfpcc_amd.voxelize.Lattice), or None for the cloud's own fit."""
+    from nvfpcc_amd import voxelize as vx
+    cmd = args.command
+    if hasattr(args, 'source_frame') and cmd != 'decode':
+        raise SystemExit(f"{cmd}: --source_frame is a switch of decode: it writes the decoded cloud in the frame of the "
+                         f"pack's vox_pack")
+    if not hasattr(args, 'voxelize'):
+        if hasattr(args, 'vox_step'):
+            raise SystemExit(f"{cmd}: --vox_step {args.vox_step!r} is the lattice step of --voxelize; give --voxelize too")
+        if hasattr(args, 'vox_origin'):
+            raise SystemExit(f"{cmd}: --vox_origin places the lattice of --voxelize --vox_step; give both too")
+        return
+    if cmd == 'decode':
+        raise SystemExit("decode: --voxelize belongs to train and encode; decode reads the lattice from the pack's "
+                         "vox_pack (--source_frame writes the cloud in the input's frame)")
+    if not hasattr(args, 'from_ply'):
+        raise SystemExit(f"{cmd}: --voxelize needs --from_ply: it reads the cloud itself, with float coordinates, and "
+                         f"there is no *_l5_*.npy file of such a cloud")
+    args.vox_lattice = vx.lattice_from_args(args, cmd)
+    if hasattr(args, 'gof') and args.vox_lattice is None:
+        raise SystemExit(f"{cmd}: --gof with --voxelize needs one lattice for all frames of the group, and a fit is each "
+                         f"frame's own; give --vox_step / --vox_origin")
+
+
 def _load_data(args, dev, shuffle=True):
     """The dataset of `args.input`: the three `*_l5_*.npy` files next to it, or -- with --from_ply -- the cloud itself,
     pre-processed on the device (nothing is read from or written to disk besides the PLY).  -> (dataset, the
@@ -115,7 +146,18 @@ def _load_data(args, dev, shuffle=True):
     def one(name):
         if getattr(args, 'from_ply', False):
             from nvfpcc_amd import ply_io, preprocess as pp
-            pre = pp.preprocess_device(ply_io.read_ply(name, device=dev)[0], dev, bits=getattr(args, 'bits', 10))
+            if hasattr(args, 'voxelize'):   # float coordinates: the distinct lattice points stand for the cloud from here on
+                from nvfpcc_amd import voxelize as vx
+                try:
+                    vox = vx.voxelize(ply_io.read_ply(name, coords='float')[0], dev, bits=getattr(args, 'bits', 10),
+                                      lattice=args.vox_lattice)
+                except (OSError, ValueError) as e:
+                    raise SystemExit(f"--voxelize {name}: {e}")
+                pre = pp.preprocess_device(vox.points, dev, bits=vox.lattice.bits)
+                pre.vox_lattice, pre.vox_line = vox.lattice, vx.voxelize_line(vox)
+                print(pre.vox_line)
+            else:
+                pre = pp.preprocess_device(ply_io.read_ply(name, device=dev)[0], dev, bits=getattr(args, 'bits', 10))
             return LoadedVoxelDataset.from_device(pre, shuffle=shuffle), pre
         fid = name[:-4]
         return LoadedVoxelDataset(f'{fid}_l5_origins.npy', f'{fid}_l5_gt_grid.npy', f'{fid}_l5_dist.npy',
@@ -123,6 +165,9 @@ def _load_data(args, dev, shuffle=True):
     if hasattr(args, 'gof'):    # the frames' blocks, frame-major, as one dataset; its frame(k) carries frame k's `pre`
         from nvfpcc_amd import gof
         frames, pres = zip(*[gof.quiet(one, name) for name in _gof_names(args)])
+        for pre in pres:            # (quiet dropped them with the frames' [data] lines)
+            if getattr(pre, 'vox_line', None):
+                print(pre.vox_line)
         return gof.GofDataset(frames, shuffle=shuffle, pres=pres), None
     return one(args.input)
 
@@ -217,6 +262,7 @@ FIT_LINE = '[Fit %04d %.1f seconds] J: %.9e improved: %d / %d b_latent: %.4f'
 def train(args):
     from nvfpcc_amd import dist as nd, ops
     from nvfpcc_amd.engine import TrainEngine, EpochDriver
+    _voxelize_refusals(args)
     if hasattr(args, 'freeze_decoder'):
         return fit_frozen(args)
     peak = (1 << _bits(args)) - 1
@@ -310,6 +356,7 @@ TEST_LINE = ('[Epoch %04d TEST %.1f seconds] Loss: %.4e PosiPenal: %.4f PosiGain
 def encode(args):
     """Pack everything the decoder needs (NVFPCC.py:395-554)."""
     from nvfpcc_amd import weight_codec
+    _voxelize_refusals(args)
     lossless_ctx_refusals(args)
     bits = _bits(args)
     names = _gof_names(args)
@@ -421,6 +468,10 @@ def _encode_frame(args, net, net_weight_pack, emb, data, pre, dev, bits, fmt, st
         total_pack['lossless_lod_pack'] = lossless_lod['pack']
         if 'mv_pack' in lossless_lod:       # --lossless_mv: the vectors the reference words were fetched under
             total_pack['lossless_mv_pack'] = lossless_lod['mv_pack']
+    lattice = getattr(pre, 'vox_lattice', None)
+    if lattice is not None:                 # --voxelize: the lattice the points lie on, for decode --source_frame
+        from nvfpcc_amd import voxelize as vx
+        total_pack['vox_pack'] = vx.pack(lattice)
     frame_pack = {k: v for k, v in total_pack.items() if k != 'net_weight_pack'}
     if write_pack is not None:
         write_pack(frame_pack)
@@ -440,6 +491,7 @@ def _encode_frame(args, net, net_weight_pack, emb, data, pre, dev, bits, fmt, st
     side_bits = (0 if sel is None else 8 * len(sel['pack'])) + 8 * len(total_pack.get('octree_pack', b''))
     side_bits += 8 * len(total_pack.get('lod_pack', b'')) + 8 * len(total_pack.get('lossless_pack', b''))
     side_bits += 8 * len(total_pack.get('lossless_lod_pack', b'')) + 8 * len(total_pack.get('lossless_mv_pack', b''))
+    side_bits += 8 * len(total_pack.get('vox_pack', b''))
     if sel is not None:
         print(sel['line'])
     if write_pack is not None:
@@ -447,7 +499,7 @@ def _encode_frame(args, net, net_weight_pack, emb, data, pre, dev, bits, fmt, st
     print('[Recon] Pacc: %.4f Nacc: %.4f MSE1: %.4f PSNR1: %.4f' % (
         m[0] / max(m[1], 1), m[2] / max(m[3], 1), *_psnr1(m[4], m[5], (1 << bits) - 1)))
     ply_io.write_ply(stem + '.ply', pts, fmt=fmt, device=dev)
-    _print_pc_error(args, pts, dev)
+    _print_pc_error(args, pts, dev, lattice=lattice)
     if lod is not None:
         for level, (line, lod_pts) in enumerate(zip(lod['lines'], lod['points']), 1):
             print(line)
@@ -617,6 +669,7 @@ def decode(args):
     if hasattr(args, 'lossless_mv'):
         raise SystemExit(f"decode: --lossless_mv {args.lossless_mv} is the search radius of encode; decode reads the "
                          f"vectors from the pack's lossless_mv_pack")
+    _voxelize_refusals(args)
     lossless_refusals(args, None)
     lossless_lod_refusals(args, None)
     fmt = getattr(args, 'ply_format', 'ascii')
@@ -689,6 +742,16 @@ def _decode_pack(args, total_pack, dev, fmt, net, out_fn):
     from nvfpcc_amd.recon import reconstruct_points, reconstruct_points_lod
     lossless_refusals(args, total_pack)
     lossless_lod_refusals(args, total_pack)
+    lattice = None
+    if 'vox_pack' in total_pack:            # read only for --source_frame and --ref_ply; the decoded cloud does not depend on it
+        from nvfpcc_amd import voxelize as vx
+        try:
+            lattice = vx.unpack(total_pack['vox_pack'])
+        except ValueError as e:
+            raise SystemExit(f"decode {args.input}: {e}")
+    elif hasattr(args, 'source_frame'):
+        raise SystemExit(f"decode --source_frame: {args.input} carries no vox_pack (it was encoded without --voxelize): its "
+                         f"cloud has no other frame than the lattice")
     lod, lod_side = getattr(args, 'lod', 0), None
     if lod:
         from nvfpcc_amd import lod_pack as lp
@@ -759,8 +822,10 @@ def _decode_pack(args, total_pack, dev, fmt, net, out_fn):
         if block_counts is not None:
             print(ts.threshold_line('block-count', block_counts=block_counts, thresholds=torch.cat(used).cpu().numpy()))
     ply_io.write_ply(out_fn, pts, fmt=fmt, device=dev)
+    if hasattr(args, 'source_frame'):       # the same points in the input's frame; at level L the step is s 2^L
+        ply_io.write_ply_float(out_fn.replace('rc_dec', 'rc_dec_src', 1), vx.to_source(pts, lattice, dev, level=level), fmt)
     if args.ref_ply is not None:
-        _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins), lod=level)
+        _print_pc_error(args, pts, dev, bits=_pack_bits(total_pack, origins), lod=level, lattice=lattice)
 
 
 def _decoder_from_pack(args, total_pack, dev, net=None, lod_side=None):
@@ -851,16 +916,25 @@ def _pack_bits(total_pack, origins):
     raise SystemExit(f"--ref_ply: the pack's leaf cubes reach coordinate {top}, beyond 12 bits per axis")
 
 
-def _print_pc_error(args, pts, dev, bits=10, lod=0):
+def _print_pc_error(args, pts, dev, bits=10, lod=0, lattice=None):
     """--ref_ply: symmetric D1 / D2 geometry PSNR of the written cloud against the original (nvfpcc_amd.pc_metrics);
     `bits` is the domain of both clouds, and the peak of the PSNR is 2^bits - 1.  lod > 0: `pts` lie on the lattice of
     bits - lod bits per axis; the original is reduced to it (>> lod, duplicates removed: its normals do not survive,
-    D2 uses estimated ones) and bits - lod is the domain and the peak."""
+    D2 uses estimated ones) and bits - lod is the domain and the peak.  lattice (encode --voxelize, decode of a pack with
+    vox_pack): the original has float coordinates; it is voxelised under that lattice, never under a fit of its own,
+    and scored on the lattice (its normals do not survive the merging of points either)."""
     if args.ref_ply is None:
         return
     from nvfpcc_amd import ply_io
     from nvfpcc_amd.pc_metrics import geometry_psnr
-    ref, ref_normals = ply_io.read_ply(args.ref_ply, device=dev, normals=True)      # ASCII or binary
+    if lattice is not None:
+        from nvfpcc_amd import voxelize as vx
+        try:
+            ref, ref_normals = vx.voxelize(ply_io.read_ply(args.ref_ply, coords='float')[0], dev, lattice=lattice).points, None
+        except (OSError, ValueError) as e:
+            raise SystemExit(f"--ref_ply {args.ref_ply}: {e}")
+    else:
+        ref, ref_normals = ply_io.read_ply(args.ref_ply, device=dev, normals=True)      # ASCII or binary
     if lod:
         from nvfpcc_amd.recon import reduce_to_lattice
         ref = ref.cpu().numpy() if isinstance(ref, torch.Tensor) else ref
@@ -980,6 +1054,18 @@ def build_parser():
     p.add_argument('--ply_format', choices=['ascii', 'binary'], default=argparse.SUPPRESS,
                    help='encode / decode: format of the rc_*.ply files written.  ascii (also when absent): double x y z '
                         'as text; binary: binary_little_endian with float x y z.')
+    p.add_argument('--voxelize', action='store_true', default=argparse.SUPPRESS,
+                   help='train / encode --from_ply: the input has float coordinates in a frame of its own and may repeat '
+                        'points.  It is voxelised on the device (nvfpcc_amd.voxelize) to --bits bits per axis, under the '
+                        'lattice of --vox_step / --vox_origin or under its own fit; every count downstream is the number '
+                        'of distinct voxels.  encode carries the lattice in the pack (vox_pack, 34 bytes, counted in '
+                        'Gross bpp).  Give train and encode the same flags.')
+    from nvfpcc_amd.voxelize import add_lattice_arguments
+    add_lattice_arguments(p)
+    p.add_argument('--source_frame', action='store_true', default=argparse.SUPPRESS,
+                   help='decode of a pack with vox_pack: also write rc_dec_src.ply (rc_dec_src_<number>.ply for a group), '
+                        'the decoded points in the input\'s frame, origin + q * step, as float64 in --ply_format.  With '
+                        '--lod / --lossless_lod L the step is 2^L times the pack\'s.')
     p.add_argument('--ref_ply', default=None,
                    help='Original cloud (ASCII or binary PLY): encode / decode also print its D1 / D2 geometry PSNR.')
     return p

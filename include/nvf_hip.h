@@ -1161,6 +1161,42 @@ int nvf_ply_parse_xyz(const uint8_t* text, int64_t nbytes, const int64_t* starts
 int nvf_ply_format_sizes(const int32_t* xyz, int64_t n, int32_t* sizes, void* stream);
 int nvf_ply_format_xyz(const int32_t* xyz, const int64_t* offsets, int64_t n, uint8_t* text, int64_t nbytes, void* stream);
 
+/* ---- voxelisation of a float cloud (nvfpcc_amd/voxelize.py, csrc/voxelize.hip) ---------------------------------------
+ * float64 [n, 3] points under the lattice (bits, o, s) -> the distinct lattice points, their counts and the error.  The
+ * arithmetic is the format: t = x - o, u = t * inv, q = floor(u + 0.5) forward and x = o + q * s back,
+ * every operation rounded to float64 on its own (the file is compiled with contraction off).  inv is 1.0 / s, divided
+ * once by the caller.  A point is NON-FINITE if a coordinate is a NaN or an infinity, else OUTSIDE if some u + 0.5 is
+ * below 0 or at least 2^bits (decided in float64), else INSIDE.  Call order: (bounds, when the lattice is to be fitted,)
+ * quantize, (sort the keys ascending), unique.  Every call returns NVF_EINVAL before any HIP call on a null pointer, n
+ * outside [1, 2^30), bits outside 10..12, s or inv not finite and above 0, or a non-finite origin, where it takes them.
+ * A lowest-index word is -1 when there is no such point.
+ * nvf_vox_bounds: bounds, 8-byte words [NVF_VOX_BOUNDS_WORDS]: [0..2] the minimum and [3..5] the maximum of each axis
+ *   over the finite points as doubles (+inf / -inf when there is none), [6] the count of non-finite points, [7] the
+ *   lowest index of one.  work [NVF_VOX_BOUNDS_WORK_WORDS] is scratch: one partial record per workgroup, folded by a
+ *   final one-workgroup launch.  min and max are exact in any order; no atomics.
+ * nvf_vox_quantize: q int32 [n, 3] and keys int64 [n]: for a point inside, its q and key = q0 << 2 bits | q1 << bits |
+ *   q2 (30, 33 or 36 bits); for any other, q = -1 and key = INT64_MAX, which sorts last.  status, 8-byte words
+ *   [NVF_VOX_STATUS_WORDS], cleared and written by the call: [0] non-finite points, [1] outside points, [2] and [3] the
+ *   lowest index of either kind, [4] the maximum as a double and [8 + g], g < [6], the sum per workgroup, also doubles,
+ *   of e2 = sum over axes 0, 1, 2 of (x - (o + q s))^2 over the points inside (each partial summed in a fixed order:
+ *   the same call gives the same bits), [5] written by nvf_vox_unique, [6] the number of partial sums, [7] zero.
+ * nvf_vox_unique: sorted_keys int64 [n] ascending -> pts int32 [M, 3] (room for n rows), the distinct points inside in
+ *   ascending key order, counts int32 [M] (room for n) how many keys each had, and M in status[5].  Keys of INT64_MAX
+ *   belong to no point.  work int32 [NVF_VOX_MAX_GROUPS] is scratch.  Three launches: sums per workgroup, one workgroup
+ *   scans them, emit; no workgroup waits for another.  A run of equal keys may be longer than a workgroup's span and may
+ *   straddle two: its count is the difference of two indices, each added by the workgroup that holds that end.
+ * nvf_vox_dequantize: xyz float64 [n, 3] = o + q * s for q int32 [n, 3], any integers. */
+#define NVF_VOX_MAX_GROUPS 1024
+#define NVF_VOX_STATUS_WORDS (8 + NVF_VOX_MAX_GROUPS)
+#define NVF_VOX_BOUNDS_WORDS 8
+#define NVF_VOX_BOUNDS_WORK_WORDS (NVF_VOX_BOUNDS_WORDS * NVF_VOX_MAX_GROUPS)
+int nvf_vox_bounds(const double* xyz, int n, int64_t* bounds, int64_t* work, void* stream);
+int nvf_vox_quantize(const double* xyz, int n, int bits, double ox, double oy, double oz, double s, double inv, int32_t* q,
+                     int64_t* keys, int64_t* status, void* stream);
+int nvf_vox_unique(const int64_t* sorted_keys, int n, int bits, int32_t* pts, int32_t* counts, int64_t* status,
+                   int32_t* work, void* stream);
+int nvf_vox_dequantize(const int32_t* q, int n, double ox, double oy, double oz, double s, double* xyz, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -191,7 +191,7 @@ def extract(total_pack, k):
     return {'net_weight_pack': total_pack['net_weight_pack'], **frames[k]}
 
 
-SIDE_KEYS = ('thh_pack', 'octree_pack', 'lod_pack', 'lossless_pack', 'lossless_lod_pack')
+SIDE_KEYS = ('thh_pack', 'octree_pack', 'lod_pack', 'lossless_pack', 'lossless_lod_pack', 'vox_pack')
 
 
 def frame_bits(frame_pack):

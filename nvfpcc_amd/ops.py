@@ -1981,3 +1981,80 @@ def ply_format_xyz(xyz, guard=0):
     if nbytes:
         check(lib().nvf_ply_format_xyz(_ptr(xyz), _ptr(offsets), n, _ptr(text), nbytes, _stream()), "nvf_ply_format_xyz")
     return (text, nbytes) if guard else text
+
+
+# ---- voxelisation of a float cloud (csrc/voxelize.hip; the definition: nvfpcc_amd/voxelize.py) ----------------------------
+VOX_STATUS_WORDS, VOX_BOUNDS_WORDS = _K["NVF_VOX_STATUS_WORDS"], _K["NVF_VOX_BOUNDS_WORDS"]
+VOX_BOUNDS_WORK_WORDS, VOX_MAX_GROUPS = _K["NVF_VOX_BOUNDS_WORK_WORDS"], _K["NVF_VOX_MAX_GROUPS"]
+
+
+def _vox_xyz(xyz):
+    _chk(xyz)
+    if xyz.dtype != torch.float64 or xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.shape[0] == 0:
+        raise RuntimeError("voxelize: points must be float64 [n, 3], n >= 1")
+
+
+def vox_bounds(xyz):
+    """xyz float64 [n, 3] on the device -> (lo, hi: float64 numpy [3] over the finite points, the count of non-finite
+    points, the lowest index of one or -1): nvf_vox_bounds, and one read of its 64-byte record."""
+    _vox_xyz(xyz)
+    bounds = torch.empty(VOX_BOUNDS_WORDS, dtype=torch.int64, device=xyz.device)
+    work = torch.empty(VOX_BOUNDS_WORK_WORDS, dtype=torch.int64, device=xyz.device)
+    check(lib().nvf_vox_bounds(_ptr(xyz), xyz.shape[0], _ptr(bounds), _ptr(work), _stream()), "nvf_vox_bounds")
+    b = bounds.cpu().numpy()
+    return b[0:3].view("f8").copy(), b[3:6].view("f8").copy(), int(b[6]), int(b[7])
+
+
+def vox_quantize(xyz, bits, origin, step, inv):
+    """-> (q int32 [n, 3], keys int64 [n], status int64 [VOX_STATUS_WORDS]) on the device: nvf_vox_quantize."""
+    _vox_xyz(xyz)
+    n, dev = xyz.shape[0], xyz.device
+    q = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    keys = torch.empty(n, dtype=torch.int64, device=dev)
+    status = torch.empty(VOX_STATUS_WORDS, dtype=torch.int64, device=dev)
+    ox, oy, oz = (float(v) for v in origin)
+    check(lib().nvf_vox_quantize(_ptr(xyz), n, int(bits), ox, oy, oz, float(step), float(inv), _ptr(q), _ptr(keys),
+                                 _ptr(status), _stream()), "nvf_vox_quantize")
+    return q, keys, status
+
+
+def vox_unique(sorted_keys, bits, status):
+    """sorted_keys int64 [n] ascending -> (points int32 [n, 3], counts int32 [n]) on the device, of which the first
+    M = status[5] rows are written: nvf_vox_unique."""
+    _chk(sorted_keys, status)
+    if sorted_keys.dtype != torch.int64 or sorted_keys.dim() != 1 or sorted_keys.numel() == 0:
+        raise RuntimeError("vox_unique: keys must be int64 [n], n >= 1")
+    if status.dtype != torch.int64 or status.numel() != VOX_STATUS_WORDS:
+        raise RuntimeError("vox_unique: status must be the record vox_quantize made")
+    n, dev = sorted_keys.numel(), sorted_keys.device
+    pts = torch.empty((n, 3), dtype=torch.int32, device=dev)
+    counts = torch.empty(n, dtype=torch.int32, device=dev)
+    work = torch.empty(VOX_MAX_GROUPS, dtype=torch.int32, device=dev)
+    check(lib().nvf_vox_unique(_ptr(sorted_keys), n, int(bits), _ptr(pts), _ptr(counts), _ptr(status), _ptr(work),
+                               _stream()), "nvf_vox_unique")
+    return pts, counts
+
+
+def vox_status(status):
+    """The status record on the host (one copy, one sync) as a dict: nonfinite, outside, first_nonfinite,
+    first_outside, max_err2, voxels, sum_err2 (the workgroups' partial sums, added in their order)."""
+    s = status.cpu().numpy()
+    groups = int(s[6])
+    total = 0.0
+    for p in s[8:8 + groups].view("f8").tolist():
+        total += p
+    return {"nonfinite": int(s[0]), "outside": int(s[1]), "first_nonfinite": int(s[2]), "first_outside": int(s[3]),
+            "max_err2": float(s[4:5].view("f8")[0]), "voxels": int(s[5]), "sum_err2": total}
+
+
+def vox_dequantize(q, origin, step):
+    """q int32 [n, 3] on the device -> origin + q * step, float64 [n, 3]: nvf_vox_dequantize."""
+    _chk(q)
+    if q.dtype != torch.int32 or q.dim() != 2 or q.shape[1] != 3:
+        raise RuntimeError("vox_dequantize: lattice points must be int32 [n, 3]")
+    xyz = torch.empty((q.shape[0], 3), dtype=torch.float64, device=q.device)
+    if q.shape[0]:
+        ox, oy, oz = (float(v) for v in origin)
+        check(lib().nvf_vox_dequantize(_ptr(q), q.shape[0], ox, oy, oz, float(step), _ptr(xyz), _stream()),
+              "nvf_vox_dequantize")
+    return xyz

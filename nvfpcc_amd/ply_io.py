@@ -1,12 +1,15 @@
 """PLY files in and out: ASCII bodies parsed and formatted on the device, binary PLY on the host.
 
-    read_ply(path, device=None, normals=False, fallback=True) -> (xyz, normals or None)
+    read_ply(path, device=None, normals=False, fallback=True, coords="int" | "float") -> (xyz, normals or None)
     write_ply(path, points, fmt="ascii" | "binary", device=None)
+    write_ply_float(path, xyz, fmt="ascii" | "binary")
     parse_header(raw, path) -> Header
 
 Formats: ascii, binary_little_endian, binary_big_endian; x, y, z are found by property name in the `vertex` element and
 need not come first or in that order; elements before and after `vertex` are skipped (before it, in a binary file, they
-must not hold list properties: their size is unknown without walking them).  Coordinates are integers.
+must not hold list properties: their size is unknown without walking them).  Coordinates are integers, unless
+read_ply is asked for coords="float": then they come back as float64 on the host, whatever they are (NaN and infinities
+included: nvfpcc_amd.voxelize refuses them), and write_ply_float writes such a cloud; both on the host.
 
 With a HIP device the body of an ASCII file goes up as bytes and the kernels of csrc/ply_io.hip (ops.ply_parse_xyz) turn
 it into an int32 tensor [n, 3] there; write_ply formats an int32 tensor into the text of the file there
@@ -24,6 +27,7 @@ on both routes.
 """
 import io
 import re
+import warnings
 from collections import namedtuple
 
 import numpy as np
@@ -105,8 +109,9 @@ def _record(element, order):
     return np.dtype([(f"p{i}", order + _NP[p.type]) for i, p in enumerate(element.props)])
 
 
-def _read_binary(arr, header, path, normals):
-    """xyz int64 [n, 3] (and nx ny nz float64 [n, 3], when asked for and present) of a binary PLY held in `arr`."""
+def _read_binary(arr, header, path, normals, coords="int"):
+    """xyz int64 [n, 3] (float64, as stored, with coords="float"; and nx ny nz float64 [n, 3], when asked for and present)
+    of a binary PLY held in `arr`."""
     order = "<" if header.format == "binary_little_endian" else ">"
     vi, v, col = _vertex(header)
     offset = header.body + sum(e.count * _record(e, order).itemsize for e in header.elements[:vi])
@@ -118,12 +123,12 @@ def _read_binary(arr, header, path, normals):
     rows = np.frombuffer(arr, dtype=rec, count=v.count, offset=offset)
     xyz = np.stack([rows[f"p{col[a]}"].astype(np.float64) for a in ("x", "y", "z")], 1) if v.count else \
         np.zeros((0, 3), np.float64)
-    if not np.all(np.isfinite(xyz)) or np.any(xyz != np.round(xyz)):
+    if coords == "int" and (not np.all(np.isfinite(xyz)) or np.any(xyz != np.round(xyz))):
         raise ValueError(f"{path}: coordinates must be integers")
     nrm = None
     if normals and all(a in col for a in ("nx", "ny", "nz")):
         nrm = np.stack([rows[f"p{col[a]}"].astype(np.float64) for a in ("nx", "ny", "nz")], 1).reshape(-1, 3)
-    return xyz.astype(np.int64), nrm
+    return (xyz.reshape(-1, 3) if coords == "float" else xyz.astype(np.int64)), nrm
 
 
 def _gpu(device):
@@ -145,23 +150,47 @@ def _on_device(xyz, dev):
     return torch.from_numpy(xyz.astype(np.int32) if fits else xyz).to(dev)
 
 
-def _ascii_normals(arr, header, path):
-    """nx ny nz float64 [n, 3] of an ASCII body by np.loadtxt, for a file whose vertex lines the device parser has
-    already found complete (so no vertex line is blank, and loadtxt's rows are the vertex lines)."""
+def _ascii_normals(arr, header, path, names=("nx", "ny", "nz")):
+    """nx ny nz (or the columns `names`) float64 [n, 3] of an ASCII body by np.loadtxt, for a file whose vertex lines
+    the device parser has already found complete (so no vertex line is blank, and loadtxt's rows are the vertex lines)."""
     vi, v, col = _vertex(header)
     body = arr[header.body:].tobytes()
     pos = 0
     for _ in range(sum(e.count for e in header.elements[:vi])):
         pos = body.find(b"\n", pos) + 1
     return np.loadtxt(io.BytesIO(body[pos:]), dtype=np.float64, comments=None, max_rows=v.count,
-                      usecols=(col["nx"], col["ny"], col["nz"]), ndmin=2).reshape(-1, 3)
+                      usecols=tuple(col[a] for a in names), ndmin=2).reshape(-1, 3)
 
 
-def read_ply(path, device=None, normals=False, fallback=True):
+def _read_float(arr, header, path, normals):
+    """coords="float": (xyz float64 [n, 3], normals or None) on the host.  Binary files through the record path; ASCII
+    bodies through np.loadtxt on the x, y, z columns by name (it skips blank lines, as the host reader of the integer
+    route does)."""
+    if header.format != "ascii":
+        return _read_binary(arr, header, path, normals, coords="float")
+    vi, v, col = _vertex(header)
+    if v.count == 0:
+        return np.zeros((0, 3), np.float64), None
+    try:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", UserWarning)        # loadtxt announces every blank line it skips
+            xyz = _ascii_normals(arr, header, path, ("x", "y", "z"))
+            nrm = _ascii_normals(arr, header, path) if normals and all(a in col for a in ("nx", "ny", "nz")) else None
+    except ValueError as e:
+        raise ValueError(f"{path}: {e}") from None
+    if xyz.shape[0] != v.count:
+        raise ValueError(f"{path}: PLY holds fewer vertex values than its header declares ({xyz.shape[0]} of {v.count})")
+    return xyz, nrm
+
+
+def read_ply(path, device=None, normals=False, fallback=True, coords="int"):
     """(xyz, normals or None) of an ASCII or binary PLY.  With a HIP `device`, xyz is an int32 tensor [n, 3] on it (int64
     in the one case of _on_device); without, int64 numpy.  normals=True: float64 numpy [n, 3] when the file has nx ny nz.
     fallback=False: an ASCII file outside the device parser's grammar raises ValueError instead of going to the host
-    reader."""
+    reader.  coords="float": the coordinates as the file holds them, widened to float64 numpy [n, 3] on the host
+    (`device` and `fallback` are not read; NaN and infinities pass through)."""
+    if coords not in ("int", "float"):
+        raise ValueError(f"coords must be 'int' or 'float', got {coords!r}")
     dev = _gpu(device)
     arr = np.fromfile(path, dtype=np.uint8)
     try:
@@ -170,6 +199,8 @@ def read_ply(path, device=None, normals=False, fallback=True):
         if arr.size <= _HEAD_BYTES:
             raise
         header = parse_header(arr.tobytes(), path)
+    if coords == "float":
+        return _read_float(arr, header, path, normals)
     if header.format != "ascii":
         xyz, nrm = _read_binary(arr, header, path, normals)
         return (xyz if dev is None else _on_device(xyz, dev)), nrm
@@ -247,3 +278,24 @@ def write_ply(path, points, fmt="ascii", device=None):
             torch.from_numpy(out[len(head):]).copy_(text)       # one device-to-host copy, into the file's buffer
     with open(path, "wb") as f:
         f.write(memoryview(out))                                # one write
+
+
+def write_ply_float(path, xyz, fmt="ascii"):
+    """Writes points [n, 3] (numpy or tensor) with float64 coordinates as a PLY, on the host.  fmt="binary":
+    binary_little_endian, double x y z; fmt="ascii": "%.17g" per coordinate, which reads back to the same float64.
+    read_ply(path, coords="float") returns the very bits, -0.0, NaN and infinities included."""
+    if fmt not in ("ascii", "binary"):
+        raise ValueError(f"fmt must be 'ascii' or 'binary', got {fmt!r}")
+    a = xyz.detach().cpu().numpy() if isinstance(xyz, torch.Tensor) else np.asarray(xyz)
+    if a.ndim != 2 or a.shape[1] != 3 or a.dtype.kind not in "fiu":
+        raise ValueError(f"write_ply_float: expected points of shape [n, 3], got {a.dtype} {a.shape}")
+    a = np.ascontiguousarray(a, np.float64)
+    form = "ascii" if fmt == "ascii" else "binary_little_endian"
+    head = (f"ply\nformat {form} 1.0\ncomment Created by nvfpcc_amd\nelement vertex {a.shape[0]}\n"
+            f"property double x\nproperty double y\nproperty double z\nend_header\n").encode("ascii")
+    with open(path, "wb") as f:
+        f.write(head)
+        if fmt == "binary":
+            f.write(a.astype("<f8").tobytes())
+        else:
+            f.write("".join("%.17g %.17g %.17g\n" % tuple(r) for r in a.tolist()).encode("ascii"))
